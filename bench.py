@@ -9,9 +9,15 @@ trapdoor per proof and step) through
     bzh_prove_batch       (create_proof for the batch in lockstep: every MSM, NTT, gate evaluation, scan and IPA round
                            is one launch for the batch; transcript included; proof bytes back on the host)
 both INSIDE the timed region.  `proof_k11` is the ShotCircuit at the reference's own size (benches/shot.rs:22),
-`proof_k12` the BoardCircuit at its own size (benches/board.rs:22), `proof_k17` the Board scale-up.  After the timed
-region the last batch of every thread is checked with bzh_verify_batch (untimed).
+`proof_k12` the BoardCircuit at its own size (benches/board.rs:22), `proof_k17` the Board scale-up.  With `--full`, after
+the timed region the last batch of every thread is checked with bzh_verify_batch (untimed).
 `--batch 1 --concurrency 1` is the single-proof latency configuration.
+
+A plain run sets up, warms up, times `--steps` steps and prints the one JSON line (`value`, `ms_per_step`, the kernel
+classes' HIP-event times of the timed region).  `--full` adds what takes work of its own after the timed region: the CPU
+baselines, the other workloads of BASELINE.json's metric, the single-batch-in-flight roofline, the verification of the last
+batches and the decode check of the proof records.  `--dump-outputs DIR` writes what the last timed step computed (the proofs
+and public inputs of the proof workloads) as float32 .npy files, for comparing two builds on the same seeded inputs.
 
 `mixed_board_shot` is BASELINE.json configs[3]: a FIXED batch of 256 Board (k = 14) + 2560 Shot (k = 11) proofs per step
 (divided by --mix-divisor), sharded over the ranks with bzh2.shard.shard_range (strong scaling), gathered as
@@ -99,6 +105,24 @@ import torch  # noqa: E402
 import bzh2  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
+DUMP_BYTES = 64_000_000  # --dump-outputs: every file together
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: every array (unsigned integers below 2^24, rows first) as out_dir/<name>.npy in float32, which holds them
+    exactly.  An array over its share of the budget is cut to a fixed, seeded sample of its rows -- the same rows in every run
+    of the same shape --, whose numbers go to out_dir/<name>_rows.npy."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1) - 1024           # less the two .npy headers
+    for name, a in arrays.items():
+        if 4 * a.size > share:
+            row_bytes = 4 * (a.size // a.shape[0])
+            rows = np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], share // (row_bytes + 8), replace=False)
+            rows.sort()
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 def pin_to_gpu_numa(local_rank):
@@ -185,11 +209,18 @@ def parse():
                     help="world size 1: still join a process group on --dist-backend (nccl = RCCL) and run the record all_gather, the "
                          "barriers and the MAX all_reduce of the multi-GPU path (tests/test_gpu_bench_ranks.py: the first 8-GPU run must "
                          "not be the first time that code executes)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure, after the timed region: the CPU baselines, the other workloads "
+                         "(--other-workloads auto), the single-batch-in-flight roofline, bzh_verify_batch of the last batches and the "
+                         "decode check of the proof records.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; "
+                         "a fixed, seeded sample of rows where the whole would exceed 64 MB, its row numbers in DIR/<name>_rows.npy)")
     ap.add_argument("--other-workloads", default="auto", choices=["auto", "all", "none"],
                     help="after the main timed region, short regions for the rest of BASELINE.json's metric -- proof_k11 (Shot 128 x 8), "
                          "proof_k12, proof_k17 (8 x 4), verify_k14, msm24 and ntt22 on vesta and bn254 -- reported under "
-                         "config.other_workloads, each with its own roofline and cpu_baseline.  auto: when the main workload is the default "
-                         "proof_k14 at the default batch / concurrency; with several ranks only the proof sizes run (weak scaling)")
+                         "config.other_workloads, each with its own roofline and cpu_baseline.  auto: with --full, when the main workload is "
+                         "the default proof_k14 at the default batch / concurrency; with several ranks only the proof sizes run (weak scaling)")
     ap.add_argument("--concurrency", type=int, default=4,
                     help="proof_k* workloads: independent proofs in flight per GPU (host threads, one ctx + stream each)")
     return ap.parse_args()
@@ -381,6 +412,19 @@ class ProofRunner:
         a = np.frombuffer(b"".join(r for _, r in items), dtype=np.uint8).reshape(len(items), -1)
         return torch.from_numpy(a.copy()).to(self.device)
 
+    def step_outputs(self):
+        """the last step's proofs of this rank in index order, as the callers of bzh_synthesize_* / bzh_prove_batch receive them:
+        the proof bytes (zero-padded to the key's largest proof), their lengths, and the public inputs (16-bit chunks of each
+        canonical value, least significant first)"""
+        items = sorted(((lo + j, insts[j], pr) for batches in self.step_batches for lo, insts, proofs in batches
+                        for j, pr in enumerate(proofs)), key=lambda it: it[0])
+        proofs = np.zeros((len(items), self.proof_stride), dtype=np.uint8)
+        for i, (_, _, pr) in enumerate(items):
+            proofs[i, :len(pr)] = np.frombuffer(pr, dtype=np.uint8)
+        inst = np.array([[np.frombuffer(int(v).to_bytes(32, "little"), dtype="<u2") for col in insts for v in col] for _, insts, _ in items],
+                        dtype=np.uint16)
+        return {"proofs": proofs, "proof_lengths": np.array([len(pr) for _, _, pr in items], dtype=np.uint32), "instances": inst}
+
     def verify_last(self):
         ok = True
         for wi in range(len(self.ctxs)):
@@ -482,10 +526,12 @@ class Workload:
             self.runner.plan(0, batch)[0]()
             self.insts, self.proofs = self.runner.last_insts[0], self.runner.last_batch[0]
             self.accepted = 0
+            self.verdicts = []
 
             def verify():
                 res = self.runner.pks[0].verify_batch(self.insts, self.proofs)
                 self.accepted = sum(res)
+                self.verdicts = res
             self.calls = [("bzh_verify_batch", verify)]
             self.units_per_step = batch
             self.alg_bytes_msm_launch = 0
@@ -569,6 +615,31 @@ class Workload:
     def step(self):
         for _, fn in self.calls:
             fn()
+
+    def outputs(self):
+        """what a caller of the step holds after it, as integer arrays with rows first (--dump-outputs): the proof workloads'
+        proofs and public inputs, the verifier's verdicts, else the MSM results (affine, so that the point and not its Jacobian
+        representation is compared) and the transformed columns as 16-bit chunks of their limbs"""
+        if hasattr(self, "provers"):
+            return {"%s_%s" % (p.kind, name): a for p in self.provers for name, a in p.step_outputs().items()}
+        if self.name.startswith("proof_k"):
+            return self.runner.step_outputs()
+        if self.name.startswith("verify_k"):
+            return {"verdicts": np.array(self.verdicts, dtype=np.uint8)}
+        torch.cuda.synchronize()
+
+        def chunks(t):
+            return np.ascontiguousarray(t.cpu().numpy()).view(np.uint16).reshape(-1, 16)
+        out = {}
+        if getattr(self, "msm_out", None) is not None:
+            jac = np.ascontiguousarray(self.msm_out.cpu().numpy()).view(np.uint64)
+            out["msm"] = bzh2.jacobian_to_affine(self.curve, jac, bzh2.FORM_MONTGOMERY).view(np.uint16).reshape(-1, 32)
+        if getattr(self, "total_point", None) is not None:       # msm24 over several ranks: the combined point every rank holds
+            out["msm_total"] = bzh2.jacobian_to_affine(self.curve, self.total_point, bzh2.FORM_MONTGOMERY).view(np.uint16).reshape(-1, 32)
+        for name in ("cols", "ext", "hx", "data"):
+            if getattr(self, name, None) is not None:
+                out[name] = chunks(getattr(self, name))
+        return out
 
     def close(self):
         for r in [getattr(self, "runner", None)] + list(getattr(self, "provers", [])):
@@ -915,7 +986,7 @@ def run_other_workloads(args, ctx, device, rank, world, dist):
                 ent["roofline"] = {"bound": "hbm", "kernel": dom_name, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
                                    "traffic": None, "algorithmic_bytes_per_launch": a_bytes, "avg_launch_ms": a_ms, "basis": basis}
             ent["kernel_ms_per_step"] = {kname: round(v["ms"] / steps, 3) for kname, v in timings.items() if v["launches"]}
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 t_cpu = time.perf_counter()
                 if name.startswith("proof_k"):
                     ent["cpu_baseline"] = cpu_baseline_proof(wl.runner)
@@ -1036,7 +1107,10 @@ def main():
             wl.combine(gathered)
     barrier()
     elapsed = time.perf_counter() - t0
-    if rank == 0 and hasattr(wl, "records"):   # untimed: every gathered record decodes (bzh_record_decode: canonical public inputs)
+    if rank == 0 and args.dump_outputs:       # before any untimed step below replaces the last step's results
+        dump_outputs(wl.outputs(), args.dump_outputs)
+    if rank == 0 and hasattr(wl, "records") and (args.full or args.records_out):
+        # untimed: every gathered record decodes (bzh_record_decode: canonical public inputs)
         from bzh2.wire import BattleZipsRecord
         recs = (gathered if dist is not None else wl.records()).cpu().numpy()
         decoded = [BattleZipsRecord.from_fixed(recs[i].tobytes()) for i in range(recs.shape[0])]
@@ -1075,7 +1149,7 @@ def main():
     # overlapping, every kernel shares the GPU with the others' and its own duration stretches, which says nothing about
     # the kernel.  Reported beside the timed region's figures as roofline.single_batch_in_flight.
     solo = None
-    if rank == 0 and hasattr(wl, "solo_step") and len(all_ctx) > 1:
+    if args.full and rank == 0 and hasattr(wl, "solo_step") and len(all_ctx) > 1:
         wl.solo_step()
         torch.cuda.synchronize(device)
         ctx.profile(True)
@@ -1086,7 +1160,7 @@ def main():
         solo["msm_additions"] = ctx.msm_additions()
         ctx.profile(False)
     verified = None
-    if hasattr(wl, "verify_last"):  # untimed: every proof of every thread's last batch through bzh_verify_batch
+    if args.full and hasattr(wl, "verify_last"):  # untimed: every proof of every thread's last batch through bzh_verify_batch
         verified = bool(wl.verify_last())
         assert verified, "a proof of the last batch does not verify"
     if dist is not None:
@@ -1302,7 +1376,7 @@ def main():
                 pass
             line["config"]["srs_window_bits"] = wl.window_bits or "planner"
             line["config"]["distinct_proofs_in_last_batch"] = len(set(wl.runner.last_batch[0]))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if is_full:
                 line["cpu_baseline"] = cpu_baseline_proof(wl.runner)
             elif is_proof and args.workload != "shot_k11_batch":
@@ -1312,7 +1386,7 @@ def main():
             elif is_verify:
                 line["cpu_baseline"] = cpu_baseline_verify(wl.runner)
     # the rest of BASELINE.json's metric in the same line: short regions after the main one (every rank takes part)
-    want_others = args.other_workloads == "all" or (args.other_workloads == "auto" and args.workload == "proof_k14" and args.batch == 64
+    want_others = args.other_workloads == "all" or (args.other_workloads == "auto" and args.full and args.workload == "proof_k14" and args.batch == 64
                                                     and args.concurrency == 4 and not args.no_kernel_timers and not args.explicit_rng
                                                     and not args.no_quotient_codegen and not args.window_bits)
     others = None
