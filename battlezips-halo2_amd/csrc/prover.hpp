@@ -158,17 +158,7 @@ struct Prover {
     }
     int to_extended(uint32_t* dst, const uint32_t* polys, size_t count) {
         if (!count) return BZH_OK;
-        if (q29) {
-            static const bool unfused = getenv("BZH_QUOTIENT29_UNFUSED") != nullptr;   // experiment: saturated cosets + a conversion pass
-            if (!unfused) return ntt_run_padded(ctx, field, nullptr, polys, pk.k, pk.ek, count, pk.eomega, pk.zeta, dst);
-            ArenaScope scope(arena);
-            uint32_t* sat = dalloc(count * en);
-            if (!sat) return BZH_E_OOM;
-            PV_TRY(ntt_run_padded(ctx, field, sat, polys, pk.k, pk.ek, count, pk.eomega, pk.zeta));
-            hipLaunchKernelGGL((k_sat_to_fe29_planes<SF>), dim3((unsigned)((en + 255) / 256), (unsigned)count), dim3(256), 0, st, sat, dst, en);
-            BZH_HIP_TRY(ctx, hipGetLastError());
-            return BZH_OK;
-        }
+        if (q29) return ntt_run_padded(ctx, field, nullptr, polys, pk.k, pk.ek, count, pk.eomega, pk.zeta, dst);
         return ntt_run_padded(ctx, field, dst, polys, pk.k, pk.ek, count, pk.eomega, pk.zeta);
     }
     // Params::commit for `count` polynomials (rows of `pitch` elements): affine canonical points out

@@ -389,12 +389,10 @@ static std::string program2_source29_policy(const Program2& pg, int field, bool 
     // (132 VGPRs, three waves per SIMD: forcing four with amdgpu_waves_per_eu(4, 4) -- 128 VGPRs, 3 spilled -- measured slower,
     // 34.2 against 33.4 ms per batch of 64)
     // A scheduling barrier after every operation keeps the compiler from hoisting the column loads of the whole program to its top.
-    // BZH_QUOTIENT29_NO_BARRIERS=1 (generation time) drops them and caps the kernel at three waves' registers instead: LLVM then
-    // merges the program's repeated products (mulv is pure: Board 565 -> 426 calls) but spills ~1 900 words per row to scratch
-    // -- measured 30.2 vs 31.1 ms for Board and ShotCircuit's throughput -4 %: not the default.
-    static const bool barriers = getenv("BZH_QUOTIENT29_NO_BARRIERS") == nullptr;
-    add("extern \"C\" __global__ void __launch_bounds__(128) %s%s(const uint32_t* const* __restrict__ cols, ",
-        barriers ? "" : "__attribute__((amdgpu_waves_per_eu(3, 3))) ", kname);
+    // Without them (and the kernel capped at three waves' registers) LLVM merges the program's repeated products (mulv is pure:
+    // Board 565 -> 426 calls) but spills ~1 900 words per row to scratch -- measured 30.2 vs 31.1 ms for Board and ShotCircuit's
+    // throughput -4 %.
+    add("extern \"C\" __global__ void __launch_bounds__(128) %s(const uint32_t* const* __restrict__ cols, ", kname);
     src += "const size_t* __restrict__ strides, const uint32_t* __restrict__ consts, size_t const_stride, size_t size, "
            "uint32_t* __restrict__ out) {\n"
            "    const size_t r = blockIdx.x * (size_t)128 + threadIdx.x, v = blockIdx.y;\n"
@@ -409,7 +407,8 @@ static std::string program2_source29_policy(const Program2& pg, int field, bool 
         double V;
         uint64_t L, T;
     };
-    static const bool eager = getenv("BZH_QUOTIENT29_EAGER_CARRY") != nullptr;   // (measurement: the carry pass after every + and -)
+    // carry passes only where a consumer needs one (a carry pass after every + and - was measured: 598 against 115 passes per row
+    // for Board, 33.8 against 32.4 ms)
     constexpr uint64_t kCarried = ((uint64_t)1 << 29) + 8;                          // fe29_carry's output: limbs 0..7 below this
     constexpr uint64_t kBiasLimb = ((uint64_t)1 << 30) + ((uint64_t)1 << 29);       // a limb of a bias K p stays below this
     constexpr double kColumn = 1.8e18;                                              // A * B of a product's limb bounds (header)
@@ -427,12 +426,12 @@ static std::string program2_source29_policy(const Program2& pg, int field, bool 
     // ---- fused pairs: X = (product) ; Y = slot * constant ; X + Y  ->  one dot2 with one reduction.  Two shapes come out of
     //      Compiler2::quotient: [rP = a * b] [rP+1 = ACC * y^m] [rP += rP+1] (adjacent), and Horner's [rP = IN * y] ... [rP+1 = a * b]
     //      [rP += rP+1] (the first product is deferred to the second: its operands are a slot nothing stores to in between and a constant).
+    //      Measured against the two products apart: Board 283 instead of 386 instructions per pair, 26.7 -> 25.3 ms per batch of 64.
     struct Fuse {
         int slot = -1, cst = -1, dst = -1;   // at the surviving product: the other product's slot and constant, the register that gets the sum
     };
     std::vector<Fuse> fuse(nops);
     std::vector<char> skip(nops, 0);
-    static const bool no_dot2 = getenv("BZH_QUOTIENT29_NO_DOT2") != nullptr;
     {
         auto fm = [&](size_t i) { return pg.ops[i].code >> 4; };
         auto opc = [&](size_t i) { return (pg.ops[i].code >> 2) & 3; };
@@ -448,7 +447,7 @@ static std::string program2_source29_policy(const Program2& pg, int field, bool 
             return false;
         };
         auto writes = [&](size_t i, int p) { return !(fm(i) == V2_UN && opc(i) == V2_STORE) && ps(i) == p; };
-        for (size_t k = 2; k < nops && !no_dot2; k++) {
+        for (size_t k = 2; k < nops; k++) {
             if (!(fm(k) == V2_SS && opc(k) == V2_ADD) || skip[k]) continue;
             const int P = ps(k);
             if (skip[k - 1] || skip[k - 2] || fuse[k - 1].dst >= 0 || fuse[k - 2].dst >= 0) continue;
@@ -568,16 +567,12 @@ static std::string program2_source29_policy(const Program2& pg, int field, bool 
             }
             if (a.b.V + b.b.V > 100.0 || a.b.L + b.b.L > 0xffffffffull) pg_fail = true;
             const Bnd sum{a.b.V + b.b.V, a.b.L + b.b.L, a.b.T + b.b.T};
-            if (eager) {
-                add("    %s = fe29_add_c(%s, %s);\n", dst.c_str(), a.name.c_str(), b.name.c_str());
-                return Bnd{sum.V, (((uint64_t)1 << 29) - 1) + (sum.L >> 29), sum.T + (sum.L >> 29)};
-            }
             add("    %s = fe29_add(%s, %s);\n", dst.c_str(), a.name.c_str(), b.name.c_str());
             return sum;
         }
         // a - b: the bias K p = J copies of (K / J) p has to dominate b limb by limb
         if (b.b.V > 60.0) fold(b), sync(b, a);
-        if (b.b.L > 2 * (((uint64_t)1 << 30) - 2) || eager) carry(b), sync(b, a);
+        if (b.b.L > 2 * (((uint64_t)1 << 30) - 2)) carry(b), sync(b, a);
         const int J = b.b.L > ((uint64_t)1 << 30) - 2 ? 2 : 1;
         int K = pow2_over(b.b.V);
         while ((uint64_t)K * ((uint64_t)1 << 22) < b.b.T + 2 * (uint64_t)J) K *= 2;
@@ -585,10 +580,6 @@ static std::string program2_source29_policy(const Program2& pg, int field, bool 
         if (a.b.L + (uint64_t)J * kBiasLimb > 0xffffffffull) carry(a), sync(a, b);
         if (same || a.b.V + K > 100.0 || K > 64 || a.b.L + (uint64_t)J * kBiasLimb > 0xffffffffull) pg_fail = true;   // (x - x is never emitted)
         const Bnd diff{a.b.V + K, a.b.L + (uint64_t)J * kBiasLimb, a.b.T + (uint64_t)K * ((uint64_t)1 << 22) + (uint64_t)K};
-        if (eager) {
-            add("    %s = fe29_sub<P, %d>(%s, %s);\n", dst.c_str(), K, a.name.c_str(), b.name.c_str());
-            return Bnd{diff.V, (((uint64_t)1 << 29) - 1) + (diff.L >> 29), diff.T + (diff.L >> 29)};
-        }
         add("    %s = fe29_sub_lazy<P, %d, %d>(%s, %s);\n", dst.c_str(), K, J, a.name.c_str(), b.name.c_str());
         return diff;
     };
@@ -634,7 +625,7 @@ static std::string program2_source29_policy(const Program2& pg, int field, bool 
             const Val a = form == V2_LL ? operand("la", i, o.a_kind, o.a_idx) : Val{ra, br[pos], false};
             const Val b = form == V2_SS ? Val{regs[(pos + 1) & 3], br[(pos + 1) & 3], false} : operand("lb", i, o.b_kind, o.b_idx);
             br[fuse[i].dst] = dot2(rd, a, b, fuse[i]);
-            if (barriers) src += "    __builtin_amdgcn_sched_barrier(0);\n";
+            src += "    __builtin_amdgcn_sched_barrier(0);\n";
             continue;
         }
         if (form == V2_SS) {
@@ -659,7 +650,7 @@ static std::string program2_source29_policy(const Program2& pg, int field, bool 
             add("    s%d = %s;\n", o.a_idx, ra.c_str());
             bs[(size_t)o.a_idx] = br[pos];
         }
-        if (barriers) src += "    __builtin_amdgcn_sched_barrier(0);\n";
+        src += "    __builtin_amdgcn_sched_barrier(0);\n";
     }
     if (br[0].L > 0xfffffff0ull || br[0].V > 120.0) pg_fail = true;
     if (pg_fail) return std::string();

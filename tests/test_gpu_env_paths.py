@@ -1,7 +1,7 @@
 """The library's tuning knobs and fallback paths (environment variables read once per process) must not change a single
-bit: the global-sort MSM path, other accumulate workgroup / chunk sizes, the quotient VM v1 fallback, no hoisted
-columns, other shared-subexpression slot counts, the interpreted quotient, the LDS-tile NTT kernel, and the opening's
-generator collapse off / forced at several rounds and tail windows.  Each setting runs tests/helpers/env_case.py in its own process; all digests
+bit: the quotient VM v1 fallback, no hoisted columns, other shared-subexpression slot counts, the interpreted quotient,
+the LDS-tile NTT kernel, and the opening's generator collapse off / forced at several rounds and tail windows.  Each setting
+runs tests/helpers/env_case.py in its own process; all digests
 (MSM results + the bytes of two real ShotCircuit proofs under fixed seeds) must equal the default's."""
 import os
 import subprocess
@@ -15,9 +15,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASE = os.path.join(ROOT, "tests", "helpers", "env_case.py")
 
 SETTINGS = [
-    {"BZH_MSM_GS": "1"},
-    {"BZH_ACC_THREADS": "128"},
-    {"BZH_ACC_THREADS": "512", "BZH_ACC_CHUNK": "4096"},
     {"BZH_QUOTIENT_V1": "1"},
     {"BZH_NO_HOIST": "1"},
     {"BZH_VM2_CSE": "0"},                                   # (other slot counts = another program: no builtin kernel, the interpreter runs it)
@@ -27,7 +24,6 @@ SETTINGS = [
     {"BZH_QUOTIENT": "interp"},
     {"BZH_NTT_LDS": "1"},
     {"BZH_ACC_SATURATED": "1"},                             # bucket accumulation in saturated 8 x 32 limbs (default: unsaturated 9 x 29, csrc/fe29.cuh)
-    {"BZH_ACC_SATURATED": "1", "BZH_ACC_THREADS": "512", "BZH_ACC_CHUNK": "4096"},
     {"BZH_QUOTIENT_SATURATED": "1"},                        # the builtin quotient kernel in saturated limbs (default: its unsaturated-limb flavour)
     {"BZH_RED_WG_MAX": "0"},                                # latency-mode reductions: one wave per segment everywhere
     {"BZH_RED_WG_MAX": "4096"},                             # ... the workgroup flavour everywhere
@@ -45,7 +41,7 @@ SETTINGS = [
 
 def _digest(extra):
     env = dict(os.environ)
-    for k in ("BZH_MSM_GS", "BZH_ACC_THREADS", "BZH_ACC_CHUNK", "BZH_QUOTIENT_V1", "BZH_NO_HOIST", "BZH_VM2_CSE", "BZH_QUOTIENT", "BZH_NTT_LDS",
+    for k in ("BZH_QUOTIENT_V1", "BZH_NO_HOIST", "BZH_VM2_CSE", "BZH_QUOTIENT", "BZH_NTT_LDS",
               "BZH_IPA_COLLAPSE", "BZH_IPA_TAIL_C", "BZH_NO_COMMIT_SHIFT", "BZH_MSM_NO_QUAD", "BZH_ACC_NO_XCD_MAP", "BZH_ACC_SATURATED", "BZH_QUOTIENT_SATURATED", "BZH_RED_WG_MAX", "BZH_VM2_GLOBAL"):
         env.pop(k, None)
     env.update(extra)
