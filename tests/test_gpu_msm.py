@@ -251,3 +251,74 @@ def test_bases_walk_is_the_oracles_point_walk(gpu_ctx, oracle_c, cid):
                     gpu_ctx.bases_points(b, n - 1, 2)
         finally:
             b.free()
+
+
+# ---- digit-boundary scalars and colliding bases (tests/helpers/msm_edges.py) ---------------------------------------------------
+def _compressed(bzh2, cid, jac):
+    return bzh2.affine_compress(cid, bzh2.jacobian_to_affine(cid, jac))
+
+
+@pytest.mark.parametrize("cid", [0, 1, 2])
+@pytest.mark.parametrize("c", list(range(4, 16)))
+def test_msm_window_table_every_width_on_digit_boundary_scalars(gpu_ctx, oracle_c, cid, c):
+    """every window width bzh_bases_precompute accepts, with scalars whose windows of that width hold 0, 1, 2^(c-1) - 1,
+    2^(c-1), 2^(c-1) + 1, 2^c - 1, every single-bit scalar, r - 1, r - 2 and (r - 1) / 2"""
+    import bzh2
+    from helpers.msm_edges import boundary_scalars
+    r = SCALAR_MODULUS[cid]
+    n = 640                                  # 382 window-assembled scalars, then r - 1, r - 2, (r - 1) / 2 and all 255 powers of two
+    bases = walk_bases(cid, n, seed=60 + cid)
+    sc = C.ints_to_array(boundary_scalars(c, r, random.Random(100 * cid + c), n))
+    assert gpu_msm_compressed(bzh2, gpu_ctx, cid, bases, sc, precompute=c) == oracle_compressed(cid, bases, sc)
+
+
+@pytest.mark.parametrize("cid,n", [(0, 64), (0, 2048), (0, 1 << 14), (0, 1 << 16), (1, 2048), (2, 2048)])
+def test_msm_plain_path_on_digit_boundary_scalars(gpu_ctx, oracle_c, cid, n):
+    """the plain (no table) path, one scalar vector per window width 3..15 -- the width the library chooses for this size is
+    among them, whichever it is -- in one batched call; half of every vector, at n = 64 too, is assembled window by window for
+    its width (tests/helpers/msm_edges.py), so the 13 vectors differ"""
+    import bzh2
+    from helpers.msm_edges import boundary_scalars
+    r = SCALAR_MODULUS[cid]
+    bases = walk_bases(cid, n, seed=70 + cid)
+    rng = random.Random(1000 * cid + n)
+    batch = np.stack([C.ints_to_array(boundary_scalars(c, r, rng, n)) for c in range(3, 16)])
+    assert len({v.tobytes() for v in batch}) == 13
+    got = gpu_msm_compressed(bzh2, gpu_ctx, cid, bases, batch)
+    want = oracle_compressed(cid, bases, batch)
+    assert got == want, [c for c, g, w in zip(range(3, 16), got, want) if g != w]
+
+
+def _colliding_case(cid, n, c, nvec, seed):
+    from helpers.msm_edges import colliding_bases, colliding_scalar_vectors
+    cv = O.CURVE_BY_ID[cid]
+    rng = random.Random(seed)
+    bases = C.points_to_array(colliding_bases(cv, n, rng))
+    batch = colliding_scalar_vectors(SCALAR_MODULUS[cid], n, c, nvec, rng, np.random.default_rng(seed), uniform_below)
+    return bases, batch
+
+
+@pytest.mark.parametrize("cid,nvec", [(0, 24), (0, 13), (1, 4)])
+def test_msm_window_table_colliding_bases_chunk_presum(gpu_ctx, oracle_c, cid, nvec):
+    """the proof regime's shape (2^14 + 2 scalars, precompute(11), 24 / 13 vectors: chunk pre-sum, XCD-aware order) over a base
+    set of 64 distinct points repeated, every third repeat negated, with identities: bucket accumulation, the chunk sums and
+    the reductions meet the same point twice and a point with its negative all the time"""
+    import bzh2
+    n = (1 << 14) + 2
+    bases, batch = _colliding_case(cid, n, 11, nvec, 500 + 10 * cid + nvec)
+    hb = gpu_ctx.upload_bases(cid, bases).precompute(11)
+    try:
+        got = _compressed(bzh2, cid, gpu_ctx.msm(hb, batch))
+    finally:
+        hb.free()
+    want = oracle_compressed(cid, bases, batch)
+    assert got == want, [v for v, (g, w) in enumerate(zip(got, want)) if g != w]
+
+
+def test_msm_plain_path_colliding_bases_2_16(gpu_ctx, oracle_c):
+    import bzh2
+    n = 1 << 16
+    bases, batch = _colliding_case(0, n, 13, 4, 616)
+    got = gpu_msm_compressed(bzh2, gpu_ctx, 0, bases, batch)
+    want = oracle_compressed(0, bases, batch)
+    assert got == want, [v for v, (g, w) in enumerate(zip(got, want)) if g != w]

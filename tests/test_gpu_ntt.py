@@ -173,3 +173,119 @@ def test_coeff_to_extended_montgomery_device_path_leaves_source_intact(gpu_ctx, 
         padded[: 1 << k] = a[b]
         want = C.array_to_ints(C.ntt(0, padded, F.omega(ek), coset_shift=zeta, threads=8))
         assert C.array_to_ints(got[b]) == [x * R % p for x in want]
+
+
+# ---- closed-form inputs: expected values from Python integers by iterated products, no second NTT involved -------------------
+def _batch_inverse(ds, p):
+    """inverses of the non-zero ds (Montgomery's trick: one modular inversion)"""
+    pre, acc = [], 1
+    for d in ds:
+        pre.append(acc)
+        acc = acc * d % p
+    inv = pow(acc, -1, p)
+    out = [0] * len(ds)
+    for i in range(len(ds) - 1, -1, -1):
+        out[i] = inv * pre[i] % p
+        inv = inv * ds[i] % p
+    return out
+
+
+def _geometric_unit(q, n, w, shift, p):
+    """forward transform of a[j] = q^j on the coset `shift`: out[i] = sum_j (q shift w^i)^j -- n where the ratio is 1,
+    otherwise ((q shift)^n - 1) / (q shift w^i - 1), which is EXACTLY zero when (q shift)^n == 1"""
+    base = q * shift % p
+    num = (pow(base, n, p) - 1) % p
+    ratios, r = [], base
+    for _ in range(n):
+        ratios.append(r)
+        r = r * w % p
+    if num == 0:
+        return [n if r == 1 else 0 for r in ratios]
+    assert 1 not in ratios
+    return [num * d % p for d in _batch_inverse([r - 1 for r in ratios], p)]
+
+
+def _impulse_transform(v, j, n, w, shift, p):
+    """forward transform of v at index j: out[i] = v shift^j (w^j)^i"""
+    step, x, out = pow(w, j, p), v * pow(shift, j, p) % p, []
+    if step == 1:
+        return [x] * n
+    if step == p - 1:
+        return [x, p - x if x else 0] * (n // 2)
+    for _ in range(n):
+        out.append(x)
+        x = x * step % p
+    return out
+
+
+def _closed_form_cases(fid, k, mode):
+    """[(name, input array, expected ints)] for one field, size and mode ('forward', 'inverse', 'coset')"""
+    from helpers import field_edges as E
+    F = O.FIELD_BY_ID[fid]
+    p, n = F.p, 1 << k
+    vals = E.edge_values(p)
+    w = F.omega(k)
+    assert (p - 1) % 3 == 0
+    zeta = pow(F.g, (p - 1) // 3, p)
+    shift = zeta if mode == "coset" else 1
+    w_eff = pow(w, -1, p) if mode == "inverse" else w
+    ninv = pow(n, -1, p)
+    post = (lambda out: [x * ninv % p for x in out]) if mode == "inverse" else (lambda out: out)
+    cases = []
+    # impulses: values p - 1, R mod p, 2^224 - 1 and a low part of p, one at each of the four positions
+    for j, v in zip(sorted({0, 1, n // 2, n - 1}), (vals[3], vals[7], (1 << 224) - 1, p % (1 << 96))):
+        assert v in vals
+        a = np.zeros((n, 4), dtype=np.uint64)
+        a[j] = C.int_to_limbs(v)
+        cases.append(("impulse %#x at %d" % (v, j), a, post(_impulse_transform(v, j, n, w_eff, shift, p))))
+    unit = {}
+    for name, c, q in (("constant R^2 mod p", vals[8], 1), ("all p - 1", p - 1, 1), ("alternating (x, p - x)", vals[5], p - 1)):
+        a = np.tile(C.ints_to_array([c, c if q == 1 else p - c]), (max(n // 2, 1), 1))[:n]
+        if q not in unit:
+            unit[q] = _geometric_unit(q, n, w_eff, shift, p)
+        want = post([c * u % p if u else 0 for u in unit[q]])
+        if mode != "coset":                       # n c (forward) or c (inverse) at one index, exactly zero elsewhere
+            at = 0 if q == 1 else n // 2
+            assert want == [(c if mode == "inverse" else n * c % p) if i == at else 0 for i in range(n)]
+        cases.append((name, a, want))
+    return w, (zeta if mode == "coset" else None), cases
+
+
+@pytest.mark.parametrize("mode", ["forward", "inverse", "coset"])
+@pytest.mark.parametrize("k", [1, 6, 11, 12, 17, 19])
+@pytest.mark.parametrize("fid", [0, 1, 2])
+def test_ntt_closed_form_inputs(gpu_ctx, fid, k, mode):
+    """Impulses, constant vectors, all p - 1 and alternating (x, p - x) through one, two and three passes: inputs whose
+    transform has a closed form (a geometric sequence, or n c at one index and exactly zero elsewhere), with edge values of
+    tests/helpers/field_edges.py as the non-zero entries.  Butterflies then meet a + b == p, a - a and operands 0 and p - 1
+    at every stage, which uniform inputs never produce."""
+    w, shift, cases = _closed_form_cases(fid, k, mode)
+    a = np.stack([c[1] for c in cases])
+    got = gpu_ctx.ntt(fid, a, omega=w, inverse=(mode == "inverse"), coset_shift=shift)
+    for b, (name, _, want) in enumerate(cases):
+        bad = (got[b] != C.ints_to_array(want)).any(axis=1)
+        assert not bad.any(), "field %d k=%d %s, %s: %d outputs differ, first at index %d: got %#x want %#x" % (
+            fid, k, mode, name, int(bad.sum()), int(np.argmax(bad)), C.limbs_to_int(got[b][int(np.argmax(bad))]),
+            want[int(np.argmax(bad))])
+
+
+@pytest.mark.parametrize("mode", ["forward", "inverse", "coset"])
+@pytest.mark.parametrize("k", [1, 6, 11, 12, 14])
+@pytest.mark.parametrize("fid", [0, 1, 2])
+def test_ntt_of_the_edge_values_in_montgomery_form(gpu_ctx, oracle_c, fid, k, mode):
+    """a vector cycling through the 256 edge values as raw Montgomery-form bits (no conversion touches them before the first
+    butterfly) against the oracle's transform of the same values times R^-1"""
+    import bzh2
+    from helpers import field_edges as E
+    F = O.FIELD_BY_ID[fid]
+    p, n = F.p, 1 << k
+    vals = E.edge_values(p)
+    raw = [vals[i % 256] for i in range(n)]
+    rinv = pow(E.R, -1, p)
+    w = F.omega(k)
+    zeta = pow(F.g, (p - 1) // 3, p) if mode == "coset" else None
+    want = C.array_to_ints(C.ntt(fid, C.ints_to_array([x * rinv % p for x in raw]), w, inverse=(mode == "inverse"),
+                                 coset_shift=zeta, threads=8))
+    got = gpu_ctx.ntt(fid, C.ints_to_array(raw), omega=w * E.R % p, inverse=(mode == "inverse"),
+                      coset_shift=None if zeta is None else zeta * E.R % p, form=bzh2.FORM_MONTGOMERY)
+    assert C.array_to_ints(got) == [x * E.R % p for x in want], (fid, k, mode)
