@@ -6,6 +6,7 @@
 // bzh_bases_points reads points of any table back (canonical affine): what the tests compare.
 #include "ctx.hpp"
 #include "curve.cuh"
+#include "host_field.hpp"
 
 using namespace bzh;
 
@@ -99,9 +100,7 @@ int bzh_bases_walk(bzh_ctx* ctx, int curve, const uint64_t* g_xy, int form, size
         ctx->last_error = "hipMalloc(bases walk)";
         return BZH_E_OOM;
     }
-    int rc = curve == BZH_CURVE_VESTA ? walk_t<VestaCurve>(ctx, g_xy, form, n, b->d_xy)
-             : curve == BZH_CURVE_PALLAS ? walk_t<PallasCurve>(ctx, g_xy, form, n, b->d_xy)
-                                         : walk_t<Bn254Curve>(ctx, g_xy, form, n, b->d_xy);
+    int rc = with_curve(curve, [&](auto c) { return walk_t<decltype(c)>(ctx, g_xy, form, n, b->d_xy); });
     if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) {
         ctx->last_error = "k_bases_walk failed";
         rc = BZH_E_HIP;
@@ -128,11 +127,10 @@ int bzh_bases_points(bzh_ctx* ctx, const bzh_bases* bases, size_t first, size_t 
     const size_t elems = count * 2;
     const uint32_t* src = bases->d_xy + first * 16;
     const dim3 grid((unsigned)((elems + 255) / 256));
-    switch (bases->curve) {
-        case BZH_CURVE_VESTA: hipLaunchKernelGGL((k_points_canonical<VestaCurve::Base>), grid, dim3(256), 0, ctx->stream, (uint32_t*)tmp, src, elems); break;
-        case BZH_CURVE_PALLAS: hipLaunchKernelGGL((k_points_canonical<PallasCurve::Base>), grid, dim3(256), 0, ctx->stream, (uint32_t*)tmp, src, elems); break;
-        default: hipLaunchKernelGGL((k_points_canonical<Bn254Curve::Base>), grid, dim3(256), 0, ctx->stream, (uint32_t*)tmp, src, elems); break;
-    }
+    BZH_TRY(with_curve(bases->curve, [&](auto c) {
+        hipLaunchKernelGGL((k_points_canonical<typename decltype(c)::Base>), grid, dim3(256), 0, ctx->stream, (uint32_t*)tmp, src, elems);
+        return BZH_OK;
+    }));
     BZH_HIP_TRY(ctx, hipGetLastError());
     BZH_HIP_TRY(ctx, hipMemcpyAsync(out_xy, tmp, count * 64, hipMemcpyDeviceToHost, ctx->stream));
     BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -8,6 +8,7 @@
 
 #include "ctx.hpp"
 #include "curve.cuh"
+#include "host_field.hpp"
 
 namespace bzh {
 void ntt_cache_drop(bzh_ctx* ctx);
@@ -19,7 +20,14 @@ static bool valid_curve(int c) { return c >= 0 && c <= 2; }
 static bool valid_field(int f) { return f >= 0 && f <= 3; }
 static bool valid_form(int f) { return f == BZH_FORM_CANONICAL || f == BZH_FORM_MONTGOMERY; }
 static bool valid_mem(int m) { return m == BZH_MEM_HOST || m == BZH_MEM_DEVICE; }
-static unsigned field_two_adicity(int f) { return f == BZH_FIELD_BN254_FR ? 28u : (f == BZH_FIELD_BN254_FQ ? 1u : 32u); }
+static unsigned field_two_adicity(int f) {
+    unsigned s = 0;
+    with_field(f, [&](auto p) {
+        s = FieldInfo<decltype(p)>::S;
+        return BZH_OK;
+    });
+    return s;
+}
 
 // ---- host helpers (CPU build of the same field templates) ------------------
 namespace {
@@ -60,105 +68,25 @@ struct Stager {
     }
 };
 
-template <class P>
-static Fe<P> load_host(const uint64_t* p, int form) {
-    Fe<P> v;
-    for (int i = 0; i < 4; i++) {
-        v.l[2 * i] = (uint32_t)p[i];
-        v.l[2 * i + 1] = (uint32_t)(p[i] >> 32);
-    }
-    return form == BZH_FORM_CANONICAL ? fe_to_mont(v) : v;
-}
-template <class P>
-static void store_host(uint64_t* p, Fe<P> v, int form) {
-    if (form == BZH_FORM_CANONICAL) v = fe_from_mont(v);
-    for (int i = 0; i < 4; i++) p[i] = (uint64_t)v.l[2 * i] | ((uint64_t)v.l[2 * i + 1] << 32);
-}
-
-template <class P>
-static void jac_to_aff_host(const uint64_t* xyz, size_t n, int form, uint64_t* out) {
-    // batch inversion of Z (Montgomery's trick), identity -> (0,0)
-    std::vector<Fe<P>> z(n), pref(n);
-    Fe<P> run = fe_one<P>();
-    for (size_t i = 0; i < n; i++) {
-        z[i] = load_host<P>(xyz + 12 * i + 8, form);
-        pref[i] = run;
-        if (!fe_is_zero(z[i])) run = fe_mul(run, z[i]);
-    }
-    Fe<P> inv = fe_inv(run);
-    for (size_t i = n; i-- > 0;) {
-        if (fe_is_zero(z[i])) {
-            memset(out + 8 * i, 0, 64);
-            continue;
-        }
-        Fe<P> zi = fe_mul(inv, pref[i]);
-        inv = fe_mul(inv, z[i]);
-        Fe<P> zi2 = fe_sqr(zi), zi3 = fe_mul(zi2, zi);
-        store_host<P>(out + 8 * i, fe_mul(load_host<P>(xyz + 12 * i, form), zi2), form);
-        store_host<P>(out + 8 * i + 4, fe_mul(load_host<P>(xyz + 12 * i + 4, form), zi3), form);
-    }
-}
-
-template <class P>
-static void compress_host(const uint64_t* xy, size_t n, int form, uint8_t* out) {
-    for (size_t i = 0; i < n; i++) {
-        uint64_t x[4], y[4];
-        store_host<P>(x, load_host<P>(xy + 8 * i, form), BZH_FORM_CANONICAL);
-        store_host<P>(y, load_host<P>(xy + 8 * i + 4, form), BZH_FORM_CANONICAL);
-        memcpy(out + 32 * i, x, 32);
-        out[32 * i + 31] |= (uint8_t)((y[0] & 1) << 7);
-    }
-}
-
 // sum of n Jacobian points on the host: the combine step of an MSM whose points are split over several GPUs
 // (each rank's partial result is one 96-byte point; SURVEY.md section 8e "8-GPU single MSM")
 template <class P>
 static void jac_sum_host(const uint64_t* xyz, size_t n, int form, uint64_t* out) {
     std::vector<uint64_t> aff(8 * (n ? n : 1));
-    jac_to_aff_host<P>(xyz, n, form, aff.data());
+    h_jac_to_affine<P>(xyz, n, form, form, aff.data());
     Xyzz<P> acc = xyzz_identity<P>();
     for (size_t i = 0; i < n; i++) {
         Affine<P> a;
-        a.x = load_host<P>(aff.data() + 8 * i, form);
-        a.y = load_host<P>(aff.data() + 8 * i + 4, form);
+        a.x = fe_from_u64<P>(aff.data() + 8 * i, form);
+        a.y = fe_from_u64<P>(aff.data() + 8 * i + 4, form);
         if (aff_is_id(a)) continue;
         xyzz_madd(acc, a);
     }
     Fe<P> X, Y, Z;
     xyzz_to_jacobian(acc, X, Y, Z);
-    store_host<P>(out, X, form);
-    store_host<P>(out + 4, Y, form);
-    store_host<P>(out + 8, Z, form);
-}
-
-template <class P>
-static void omega_host(unsigned S, uint32_t gen, unsigned log_n, int form, uint64_t* out) {
-    // ROOT_OF_UNITY = gen^((p-1) >> S); omega = ROOT^(2^(S - log_n))
-    uint32_t e[8];
-    uint64_t br = 1;
-    for (int i = 0; i < 8; i++) {
-        uint64_t d = (uint64_t)P::mod(i) - br;
-        e[i] = (uint32_t)d;
-        br = (d >> 63) & 1;
-    }
-    uint32_t sh[8];
-    for (int i = 0; i < 8; i++) {
-        uint64_t lo = (S < 32) ? ((uint64_t)e[i] >> S) : 0;
-        unsigned src = i + S / 32;
-        uint64_t v = 0;
-        if (S % 32 == 0) {
-            v = src < 8 ? e[src] : 0;
-        } else {
-            uint64_t a = src < 8 ? e[src] : 0, b = src + 1 < 8 ? e[src + 1] : 0;
-            v = ((a | (b << 32)) >> (S % 32)) & 0xffffffffu;
-        }
-        (void)lo;
-        sh[i] = (uint32_t)v;
-    }
-    Fe<P> g = fe_from_u32<P>(gen);
-    Fe<P> root = fe_pow(g, sh);
-    for (unsigned i = log_n; i < S; i++) root = fe_sqr(root);
-    store_host<P>(out, root, form);
+    fe_to_u64<P>(out, X, form);
+    fe_to_u64<P>(out + 4, Y, form);
+    fe_to_u64<P>(out + 8, Z, form);
 }
 
 template <class PP>
@@ -180,8 +108,8 @@ static int permute_pair_host(const uint64_t* input, const uint64_t* table, size_
         memcpy(t.data(), table, usable * 32);
     } else {
         for (size_t i = 0; i < usable; i++) {
-            store_host<PP>(a[i].l, load_host<PP>(input + 4 * i, form), BZH_FORM_CANONICAL);
-            store_host<PP>(t[i].l, load_host<PP>(table + 4 * i, form), BZH_FORM_CANONICAL);
+            fe_to_u64<PP>(a[i].l, fe_from_u64<PP>(input + 4 * i, form), BZH_FORM_CANONICAL);
+            fe_to_u64<PP>(t[i].l, fe_from_u64<PP>(table + 4 * i, form), BZH_FORM_CANONICAL);
         }
     }
     // values below 2^64 (range tables, compressed small columns -- the reference's lookups): sort the low limbs as integers
@@ -246,8 +174,8 @@ static int permute_pair_host(const uint64_t* input, const uint64_t* table, size_
         return BZH_OK;
     }
     for (size_t i = 0; i < usable; i++) {
-        store_host<PP>(out_input + 4 * i, load_host<PP>(a[i].l, BZH_FORM_CANONICAL), form);
-        store_host<PP>(out_table + 4 * i, load_host<PP>(s[i].l, BZH_FORM_CANONICAL), form);
+        fe_to_u64<PP>(out_input + 4 * i, fe_from_u64<PP>(a[i].l, BZH_FORM_CANONICAL), form);
+        fe_to_u64<PP>(out_table + 4 * i, fe_from_u64<PP>(s[i].l, BZH_FORM_CANONICAL), form);
     }
     return BZH_OK;
 }
@@ -503,17 +431,6 @@ int bzh_ntt(bzh_ctx* ctx, int field, uint64_t* data, unsigned log_n, size_t batc
     return BZH_OK;
 }
 
-// 4 host limbs, canonical -> Montgomery in place
-static int host_to_montgomery(int field, uint64_t* v) {
-    switch (field) {
-        case BZH_FIELD_FP: store_host<FpParams>(v, load_host<FpParams>(v, BZH_FORM_CANONICAL), BZH_FORM_MONTGOMERY); return BZH_OK;
-        case BZH_FIELD_FQ: store_host<FqParams>(v, load_host<FqParams>(v, BZH_FORM_CANONICAL), BZH_FORM_MONTGOMERY); return BZH_OK;
-        case BZH_FIELD_BN254_FR: store_host<BnFrParams>(v, load_host<BnFrParams>(v, BZH_FORM_CANONICAL), BZH_FORM_MONTGOMERY); return BZH_OK;
-        case BZH_FIELD_BN254_FQ: store_host<BnFqParams>(v, load_host<BnFqParams>(v, BZH_FORM_CANONICAL), BZH_FORM_MONTGOMERY); return BZH_OK;
-    }
-    return BZH_E_ARG;
-}
-
 int bzh_coeff_to_extended(bzh_ctx* ctx, int field, const uint64_t* coeffs, unsigned log_n, uint64_t* out, unsigned log_ext,
                           size_t batch, const uint64_t* omega_ext, const uint64_t* coset_shift, int form, int mem) {
     if (!ctx || !coeffs || !out || !omega_ext || !valid_field(field) || !valid_form(form) || !valid_mem(mem)) return BZH_E_ARG;
@@ -542,9 +459,12 @@ int bzh_coeff_to_extended(bzh_ctx* ctx, int field, const uint64_t* coeffs, unsig
     memcpy(w, omega_ext, 32);
     if (coset_shift) memcpy(sh, coset_shift, 32);
     if (form == BZH_FORM_CANONICAL) {
-        int rc = host_to_montgomery(field, w);
-        if (!rc && coset_shift) rc = host_to_montgomery(field, sh);
-        if (rc) return rc;
+        BZH_TRY(with_field(field, [&](auto p) {   // 4 host limbs, canonical -> Montgomery in place
+            using P = decltype(p);
+            fe_to_u64<P>(w, fe_from_u64<P>(w, BZH_FORM_CANONICAL));
+            if (coset_shift) fe_to_u64<P>(sh, fe_from_u64<P>(sh, BZH_FORM_CANONICAL));
+            return BZH_OK;
+        }));
     }
     int rc = ntt_run_padded(ctx, field, d_out, d_in, log_n, log_ext, batch, w, coset_shift ? sh : nullptr);
     if (rc) return rc;
@@ -712,16 +632,11 @@ int bzh_kate_division_batch(bzh_ctx* ctx, int field, const uint64_t* coeffs, siz
     if (mem == BZH_MEM_DEVICE && form != BZH_FORM_MONTGOMERY) return BZH_E_ARG;
     // x_v per vector, uploaded in Montgomery form
     std::vector<uint64_t> xh(batch * 4);
-    auto go = [&](auto tag) {
-        using PP = decltype(tag);
-        for (size_t v = 0; v < batch; v++) store_host<PP>(xh.data() + v * 4, load_host<PP>(xs + 4 * v, form), BZH_FORM_MONTGOMERY);
-    };
-    switch (field) {
-        case BZH_FIELD_FP: go(FpParams{}); break;
-        case BZH_FIELD_FQ: go(FqParams{}); break;
-        case BZH_FIELD_BN254_FR: go(BnFrParams{}); break;
-        default: go(BnFqParams{}); break;
-    }
+    with_field(field, [&](auto p) {
+        using PP = decltype(p);
+        for (size_t v = 0; v < batch; v++) fe_to_u64<PP>(xh.data() + v * 4, fe_from_u64<PP>(xs + 4 * v, form));
+        return BZH_OK;
+    });
     Stager s{ctx, field, BZH_FORM_MONTGOMERY};
     if ((rc = s.begin(((mem == BZH_MEM_HOST ? 2 * n : 0) + 1) * batch * 32 + 512))) return rc;
     uint32_t* d_x;
@@ -747,12 +662,7 @@ int bzh_kate_division(bzh_ctx* ctx, int field, const uint64_t* coeffs, size_t n,
 int bzh_permute_expression_pair(int field, const uint64_t* input, const uint64_t* table, size_t usable_rows, int form,
                                 uint64_t* out_input, uint64_t* out_table) {
     if (!valid_field(field) || !valid_form(form) || ((!input || !table || !out_input || !out_table) && usable_rows)) return BZH_E_ARG;
-    switch (field) {
-        case BZH_FIELD_FP: return permute_pair_host<FpParams>(input, table, usable_rows, form, out_input, out_table);
-        case BZH_FIELD_FQ: return permute_pair_host<FqParams>(input, table, usable_rows, form, out_input, out_table);
-        case BZH_FIELD_BN254_FR: return permute_pair_host<BnFrParams>(input, table, usable_rows, form, out_input, out_table);
-        default: return permute_pair_host<BnFqParams>(input, table, usable_rows, form, out_input, out_table);
-    }
+    return with_field(field, [&](auto p) { return permute_pair_host<decltype(p)>(input, table, usable_rows, form, out_input, out_table); });
 }
 
 int bzh_expr_eval_batch(bzh_ctx* ctx, int field, const bzh_expr_op* prog, size_t nops, const uint64_t* const* columns,
@@ -843,7 +753,11 @@ int bzh_ipa_open_batch(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* pol
         if (!transcripts[b]) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int field = bases->curve == BZH_CURVE_VESTA ? BZH_FIELD_FP : (bases->curve == BZH_CURVE_PALLAS ? BZH_FIELD_FQ : BZH_FIELD_BN254_FR);
+    int field = 0;
+    BZH_TRY(with_curve(bases->curve, [&](auto c) {
+        field = CurveInfo<decltype(c)>::scalar_field;
+        return BZH_OK;
+    }));
     if (mem == BZH_MEM_DEVICE) {
         if (form != BZH_FORM_MONTGOMERY) return BZH_E_ARG;
         return ipa_open(ctx, bases, (const uint32_t*)polys, batch, blinds, x3s, rng, rng_stride, transcripts, out_v);
@@ -873,47 +787,37 @@ int bzh_ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitm
 int bzh_jacobian_to_affine(int curve, const uint64_t* xyz, size_t n, int form, uint64_t* out_xy) {
     if ((!xyz || !out_xy) && n) return BZH_E_ARG;
     if (!valid_curve(curve) || !valid_form(form)) return BZH_E_ARG;
-    switch (curve) {
-        case BZH_CURVE_VESTA: jac_to_aff_host<FqParams>(xyz, n, form, out_xy); break;
-        case BZH_CURVE_PALLAS: jac_to_aff_host<FpParams>(xyz, n, form, out_xy); break;
-        case BZH_CURVE_BN254: jac_to_aff_host<BnFqParams>(xyz, n, form, out_xy); break;
-    }
-    return BZH_OK;
+    return with_curve(curve, [&](auto c) {
+        h_jac_to_affine<typename decltype(c)::Base>(xyz, n, form, form, out_xy);
+        return BZH_OK;
+    });
 }
 
 int bzh_jacobian_sum(int curve, const uint64_t* xyz, size_t n, int form, uint64_t* out_xyz) {
     if (!out_xyz || (!xyz && n)) return BZH_E_ARG;
     if (!valid_curve(curve) || !valid_form(form)) return BZH_E_ARG;
-    switch (curve) {
-        case BZH_CURVE_VESTA: jac_sum_host<FqParams>(xyz, n, form, out_xyz); break;
-        case BZH_CURVE_PALLAS: jac_sum_host<FpParams>(xyz, n, form, out_xyz); break;
-        case BZH_CURVE_BN254: jac_sum_host<BnFqParams>(xyz, n, form, out_xyz); break;
-    }
-    return BZH_OK;
+    return with_curve(curve, [&](auto c) {
+        jac_sum_host<typename decltype(c)::Base>(xyz, n, form, out_xyz);
+        return BZH_OK;
+    });
 }
 
 int bzh_affine_compress(int curve, const uint64_t* xy, size_t n, int form, uint8_t* out32) {
     if ((!xy || !out32) && n) return BZH_E_ARG;
     if (!valid_curve(curve) || !valid_form(form)) return BZH_E_ARG;
-    switch (curve) {
-        case BZH_CURVE_VESTA: compress_host<FqParams>(xy, n, form, out32); break;
-        case BZH_CURVE_PALLAS: compress_host<FpParams>(xy, n, form, out32); break;
-        case BZH_CURVE_BN254: compress_host<BnFqParams>(xy, n, form, out32); break;
-    }
-    return BZH_OK;
+    return with_curve(curve, [&](auto c) {
+        for (size_t i = 0; i < n; i++) h_compress<decltype(c)>(xy + 8 * i, form, out32 + 32 * i);
+        return BZH_OK;
+    });
 }
 
 int bzh_field_omega(int field, unsigned log_n, int form, uint64_t* out) {
     if (!out || !valid_field(field) || !valid_form(form)) return BZH_E_ARG;
     if (log_n > field_two_adicity(field)) return BZH_E_RANGE;
-    switch (field) {
-        case BZH_FIELD_FP: omega_host<FpParams>(32, 5, log_n, form, out); break;
-        case BZH_FIELD_FQ: omega_host<FqParams>(32, 5, log_n, form, out); break;
-        case BZH_FIELD_BN254_FR: omega_host<BnFrParams>(28, 7, log_n, form, out); break;
-        case BZH_FIELD_BN254_FQ: omega_host<BnFqParams>(1, 3, log_n, form, out); break;
-    }
-    return BZH_OK;
+    return with_field(field, [&](auto p) {
+        fe_to_u64(out, h_omega<decltype(p)>(log_n), form);
+        return BZH_OK;
+    });
 }
-
 
 }  // extern "C"

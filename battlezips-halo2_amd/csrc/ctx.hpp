@@ -76,6 +76,12 @@ struct bzh_ctx {
             return (e__ == hipErrorOutOfMemory) ? BZH_E_OOM : BZH_E_HIP;                          \
         }                                                                                         \
     } while (0)
+// hand a callee's status up unless it is BZH_OK
+#define BZH_TRY(expr)          \
+    do {                       \
+        int rc__ = (expr);     \
+        if (rc__) return rc__; \
+    } while (0)
 
 namespace bzh {
 

@@ -15,6 +15,7 @@
 // slot file.  Modular-integer VALU work, no MFMA.
 #include "ctx.hpp"
 #include "field.cuh"
+#include "host_field.hpp"
 
 namespace bzh {
 
@@ -142,13 +143,9 @@ static int expr_eval_t(bzh_ctx* ctx, const ExprOp* d_prog, int nops, const uint3
 int expr_eval(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint32_t* const* d_cols, const size_t* d_strides,
               const uint32_t* d_consts, size_t const_stride, size_t size, int result_slot, size_t batch, int nslots, uint32_t* d_out) {
     const ExprOp* p = (const ExprOp*)d_prog;
-    switch (field) {
-        case BZH_FIELD_FP: return expr_eval_t<FpParams>(ctx, p, nops, d_cols, d_strides, d_consts, const_stride, size, result_slot, batch, nslots, d_out);
-        case BZH_FIELD_FQ: return expr_eval_t<FqParams>(ctx, p, nops, d_cols, d_strides, d_consts, const_stride, size, result_slot, batch, nslots, d_out);
-        case BZH_FIELD_BN254_FR: return expr_eval_t<BnFrParams>(ctx, p, nops, d_cols, d_strides, d_consts, const_stride, size, result_slot, batch, nslots, d_out);
-        case BZH_FIELD_BN254_FQ: return expr_eval_t<BnFqParams>(ctx, p, nops, d_cols, d_strides, d_consts, const_stride, size, result_slot, batch, nslots, d_out);
-    }
-    return BZH_E_ARG;
+    return with_field(field, [&](auto f) {
+        return expr_eval_t<decltype(f)>(ctx, p, nops, d_cols, d_strides, d_consts, const_stride, size, result_slot, batch, nslots, d_out);
+    });
 }
 
 
@@ -246,15 +243,10 @@ int expr_eval2(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint
     ScopedTimer t(ctx, BZH_T_QUOTIENT);
     const dim3 grid((unsigned)(size / kVm2Threads), (unsigned)batch), block(kVm2Threads);
     const ExprOp2* p = (const ExprOp2*)d_prog;
-    switch (field) {
-        case BZH_FIELD_FP:
-            hipLaunchKernelGGL((k_expr_vm2<FpParams>), grid, block, lds, ctx->stream, p, nops, d_cols, d_strides, d_consts, const_stride, size, d_out);
-            break;
-        case BZH_FIELD_FQ:
-            hipLaunchKernelGGL((k_expr_vm2<FqParams>), grid, block, lds, ctx->stream, p, nops, d_cols, d_strides, d_consts, const_stride, size, d_out);
-            break;
-        default: return BZH_E_ARG;
-    }
+    BZH_TRY(with_pasta_field(field, [&](auto f) {
+        hipLaunchKernelGGL((k_expr_vm2<decltype(f)>), grid, block, lds, ctx->stream, p, nops, d_cols, d_strides, d_consts, const_stride, size, d_out);
+        return BZH_OK;
+    }));
     BZH_HIP_TRY(ctx, hipGetLastError());
     return BZH_OK;
 }

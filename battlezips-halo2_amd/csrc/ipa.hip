@@ -33,6 +33,7 @@
 #include "block.cuh"
 #include "ctx.hpp"
 #include "curve.cuh"
+#include "host_field.hpp"
 
 namespace bzh {
 
@@ -61,157 +62,12 @@ __global__ void __launch_bounds__(256) k_ipa_s_update(const uint32_t* __restrict
     fe_store(s_new + (2 * g + 1) * 8, fe_mul(v, fe_load<P>(u)));
 }
 
-// ---------------------------------------------------------------------------
-// host-side field / point helpers (portable fe_mul)
-// ---------------------------------------------------------------------------
-template <class P>
-static Fe<P> h_load(const uint64_t* p) {
-    Fe<P> v;
-    for (int i = 0; i < 4; i++) {
-        v.l[2 * i] = (uint32_t)p[i];
-        v.l[2 * i + 1] = (uint32_t)(p[i] >> 32);
-    }
-    return v;
-}
-template <class P>
-static void h_store(uint64_t* p, const Fe<P>& v) {
-    for (int i = 0; i < 4; i++) p[i] = (uint64_t)v.l[2 * i] | ((uint64_t)v.l[2 * i + 1] << 32);
-}
-// Jacobian (Montgomery limbs as produced by msm_run) -> affine canonical x||y
-template <class PB>
-static void h_jac_to_affine_canonical(const uint64_t* xyz, uint64_t* xy) {
-    Fe<PB> X = h_load<PB>(xyz), Y = h_load<PB>(xyz + 4), Z = h_load<PB>(xyz + 8);
-    if (fe_is_zero(Z)) {
-        memset(xy, 0, 64);
-        return;
-    }
-    Fe<PB> zi = fe_inv(Z), zi2 = fe_sqr(zi), zi3 = fe_mul(zi2, zi);
-    h_store<PB>(xy, fe_from_mont(fe_mul(X, zi2)));
-    h_store<PB>(xy + 4, fe_from_mont(fe_mul(Y, zi3)));
-}
-// square root in the base field (Tonelli-Shanks; Montgomery in/out); returns false if non-residue
-template <class PB>
-static bool h_sqrt(const Fe<PB>& a, unsigned S, uint32_t gen, Fe<PB>& out) {
-    if (fe_is_zero(a)) {
-        out = a;
-        return true;
-    }
-    uint32_t pm1[8], tt[8], t1h[8];
-    uint64_t br = 1;
-    for (int i = 0; i < 8; i++) {
-        uint64_t d = (uint64_t)PB::mod(i) - br;
-        pm1[i] = (uint32_t)d;
-        br = (d >> 63) & 1;
-    }
-    auto shr = [](const uint32_t* in, unsigned s, uint32_t* o) {
-        for (int i = 0; i < 8; i++) {
-            unsigned src = i + s / 32;
-            uint64_t lo = src < 8 ? in[src] : 0, hi = src + 1 < 8 ? in[src + 1] : 0;
-            o[i] = (s % 32) ? (uint32_t)(((lo | (hi << 32)) >> (s % 32)) & 0xffffffffu) : (uint32_t)lo;
-        }
-    };
-    shr(pm1, S, tt);  // t = (p-1) / 2^S (odd)
-    // (t + 1) / 2
-    uint32_t tp1[8];
-    uint64_t c = 1;
-    for (int i = 0; i < 8; i++) {
-        c += tt[i];
-        tp1[i] = (uint32_t)c;
-        c >>= 32;
-    }
-    shr(tp1, 1, t1h);
-    Fe<PB> zgen = fe_pow(fe_from_u32<PB>(gen), tt);  // generator of the 2-Sylow subgroup
-    Fe<PB> x = fe_pow(a, t1h), b = fe_pow(a, tt);
-    const Fe<PB> one = fe_one<PB>();
-    unsigned m = S;
-    while (!fe_eq(b, one)) {
-        unsigned i = 0;
-        Fe<PB> b2 = b;
-        while (!fe_eq(b2, one)) {
-            b2 = fe_sqr(b2);
-            i++;
-            if (i >= m) return false;  // not a square
-        }
-        Fe<PB> w = zgen;
-        for (unsigned k = 0; k + i + 1 < m; k++) w = fe_sqr(w);
-        zgen = fe_sqr(w);
-        x = fe_mul(x, w);
-        b = fe_mul(b, zgen);
-        m = i;
-    }
-    out = x;
-    return fe_eq(fe_sqr(x), a);
-}
-
-template <class C>
-struct CurveMeta;
-template <>
-struct CurveMeta<VestaCurve> {
-    using SF = FpParams;
-    static constexpr int scalar_field = BZH_FIELD_FP;
-    static constexpr unsigned base_S = 32;
-    static constexpr uint32_t base_gen = 5;
-};
-template <>
-struct CurveMeta<PallasCurve> {
-    using SF = FqParams;
-    static constexpr int scalar_field = BZH_FIELD_FQ;
-    static constexpr unsigned base_S = 32;
-    static constexpr uint32_t base_gen = 5;
-};
-template <>
-struct CurveMeta<Bn254Curve> {
-    using SF = BnFrParams;
-    static constexpr int scalar_field = BZH_FIELD_BN254_FR;
-    static constexpr unsigned base_S = 1;
-    static constexpr uint32_t base_gen = 3;
-};
-
-// pasta_curves from_bytes: x little-endian, bit 255 = parity of y; zeros = identity
-template <class C>
-static bool h_decompress(const uint8_t* in, uint64_t* xy_canonical) {
-    using PB = typename C::Base;
-    uint8_t raw[32];
-    memcpy(raw, in, 32);
-    const unsigned ysign = raw[31] >> 7;
-    raw[31] &= 0x7f;
-    uint64_t xl[4];
-    memcpy(xl, raw, 32);
-    if (!(xl[0] | xl[1] | xl[2] | xl[3])) {
-        if (ysign) return false;
-        memset(xy_canonical, 0, 64);
-        return true;
-    }
-    Fe<PB> x = h_load<PB>(xl);
-    // canonical check x < p
-    {
-        Fe<PB> t = x;
-        fe_cond_sub_p(t, 0);
-        if (!fe_eq(t, x)) return false;
-    }
-    Fe<PB> xm = fe_to_mont(x);
-    Fe<PB> rhs = fe_add(fe_mul(fe_sqr(xm), xm), fe_from_u32<PB>(C::b));
-    Fe<PB> y;
-    if (!h_sqrt<PB>(rhs, CurveMeta<C>::base_S, CurveMeta<C>::base_gen, y)) return false;
-    Fe<PB> yc = fe_from_mont(y);
-    if ((yc.l[0] & 1u) != ysign) yc = fe_from_mont(fe_neg(y));
-    h_store<PB>(xy_canonical, x);
-    h_store<PB>(xy_canonical + 4, yc);
-    return true;
-}
-
 struct DevBuf {
     void* p = nullptr;
     ~DevBuf() {
         if (p) (void)hipFree(p);
     }
 };
-
-#define IPA_TRY(expr)             \
-    do {                          \
-        int rc__ = (expr);        \
-        if (rc__) return rc__;    \
-    } while (0)
 
 // ---------------------------------------------------------------------------
 // prover, batched: `batch` independent openings advance in lockstep so that every round is ONE
@@ -363,37 +219,13 @@ __global__ void __launch_bounds__(256) k_ipa_round_fold(const uint32_t* __restri
     }
 }
 
-// Jacobian (Montgomery limbs as produced by msm_run) -> affine canonical x||y for `cnt` points with ONE inversion
-template <class PB>
-static void h_jac_batch_to_affine_canonical(const uint64_t* xyz, size_t cnt, uint64_t* xy) {
-    std::vector<Fe<PB>> pre(cnt + 1);
-    pre[0] = fe_one<PB>();
-    for (size_t i = 0; i < cnt; i++) {
-        const Fe<PB> Z = h_load<PB>(xyz + i * 12 + 8);
-        pre[i + 1] = fe_is_zero(Z) ? pre[i] : fe_mul(pre[i], Z);
-    }
-    Fe<PB> inv = fe_inv(pre[cnt]);
-    for (size_t i = cnt; i-- > 0;) {
-        const Fe<PB> Z = h_load<PB>(xyz + i * 12 + 8);
-        if (fe_is_zero(Z)) {
-            memset(xy + i * 8, 0, 64);
-            continue;
-        }
-        const Fe<PB> zi = fe_mul(inv, pre[i]);
-        inv = fe_mul(inv, Z);
-        const Fe<PB> zi2 = fe_sqr(zi), zi3 = fe_mul(zi2, zi);
-        h_store<PB>(xy + i * 8, fe_from_mont(fe_mul(h_load<PB>(xyz + i * 12), zi2)));
-        h_store<PB>(xy + i * 8 + 4, fe_from_mont(fe_mul(h_load<PB>(xyz + i * 12 + 4), zi3)));
-    }
-}
-
 template <class C>
 static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint64_t* blinds,
                       const uint64_t* x3s, const uint8_t* rng_bytes, size_t rng_stride, bzh_transcript* const* trs,
                       uint64_t* out_v, const uint32_t* d_raw_in) {
-    using SF = typename CurveMeta<C>::SF;
+    using SF = typename CurveInfo<C>::SF;
     using PB = typename C::Base;
-    const int field = CurveMeta<C>::scalar_field;
+    const int field = CurveInfo<C>::scalar_field;
     const size_t n = bases->n - 2, B = batch;
     unsigned k = 0;
     while (((size_t)1 << k) < n) k++;
@@ -440,7 +272,7 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
                        (kHc + 4) * 8;
     const size_t tail_words = jstar ? B * (tail_m + 2) * (size_t)tail_nwin * (16 + 20) + (tail_scratch + 3) / 4 + 64 : 0;   // table + its fe29 copy
     void* arena = nullptr;
-    IPA_TRY(ws_ensure(ctx, 4, (B * per + tail_words) * 4 + 256 + 16 * 16, &arena));   // (+ the roundings of take())
+    BZH_TRY(ws_ensure(ctx, 4, (B * per + tail_words) * 4 + 256 + 16 * 16, &arena));   // (+ the roundings of take())
     uint32_t* cur = (uint32_t*)arena;
     auto take = [&](size_t w) {   // every piece starts 16-byte aligned (uint4 loads / stores): word counts rounded up to 4
         uint32_t* r = cur;
@@ -466,7 +298,7 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
     uint32_t* d_dv = take(B * 8);       // s(x3) / v per proof
     uint32_t* d_vlr = take(B * 2 * 8);  // value_l, value_r per proof
     void* d_out = nullptr;
-    IPA_TRY(ws_ensure(ctx, 5, 2 * B * 96, &d_out));
+    BZH_TRY(ws_ensure(ctx, 5, 2 * B * 96, &d_out));
 
     const unsigned g256 = 256;
     auto grid2 = [&](size_t c) { return dim3((unsigned)((c + g256 - 1) / g256), (unsigned)B); };
@@ -477,54 +309,54 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
         BZH_HIP_TRY(ctx, hipMemcpyAsync(d_raw, d_raw_in, B * nrand * 64, hipMemcpyDeviceToDevice, st));
     } else {
         for (size_t b = 0; b < B; b++)
-            IPA_TRY(h2d_small(ctx, d_raw + b * nrand * 16, rng_bytes + b * rng_stride, nrand * 64));
+            BZH_TRY(h2d_small(ctx, d_raw + b * nrand * 16, rng_bytes + b * rng_stride, nrand * 64));
     }
     hipLaunchKernelGGL((k_reduce_wide<SF>), dim3((unsigned)((B * nrand + g256 - 1) / g256)), dim3(g256), 0, st, d_raw, B * nrand,
                        d_rand);
     BZH_HIP_TRY(ctx, hipMemcpy2DAsync(d_spoly, n * 32, d_rand, nrand * 32, n * 32, B, hipMemcpyDeviceToDevice, st));
     // the scalars the host needs (s_blind and the round blinds) come back in one strided copy
     std::vector<Fe<SF>> tail(B * ntail);
-    for (size_t b = 0; b < B; b++) IPA_TRY(d2h_async(ctx, &tail[b * ntail], d_rand + (b * nrand + n) * 8, ntail * 32));
+    for (size_t b = 0; b < B; b++) BZH_TRY(d2h_async(ctx, &tail[b * ntail], d_rand + (b * nrand + n) * 8, ntail * 32));
 
     std::vector<Fe<SF>> hc(B * kHc, fe_zero<SF>());
-    for (size_t b = 0; b < B; b++) hc[b * kHc] = fe_to_mont(h_load<SF>(x3s + 4 * b));
+    for (size_t b = 0; b < B; b++) hc[b * kHc] = fe_to_mont(fe_from_u64<SF>(x3s + 4 * b));
     auto push_hc = [&]() -> int {
         return h2d_small(ctx, d_hc, hc.data(), B * kHc * 32);
     };
-    IPA_TRY(push_hc());
+    BZH_TRY(push_hc());
     // s(X) -= s(x3)
-    IPA_TRY(poly_eval(ctx, field, d_spoly, n, B, d_hc, kHc, d_dv));
+    BZH_TRY(poly_eval(ctx, field, d_spoly, n, B, d_hc, kHc, d_dv));
     hipLaunchKernelGGL((k_sub_at0_batch<SF>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, d_spoly, n, d_dv, B);
     // S = commit(s, s_blind): scalars [s..., 0, s_blind]
     hipLaunchKernelGGL((k_ipa_commit_scalars<SF>), grid2(n + 2), dim3(g256), 0, st, d_spoly, d_rand, n, nrand, d_commit);
     BZH_HIP_TRY(ctx, hipGetLastError());
-    IPA_TRY(msm_run(ctx, bases, d_commit, n + 2, B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
+    BZH_TRY(msm_run(ctx, bases, d_commit, n + 2, B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
     std::vector<uint64_t> jac(2 * B * 12), xy(2 * B * 8);
-    IPA_TRY(d2h_async(ctx, jac.data(), d_out, B * 96));
-    IPA_TRY(d2h_finish(ctx));
-    h_jac_batch_to_affine_canonical<PB>(jac.data(), B, xy.data());
+    BZH_TRY(d2h_async(ctx, jac.data(), d_out, B * 96));
+    BZH_TRY(d2h_finish(ctx));
+    h_jac_to_affine<PB>(jac.data(), B, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, xy.data());
     uint64_t ch[4];
     std::vector<Fe<SF>> f(B);
     for (size_t b = 0; b < B; b++) {
-        IPA_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + b * 8));
-        IPA_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
-        const Fe<SF> xi = fe_to_mont(h_load<SF>(ch));
-        IPA_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
+        BZH_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + b * 8));
+        BZH_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
+        const Fe<SF> xi = fe_to_mont(fe_from_u64<SF>(ch));
+        BZH_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
         hc[b * kHc + 1] = xi;
-        hc[b * kHc + 2] = fe_to_mont(h_load<SF>(ch));
-        f[b] = fe_add(fe_mul(tail[b * ntail], xi), fe_to_mont(h_load<SF>(blinds + 4 * b)));
+        hc[b * kHc + 2] = fe_to_mont(fe_from_u64<SF>(ch));
+        f[b] = fe_add(fe_mul(tail[b * ntail], xi), fe_to_mont(fe_from_u64<SF>(blinds + 4 * b)));
     }
-    IPA_TRY(push_hc());
+    BZH_TRY(push_hc());
     // p' = poly + xi * s_poly, then p'[0] -= v with v = p'(x3)
     hipLaunchKernelGGL((k_ipa_axpy<SF>), grid2(n), dim3(g256), 0, st, d_polys, d_spoly, d_hc, n, p_cur);
-    IPA_TRY(poly_eval(ctx, field, p_cur, n, B, d_hc, kHc, d_dv));
+    BZH_TRY(poly_eval(ctx, field, p_cur, n, B, d_hc, kHc, d_dv));
     hipLaunchKernelGGL((k_sub_at0_batch<SF>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, p_cur, n, d_dv, B);
     std::vector<Fe<SF>> vm(B);
-    IPA_TRY(d2h_async(ctx, vm.data(), d_dv, B * 32));  // lands at the next d2h_finish
+    BZH_TRY(d2h_async(ctx, vm.data(), d_dv, B * 32));  // lands at the next d2h_finish
     hipLaunchKernelGGL((k_ipa_init_b_s<SF>), grid2(n), dim3(g256), 0, st, d_hc, n, b_cur, s_cur);
     BZH_HIP_TRY(ctx, hipGetLastError());
 
-    std::vector<Fe<SF>> us(B), pre(B + 1);
+    std::vector<Fe<SF>> us(B), us_inv(B);
     // the instance the rounds run on: the SRS and n points, or (from round jstar on) the per-proof tables and tail_m points
     const bzh_bases* rb = bases;
     bzh_bases tail_bases;
@@ -532,13 +364,13 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
     unsigned j0 = 0;        // the round its s vector restarted at
     for (unsigned j = 0; j < k; j++) {
         if (jstar && j == jstar) {
-            IPA_TRY(msm_collapse_table(ctx, bases, s_cur, (size_t)1 << j, B, tail_c, d_tail_table29, d_tail_table, d_tail_scratch, &tail_bases));
+            BZH_TRY(msm_collapse_table(ctx, bases, s_cur, (size_t)1 << j, B, tail_c, d_tail_table29, d_tail_table, d_tail_scratch, &tail_bases));
             rb = &tail_bases;
             rn = tail_m;
             j0 = j;
             // s restarts at (1): the folded generators ARE the instance now
             std::vector<Fe<SF>> ones(B, fe_one<SF>());
-            IPA_TRY(h2d_small(ctx, s_cur, ones.data(), B * 32));
+            BZH_TRY(h2d_small(ctx, s_cur, ones.data(), B * 32));
         }
         const size_t m = n >> j, half = m >> 1, cnt = (size_t)1 << (j - j0);
         hipLaunchKernelGGL((k_ipa_inner2<SF>), dim3((unsigned)B, 2), dim3(256), 0, st, p_cur, b_cur, half, d_vlr);
@@ -546,34 +378,30 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
             hipLaunchKernelGGL((k_ipa_round_vectors_paired<SF>), grid2(rn + 1), dim3(g256), 0, st, p_cur, s_cur, rn, k - j, d_vlr, d_hc,
                                d_rand, nrand, n, j, d_lr);
             BZH_HIP_TRY(ctx, hipGetLastError());
-            IPA_TRY(msm_run_paired(ctx, rb, d_lr, rn, k - j, B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
+            BZH_TRY(msm_run_paired(ctx, rb, d_lr, rn, k - j, B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
         } else {
             hipLaunchKernelGGL((k_ipa_round_vectors<SF>), grid2(n + 1), dim3(g256), 0, st, p_cur, s_cur, n, k - j, d_vlr, d_hc,
                                d_rand, nrand, n, j, d_lr);
             BZH_HIP_TRY(ctx, hipGetLastError());
-            IPA_TRY(msm_run(ctx, bases, d_lr, n + 2, 2 * B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
+            BZH_TRY(msm_run(ctx, bases, d_lr, n + 2, 2 * B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
         }
-        IPA_TRY(d2h_async(ctx, jac.data(), d_out, 2 * B * 96));
-        IPA_TRY(d2h_finish(ctx));
-        h_jac_batch_to_affine_canonical<PB>(jac.data(), 2 * B, xy.data());
-        pre[0] = fe_one<SF>();
+        BZH_TRY(d2h_async(ctx, jac.data(), d_out, 2 * B * 96));
+        BZH_TRY(d2h_finish(ctx));
+        h_jac_to_affine<PB>(jac.data(), 2 * B, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, xy.data());
         for (size_t b = 0; b < B; b++) {
-            IPA_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + (2 * b) * 8));
-            IPA_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + (2 * b + 1) * 8));
-            IPA_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
-            us[b] = fe_to_mont(h_load<SF>(ch));
-            if (fe_is_zero(us[b])) return BZH_E_ARG;  // a zero challenge has no inverse (probability 2^-255)
-            pre[b + 1] = fe_mul(pre[b], us[b]);
+            BZH_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + (2 * b) * 8));
+            BZH_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + (2 * b + 1) * 8));
+            BZH_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
+            us[b] = fe_to_mont(fe_from_u64<SF>(ch));
         }
-        Fe<SF> inv = fe_inv(pre[B]);
-        for (size_t b = B; b-- > 0;) {
-            const Fe<SF> u_inv = fe_mul(inv, pre[b]);
-            inv = fe_mul(inv, us[b]);
+        us_inv = us;
+        if (!h_batch_invert(us_inv.data(), B)) return BZH_E_ARG;  // a zero challenge has no inverse (probability 2^-255)
+        for (size_t b = 0; b < B; b++) {
             hc[b * kHc + 3] = us[b];
-            hc[b * kHc + 4] = u_inv;
-            f[b] = fe_add(f[b], fe_add(fe_mul(tail[b * ntail + 1 + 2 * j], u_inv), fe_mul(tail[b * ntail + 2 + 2 * j], us[b])));
+            hc[b * kHc + 4] = us_inv[b];
+            f[b] = fe_add(f[b], fe_add(fe_mul(tail[b * ntail + 1 + 2 * j], us_inv[b]), fe_mul(tail[b * ntail + 2 + 2 * j], us[b])));
         }
-        IPA_TRY(push_hc());
+        BZH_TRY(push_hc());
         // p' <- p_lo + u^-1 p_hi ; b <- b_lo + u b_hi ; s <- s (x) (1, u)
         hipLaunchKernelGGL((k_ipa_round_fold<SF>), grid2(half > cnt ? half : cnt), dim3(g256), 0, st, p_cur, b_cur, s_cur, half, cnt,
                            d_hc, p_nxt, b_nxt, s_nxt);
@@ -583,15 +411,15 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
         std::swap(s_cur, s_nxt);
     }
     std::vector<Fe<SF>> c(B);
-    IPA_TRY(d2h_async(ctx, c.data(), p_cur, B * 32));
-    IPA_TRY(d2h_finish(ctx));
+    BZH_TRY(d2h_async(ctx, c.data(), p_cur, B * 32));
+    BZH_TRY(d2h_finish(ctx));
     for (size_t b = 0; b < B; b++) {
-        h_store<SF>(out_v + 4 * b, fe_from_mont(vm[b]));
+        fe_to_u64<SF>(out_v + 4 * b, fe_from_mont(vm[b]));
         uint64_t sc[4];
-        h_store<SF>(sc, fe_from_mont(c[b]));
-        IPA_TRY(bzh_transcript_write_scalar(trs[b], sc));
-        h_store<SF>(sc, fe_from_mont(f[b]));
-        IPA_TRY(bzh_transcript_write_scalar(trs[b], sc));
+        fe_to_u64<SF>(sc, fe_from_mont(c[b]));
+        BZH_TRY(bzh_transcript_write_scalar(trs[b], sc));
+        fe_to_u64<SF>(sc, fe_from_mont(f[b]));
+        BZH_TRY(bzh_transcript_write_scalar(trs[b], sc));
     }
     return BZH_OK;
 }
@@ -604,7 +432,7 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
 template <class C>
 static int ipa_verify_t(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                         const uint8_t* proof, size_t proof_len, bzh_transcript* tr, const uint64_t* g0_u_w_xy) {
-    using SF = typename CurveMeta<C>::SF;
+    using SF = typename CurveInfo<C>::SF;
     const size_t n = bases->n - 2;
     unsigned k = 0;
     while (((size_t)1 << k) < n) k++;
@@ -623,37 +451,31 @@ static int ipa_verify_t(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* co
         return any == 0;
     };
     if (!h_decompress<C>(proof, S) || is_identity(S)) return BZH_E_VERIFY;
-    IPA_TRY(bzh_transcript_common_point(tr, S));
-    IPA_TRY(bzh_transcript_squeeze_challenge(tr, ch));
-    const Fe<SF> xi = fe_to_mont(h_load<SF>(ch));
-    IPA_TRY(bzh_transcript_squeeze_challenge(tr, ch));
-    const Fe<SF> z = fe_to_mont(h_load<SF>(ch));
+    BZH_TRY(bzh_transcript_common_point(tr, S));
+    BZH_TRY(bzh_transcript_squeeze_challenge(tr, ch));
+    const Fe<SF> xi = fe_to_mont(fe_from_u64<SF>(ch));
+    BZH_TRY(bzh_transcript_squeeze_challenge(tr, ch));
+    const Fe<SF> z = fe_to_mont(fe_from_u64<SF>(ch));
     std::vector<Fe<SF>> us(k);
     for (unsigned j = 0; j < k; j++) {
         uint64_t* L = &pts[(2 * j) * 8];
         uint64_t* R = &pts[(2 * j + 1) * 8];
         if (!h_decompress<C>(proof + 32 + 64 * j, L) || !h_decompress<C>(proof + 64 + 64 * j, R)) return BZH_E_VERIFY;
         if (is_identity(L) || is_identity(R)) return BZH_E_VERIFY;
-        IPA_TRY(bzh_transcript_common_point(tr, L));
-        IPA_TRY(bzh_transcript_common_point(tr, R));
-        IPA_TRY(bzh_transcript_squeeze_challenge(tr, ch));
-        us[j] = fe_to_mont(h_load<SF>(ch));
+        BZH_TRY(bzh_transcript_common_point(tr, L));
+        BZH_TRY(bzh_transcript_common_point(tr, R));
+        BZH_TRY(bzh_transcript_squeeze_challenge(tr, ch));
+        us[j] = fe_to_mont(fe_from_u64<SF>(ch));
         if (fe_is_zero(us[j])) return BZH_E_VERIFY;
-        h_store<SF>(&scal[(2 * j) * 4], fe_from_mont(fe_inv(us[j])));
-        h_store<SF>(&scal[(2 * j + 1) * 4], fe_from_mont(us[j]));
+        fe_to_u64<SF>(&scal[(2 * j) * 4], fe_from_mont(fe_inv(us[j])));
+        fe_to_u64<SF>(&scal[(2 * j + 1) * 4], fe_from_mont(us[j]));
     }
     uint64_t cl[4], fl[4];
     memcpy(cl, proof + 32 + 64 * k, 32);
     memcpy(fl, proof + 64 + 64 * k, 32);
-    Fe<SF> c = h_load<SF>(cl), f = h_load<SF>(fl);
-    {
-        Fe<SF> t = c;
-        fe_cond_sub_p(t, 0);
-        Fe<SF> t2 = f;
-        fe_cond_sub_p(t2, 0);
-        if (!fe_eq(t, c) || !fe_eq(t2, f)) return BZH_E_VERIFY;  // non-canonical scalars
-    }
-    const Fe<SF> cm = fe_to_mont(c), fm = fe_to_mont(f), x3m = fe_to_mont(h_load<SF>(x3)), vm = fe_to_mont(h_load<SF>(v));
+    Fe<SF> c = fe_from_u64<SF>(cl), f = fe_from_u64<SF>(fl);
+    if (!is_canonical(c) || !is_canonical(f)) return BZH_E_VERIFY;
+    const Fe<SF> cm = fe_to_mont(c), fm = fe_to_mont(f), x3m = fe_to_mont(fe_from_u64<SF>(x3)), vm = fe_to_mont(fe_from_u64<SF>(v));
     // b_0 = prod_j (1 + u_j x3^(2^(k-1-j)))
     std::vector<Fe<SF>> xp(k ? k : 1);
     if (k) {
@@ -665,19 +487,19 @@ static int ipa_verify_t(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* co
     // left-side table tail: P (1), G_0 (-v), S (xi), U (-c b0 z), W (-f)
     size_t o = 2 * (size_t)k;
     memcpy(&pts[o * 8], commitment_xy, 64);
-    h_store<SF>(&scal[o * 4], fe_from_mont(fe_one<SF>()));
+    fe_to_u64<SF>(&scal[o * 4], fe_from_mont(fe_one<SF>()));
     o++;
     memcpy(&pts[o * 8], g0_u_w_xy, 64);
-    h_store<SF>(&scal[o * 4], fe_from_mont(fe_neg(vm)));
+    fe_to_u64<SF>(&scal[o * 4], fe_from_mont(fe_neg(vm)));
     o++;
     memcpy(&pts[o * 8], S, 64);
-    h_store<SF>(&scal[o * 4], fe_from_mont(xi));
+    fe_to_u64<SF>(&scal[o * 4], fe_from_mont(xi));
     o++;
     memcpy(&pts[o * 8], g0_u_w_xy + 8, 64);
-    h_store<SF>(&scal[o * 4], fe_from_mont(fe_neg(fe_mul(fe_mul(cm, b0), z))));
+    fe_to_u64<SF>(&scal[o * 4], fe_from_mont(fe_neg(fe_mul(fe_mul(cm, b0), z))));
     o++;
     memcpy(&pts[o * 8], g0_u_w_xy + 16, 64);
-    h_store<SF>(&scal[o * 4], fe_from_mont(fe_neg(fm)));
+    fe_to_u64<SF>(&scal[o * 4], fe_from_mont(fe_neg(fm)));
 
     // device: s vector (started at c) and the two MSMs
     DevBuf arena;
@@ -702,31 +524,25 @@ static int ipa_verify_t(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* co
     }
     BZH_HIP_TRY(ctx, hipMemsetAsync(s_cur + n * 8, 0, 64, st));  // no U / W contribution on the right
     void* d_out = nullptr;
-    IPA_TRY(ws_ensure(ctx, 3, 4 * 96, &d_out));
-    IPA_TRY(msm_run(ctx, bases, s_cur, n + 2, 1, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
+    BZH_TRY(ws_ensure(ctx, 3, 4 * 96, &d_out));
+    BZH_TRY(msm_run(ctx, bases, s_cur, n + 2, 1, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
     uint64_t jac[24];
     BZH_HIP_TRY(ctx, hipMemcpyAsync(jac, d_out, 96, hipMemcpyDeviceToHost, st));
     // left side on an ad-hoc table (canonical in)
     BZH_HIP_TRY(ctx, hipMemcpyAsync(d_pts, pts.data(), nl * 64, hipMemcpyHostToDevice, st));
     BZH_HIP_TRY(ctx, hipMemcpyAsync(d_scal, scal.data(), nl * 32, hipMemcpyHostToDevice, st));
-    IPA_TRY(bases_to_montgomery(ctx, C::id, d_pts, nl));
+    BZH_TRY(bases_to_montgomery(ctx, C::id, d_pts, nl));
     bzh_bases tmp;
     tmp.curve = C::id;
     tmp.n = nl;
     tmp.d_xy = d_pts;
     tmp.device = ctx->device;
-    IPA_TRY(msm_run(ctx, &tmp, d_scal, nl, 1, BZH_FORM_CANONICAL, (uint32_t*)d_out + 24));
+    BZH_TRY(msm_run(ctx, &tmp, d_scal, nl, 1, BZH_FORM_CANONICAL, (uint32_t*)d_out + 24));
     BZH_HIP_TRY(ctx, hipMemcpyAsync(jac + 12, (uint32_t*)d_out + 24, 96, hipMemcpyDeviceToHost, st));
     BZH_HIP_TRY(ctx, hipStreamSynchronize(st));
     uint64_t rhs[8], lhs[8];
-    h_jac_to_affine_canonical<typename C::Base>(jac, rhs);
-    // the second MSM ran with canonical form: its output limbs are canonical, convert for the helper
-    {
-        using PB = typename C::Base;
-        uint64_t jm[12];
-        for (int q = 0; q < 3; q++) h_store<PB>(jm + 4 * q, fe_to_mont(h_load<PB>(jac + 12 + 4 * q)));
-        h_jac_to_affine_canonical<PB>(jm, lhs);
-    }
+    h_jac_to_affine<typename C::Base>(jac, 1, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, rhs);
+    h_jac_to_affine<typename C::Base>(jac + 12, 1, BZH_FORM_CANONICAL, BZH_FORM_CANONICAL, lhs);  // the second MSM ran with canonical form
     return memcmp(lhs, rhs, 64) == 0 ? BZH_OK : BZH_E_VERIFY;
 }
 
@@ -802,7 +618,7 @@ __global__ void __launch_bounds__(kSmallMsmThreads) k_ipa_small_msm(const uint32
 template <class C>
 static int ipa_check_batch_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts,
                              const uint64_t* lc_scal, const uint64_t* cu /* batch x (k+1) canonical: c, u_j */, int* ok) {
-    using SF = typename CurveMeta<C>::SF;
+    using SF = typename CurveInfo<C>::SF;
     using PB = typename C::Base;
     const size_t n = bases->n - 2, B = batch;
     unsigned k = 0;
@@ -812,7 +628,7 @@ static int ipa_check_batch_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch,
     const size_t na = B * nl;  // every opening's own nl points and scalars, side by side
     const size_t words = B * (n + 2) * 8 + B * (k + 1) * 8 + na * 16 + na * 8 + 2 * B * 24 + 256;
     void* arena = nullptr;
-    IPA_TRY(ws_ensure(ctx, 4, words * 4, &arena));
+    BZH_TRY(ws_ensure(ctx, 4, words * 4, &arena));
     uint32_t* d_s = (uint32_t*)arena;
     uint32_t* d_cu = d_s + B * (n + 2) * 8;
     uint32_t* d_pts = d_cu + B * (k + 1) * 8;
@@ -820,56 +636,48 @@ static int ipa_check_batch_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch,
     uint32_t* d_out = d_scal + na * 8;
     // right side
     std::vector<Fe<SF>> cum(B * (k + 1));
-    for (size_t i = 0; i < cum.size(); i++) cum[i] = fe_to_mont(h_load<SF>(cu + 4 * i));
-    IPA_TRY(h2d_small(ctx, d_cu, cum.data(), cum.size() * 32));
+    for (size_t i = 0; i < cum.size(); i++) cum[i] = fe_to_mont(fe_from_u64<SF>(cu + 4 * i));
+    BZH_TRY(h2d_small(ctx, d_cu, cum.data(), cum.size() * 32));
     hipLaunchKernelGGL((k_ipa_verify_s<SF>), dim3((unsigned)((n + 2 + 255) / 256), (unsigned)B), dim3(256), 0, st, d_cu, n, k, d_s);
     BZH_HIP_TRY(ctx, hipGetLastError());
-    IPA_TRY(msm_run(ctx, bases, d_s, n + 2, B, BZH_FORM_MONTGOMERY, d_out));
+    BZH_TRY(msm_run(ctx, bases, d_s, n + 2, B, BZH_FORM_MONTGOMERY, d_out));
     // left side: B independent nl-term sums
-    IPA_TRY(h2d_small(ctx, d_pts, lc_pts, na * 64));
-    IPA_TRY(bases_to_montgomery(ctx, C::id, d_pts, na));
-    IPA_TRY(h2d_small(ctx, d_scal, lc_scal, na * 32));
+    BZH_TRY(h2d_small(ctx, d_pts, lc_pts, na * 64));
+    BZH_TRY(bases_to_montgomery(ctx, C::id, d_pts, na));
+    BZH_TRY(h2d_small(ctx, d_scal, lc_scal, na * 32));
     hipLaunchKernelGGL((k_ipa_small_msm<C>), dim3((unsigned)B), dim3(kSmallMsmThreads), 0, st, d_pts, d_scal, nl, d_out + B * 24);
     BZH_HIP_TRY(ctx, hipGetLastError());
     std::vector<uint64_t> jac(2 * B * 12), lhs(B * 8), rhs(B * 8);
-    IPA_TRY(d2h_async(ctx, jac.data(), d_out, 2 * B * 96));
-    IPA_TRY(d2h_finish(ctx));
-    h_jac_batch_to_affine_canonical<PB>(jac.data(), B, rhs.data());
-    h_jac_batch_to_affine_canonical<PB>(jac.data() + B * 12, B, lhs.data());
+    BZH_TRY(d2h_async(ctx, jac.data(), d_out, 2 * B * 96));
+    BZH_TRY(d2h_finish(ctx));
+    h_jac_to_affine<PB>(jac.data(), B, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, rhs.data());
+    h_jac_to_affine<PB>(jac.data() + B * 12, B, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, lhs.data());
     for (size_t b = 0; b < B; b++) ok[b] = memcmp(&lhs[b * 8], &rhs[b * 8], 64) == 0;
     return BZH_OK;
 }
 
 int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
                     const uint64_t* cu, int* ok) {
-    switch (bases->curve) {
-        case BZH_CURVE_VESTA: return ipa_check_batch_t<VestaCurve>(ctx, bases, batch, nl, lc_pts, lc_scal, cu, ok);
-        case BZH_CURVE_PALLAS: return ipa_check_batch_t<PallasCurve>(ctx, bases, batch, nl, lc_pts, lc_scal, cu, ok);
-        case BZH_CURVE_BN254: return ipa_check_batch_t<Bn254Curve>(ctx, bases, batch, nl, lc_pts, lc_scal, cu, ok);
-    }
-    return BZH_E_ARG;
+    return with_curve(bases->curve, [&](auto c) { return ipa_check_batch_t<decltype(c)>(ctx, bases, batch, nl, lc_pts, lc_scal, cu, ok); });
 }
 
 // pasta_curves from_bytes for one compressed point (host): false = not on the curve / non-canonical
 bool point_decompress(int curve, const uint8_t* in, uint64_t* xy_canonical) {
-    switch (curve) {
-        case BZH_CURVE_VESTA: return h_decompress<VestaCurve>(in, xy_canonical);
-        case BZH_CURVE_PALLAS: return h_decompress<PallasCurve>(in, xy_canonical);
-        case BZH_CURVE_BN254: return h_decompress<Bn254Curve>(in, xy_canonical);
-    }
-    return false;
+    bool ok = false;
+    with_curve(curve, [&](auto c) {
+        ok = h_decompress<decltype(c)>(in, xy_canonical);
+        return BZH_OK;
+    });
+    return ok;
 }
 
 int random_field(bzh_ctx* ctx, int field, const uint32_t* d_raw, size_t count, uint32_t* d_out) {
     if (!count) return BZH_OK;
     const dim3 grid((unsigned)((count + 255) / 256)), block(256);
-    switch (field) {
-        case BZH_FIELD_FP: hipLaunchKernelGGL((k_reduce_wide<FpParams>), grid, block, 0, ctx->stream, d_raw, count, d_out); break;
-        case BZH_FIELD_FQ: hipLaunchKernelGGL((k_reduce_wide<FqParams>), grid, block, 0, ctx->stream, d_raw, count, d_out); break;
-        case BZH_FIELD_BN254_FR: hipLaunchKernelGGL((k_reduce_wide<BnFrParams>), grid, block, 0, ctx->stream, d_raw, count, d_out); break;
-        case BZH_FIELD_BN254_FQ: hipLaunchKernelGGL((k_reduce_wide<BnFqParams>), grid, block, 0, ctx->stream, d_raw, count, d_out); break;
-        default: return BZH_E_ARG;
-    }
+    BZH_TRY(with_field(field, [&](auto p) {
+        hipLaunchKernelGGL((k_reduce_wide<decltype(p)>), grid, block, 0, ctx->stream, d_raw, count, d_out);
+        return BZH_OK;
+    }));
     BZH_HIP_TRY(ctx, hipGetLastError());
     return BZH_OK;
 }
@@ -877,21 +685,15 @@ int random_field(bzh_ctx* ctx, int field, const uint32_t* d_raw, size_t count, u
 int ipa_open(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint64_t* blinds,
              const uint64_t* x3s, const uint8_t* rng_bytes, size_t rng_stride, bzh_transcript* const* trs, uint64_t* out_v,
              const uint32_t* d_raw_in) {
-    switch (bases->curve) {
-        case BZH_CURVE_VESTA: return ipa_open_t<VestaCurve>(ctx, bases, d_polys, batch, blinds, x3s, rng_bytes, rng_stride, trs, out_v, d_raw_in);
-        case BZH_CURVE_PALLAS: return ipa_open_t<PallasCurve>(ctx, bases, d_polys, batch, blinds, x3s, rng_bytes, rng_stride, trs, out_v, d_raw_in);
-        case BZH_CURVE_BN254: return ipa_open_t<Bn254Curve>(ctx, bases, d_polys, batch, blinds, x3s, rng_bytes, rng_stride, trs, out_v, d_raw_in);
-    }
-    return BZH_E_ARG;
+    return with_curve(bases->curve, [&](auto c) {
+        return ipa_open_t<decltype(c)>(ctx, bases, d_polys, batch, blinds, x3s, rng_bytes, rng_stride, trs, out_v, d_raw_in);
+    });
 }
 int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                const uint8_t* proof, size_t proof_len, bzh_transcript* tr, const uint64_t* g0_u_w_xy) {
-    switch (bases->curve) {
-        case BZH_CURVE_VESTA: return ipa_verify_t<VestaCurve>(ctx, bases, commitment_xy, x3, v, proof, proof_len, tr, g0_u_w_xy);
-        case BZH_CURVE_PALLAS: return ipa_verify_t<PallasCurve>(ctx, bases, commitment_xy, x3, v, proof, proof_len, tr, g0_u_w_xy);
-        case BZH_CURVE_BN254: return ipa_verify_t<Bn254Curve>(ctx, bases, commitment_xy, x3, v, proof, proof_len, tr, g0_u_w_xy);
-    }
-    return BZH_E_ARG;
+    return with_curve(bases->curve, [&](auto c) {
+        return ipa_verify_t<decltype(c)>(ctx, bases, commitment_xy, x3, v, proof, proof_len, tr, g0_u_w_xy);
+    });
 }
 
 }  // namespace bzh

@@ -20,6 +20,7 @@
 // Modular-integer work (v_mad_u64_u32), no MFMA.
 #include "ctx.hpp"
 #include "curve29.cuh"
+#include "host_field.hpp"
 
 namespace bzh {
 
@@ -1287,15 +1288,10 @@ static int msm_run_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_sca
 
 int msm_run(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_scalars, size_t n, size_t batch, int form,
             uint32_t* d_out_xyz) {
-    switch (bases->curve) {
-        case BZH_CURVE_VESTA:
-            return msm_run_t<VestaCurve, FpParams>(ctx, bases, d_scalars, n, batch, form, d_out_xyz, nullptr);
-        case BZH_CURVE_PALLAS:
-            return msm_run_t<PallasCurve, FqParams>(ctx, bases, d_scalars, n, batch, form, d_out_xyz, nullptr);
-        case BZH_CURVE_BN254:
-            return msm_run_t<Bn254Curve, BnFrParams>(ctx, bases, d_scalars, n, batch, form, d_out_xyz, nullptr);
-    }
-    return BZH_E_ARG;
+    return with_curve(bases->curve, [&](auto c) {
+        using C = decltype(c);
+        return msm_run_t<C, typename CurveInfo<C>::SF>(ctx, bases, d_scalars, n, batch, form, d_out_xyz, nullptr);
+    });
 }
 
 // Paired MSM against a window table of n_pair + 2 points: each of the `batch` dense vectors of n_pair + 4 scalars
@@ -1307,15 +1303,10 @@ int msm_run_paired(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_scala
                    int form, uint32_t* d_out_xyz) {
     if (!bases->pre_c || bases->n != n_pair + 2 || log_m < 1) return BZH_E_ARG;
     const MsmPair pair{log_m, n_pair, 0};
-    switch (bases->curve) {
-        case BZH_CURVE_VESTA:
-            return msm_run_t<VestaCurve, FpParams>(ctx, bases, d_scalars, n_pair + 4, batch, form, d_out_xyz, &pair);
-        case BZH_CURVE_PALLAS:
-            return msm_run_t<PallasCurve, FqParams>(ctx, bases, d_scalars, n_pair + 4, batch, form, d_out_xyz, &pair);
-        case BZH_CURVE_BN254:
-            return msm_run_t<Bn254Curve, BnFrParams>(ctx, bases, d_scalars, n_pair + 4, batch, form, d_out_xyz, &pair);
-    }
-    return BZH_E_ARG;
+    return with_curve(bases->curve, [&](auto c) {
+        using C = decltype(c);
+        return msm_run_t<C, typename CurveInfo<C>::SF>(ctx, bases, d_scalars, n_pair + 4, batch, form, d_out_xyz, &pair);
+    });
 }
 
 // the fe29 copy of a table (bzh_bases::d_xy29): 20 words per point
@@ -1375,31 +1366,17 @@ int bases_precompute(bzh_ctx* ctx, bzh_bases* b, int window_bits) {
     if (b->pre_c != 0 || b->n == 0) return BZH_OK;
     int c = window_bits ? window_bits : plan_precompute_c(b->n);
     if (c < 4 || c > 15) return BZH_E_RANGE;
-    switch (b->curve) {
-        case BZH_CURVE_VESTA: return bases_precompute_t<VestaCurve>(ctx, b, c);
-        case BZH_CURVE_PALLAS: return bases_precompute_t<PallasCurve>(ctx, b, c);
-        case BZH_CURVE_BN254: return bases_precompute_t<Bn254Curve>(ctx, b, c);
-    }
-    return BZH_E_ARG;
+    return with_curve(b->curve, [&](auto cv) { return bases_precompute_t<decltype(cv)>(ctx, b, c); });
 }
 
 int bases_to_montgomery(bzh_ctx* ctx, int curve, uint32_t* d_xy, size_t n) {
     const size_t count = n * 2;
     if (count == 0) return BZH_OK;
     dim3 grid((unsigned)((count + 255) / 256)), block(256);
-    switch (curve) {
-        case BZH_CURVE_VESTA:
-            hipLaunchKernelGGL((k_to_montgomery<FqParams>), grid, block, 0, ctx->stream, d_xy, count);
-            break;
-        case BZH_CURVE_PALLAS:
-            hipLaunchKernelGGL((k_to_montgomery<FpParams>), grid, block, 0, ctx->stream, d_xy, count);
-            break;
-        case BZH_CURVE_BN254:
-            hipLaunchKernelGGL((k_to_montgomery<BnFqParams>), grid, block, 0, ctx->stream, d_xy, count);
-            break;
-        default:
-            return BZH_E_ARG;
-    }
+    BZH_TRY(with_curve(curve, [&](auto c) {
+        hipLaunchKernelGGL((k_to_montgomery<typename decltype(c)::Base>), grid, block, 0, ctx->stream, d_xy, count);
+        return BZH_OK;
+    }));
     BZH_HIP_TRY(ctx, hipGetLastError());
     return BZH_OK;
 }
@@ -1705,12 +1682,11 @@ static int msm_collapse_table_t(bzh_ctx* ctx, const bzh_bases* srs, const uint32
 
 int msm_collapse_table(bzh_ctx* ctx, const bzh_bases* srs, const uint32_t* d_s, size_t cnt, size_t batch, int c_tail, uint32_t* d_table29,
                        uint32_t* d_table, void* d_scratch, bzh_bases* out) {
-    switch (srs->curve) {
-        case BZH_CURVE_VESTA: return msm_collapse_table_t<VestaCurve, FpParams>(ctx, srs, d_s, cnt, batch, c_tail, d_table29, d_table, d_scratch, out);
-        case BZH_CURVE_PALLAS: return msm_collapse_table_t<PallasCurve, FqParams>(ctx, srs, d_s, cnt, batch, c_tail, d_table29, d_table, d_scratch, out);
-        case BZH_CURVE_BN254: return msm_collapse_table_t<Bn254Curve, BnFrParams>(ctx, srs, d_s, cnt, batch, c_tail, nullptr, d_table, d_scratch, out);
-    }
-    return BZH_E_ARG;
+    return with_curve(srs->curve, [&](auto c) {
+        using C = decltype(c);
+        uint32_t* t29 = fe29_supported<typename C::Base>() ? d_table29 : nullptr;
+        return msm_collapse_table_t<C, typename CurveInfo<C>::SF>(ctx, srs, d_s, cnt, batch, c_tail, t29, d_table, d_scratch, out);
+    });
 }
 
 }  // namespace bzh

@@ -27,6 +27,7 @@
 #include <cstring>
 #include <vector>
 
+#include "host_field.hpp"
 #include "ntt_common.cuh"
 
 namespace bzh {
@@ -497,26 +498,17 @@ __global__ void __launch_bounds__(256) k_field_convert(uint32_t* data, size_t co
 int field_convert(bzh_ctx* ctx, int field, uint32_t* d, size_t count, int to_mont) {
     if (!count) return BZH_OK;
     dim3 grid((unsigned)((count + 255) / 256)), block(256);
-    switch (field) {
-        case BZH_FIELD_FP: hipLaunchKernelGGL((k_field_convert<FpParams>), grid, block, 0, ctx->stream, d, count, to_mont); break;
-        case BZH_FIELD_FQ: hipLaunchKernelGGL((k_field_convert<FqParams>), grid, block, 0, ctx->stream, d, count, to_mont); break;
-        case BZH_FIELD_BN254_FR: hipLaunchKernelGGL((k_field_convert<BnFrParams>), grid, block, 0, ctx->stream, d, count, to_mont); break;
-        case BZH_FIELD_BN254_FQ: hipLaunchKernelGGL((k_field_convert<BnFqParams>), grid, block, 0, ctx->stream, d, count, to_mont); break;
-        default: return BZH_E_ARG;
-    }
+    BZH_TRY(with_field(field, [&](auto p) {
+        hipLaunchKernelGGL((k_field_convert<decltype(p)>), grid, block, 0, ctx->stream, d, count, to_mont);
+        return BZH_OK;
+    }));
     BZH_HIP_TRY(ctx, hipGetLastError());
     return BZH_OK;
 }
 
 int ntt_run(bzh_ctx* ctx, int field, uint32_t* d_data, unsigned log_n, size_t batch, const uint64_t* omega,
             const uint64_t* coset_shift, int inverse, int form) {
-    switch (field) {
-        case BZH_FIELD_FP: return ntt_run_t<FpParams>(ctx, d_data, log_n, batch, omega, coset_shift, inverse, form);
-        case BZH_FIELD_FQ: return ntt_run_t<FqParams>(ctx, d_data, log_n, batch, omega, coset_shift, inverse, form);
-        case BZH_FIELD_BN254_FR: return ntt_run_t<BnFrParams>(ctx, d_data, log_n, batch, omega, coset_shift, inverse, form);
-        case BZH_FIELD_BN254_FQ: return ntt_run_t<BnFqParams>(ctx, d_data, log_n, batch, omega, coset_shift, inverse, form);
-    }
-    return BZH_E_ARG;
+    return with_field(field, [&](auto p) { return ntt_run_t<decltype(p)>(ctx, d_data, log_n, batch, omega, coset_shift, inverse, form); });
 }
 
 // coeff_to_extended without the padded copy: `batch` polynomials of 2^src_log coefficients at d_src (pitch 2^src_log)
@@ -525,13 +517,13 @@ int ntt_run_padded(bzh_ctx* ctx, int field, uint32_t* d_dst, const uint32_t* d_s
                    const uint64_t* omega, const uint64_t* coset_shift, uint32_t* d_out29) {
     const int f = BZH_FORM_MONTGOMERY;
     if (d_out29 && field != BZH_FIELD_FP && field != BZH_FIELD_FQ) return BZH_E_ARG;
-    switch (field) {
-        case BZH_FIELD_FP: return ntt_run_t<FpParams>(ctx, d_dst, log_n, batch, omega, coset_shift, 0, f, d_src, src_log, d_out29);
-        case BZH_FIELD_FQ: return ntt_run_t<FqParams>(ctx, d_dst, log_n, batch, omega, coset_shift, 0, f, d_src, src_log, d_out29);
-        case BZH_FIELD_BN254_FR: return ntt_run_t<BnFrParams>(ctx, d_dst, log_n, batch, omega, coset_shift, 0, f, d_src, src_log);
-        case BZH_FIELD_BN254_FQ: return ntt_run_t<BnFqParams>(ctx, d_dst, log_n, batch, omega, coset_shift, 0, f, d_src, src_log);
-    }
-    return BZH_E_ARG;
+    return with_field(field, [&](auto p) {
+        using P = decltype(p);
+        if constexpr (fe29_supported<P>())   // the Pasta fields
+            return ntt_run_t<P>(ctx, d_dst, log_n, batch, omega, coset_shift, 0, f, d_src, src_log, d_out29);
+        else
+            return ntt_run_t<P>(ctx, d_dst, log_n, batch, omega, coset_shift, 0, f, d_src, src_log);
+    });
 }
 
 }  // namespace bzh

@@ -11,6 +11,7 @@
 // Integer VALU work like everything else here; algorithmic bytes: 64 B in (two scalars) + 64 B out per commitment.
 #include "ctx.hpp"
 #include "curve.cuh"
+#include "host_field.hpp"
 #include "pedersen_generators.hpp"
 
 using namespace bzh;
@@ -76,16 +77,6 @@ __global__ void __launch_bounds__(64) k_pedersen_commit(const uint32_t* __restri
     fe_store<PB>(out + i * 16 + 8, fe_from_mont(a.y));
 }
 
-static bool lt_modulus_fq(const uint64_t* v) {
-    uint32_t w[8];
-    memcpy(w, v, 32);
-    for (int i = 7; i >= 0; i--) {
-        if (w[i] < FqParams::mod(i)) return true;
-        if (w[i] > FqParams::mod(i)) return false;
-    }
-    return false;
-}
-
 static int ensure_table(bzh_ctx* ctx) {
     if (ctx->ped_tbl) return BZH_OK;
     uint32_t gens[32];
@@ -121,7 +112,7 @@ extern "C" int bzh_pedersen_commit_batch(bzh_ctx* ctx, const uint64_t* messages,
     if (!ctx || !messages || !trapdoors || !out_xy || !n || n > ((size_t)1 << 24)) return BZH_E_ARG;
     for (size_t i = 0; i < n; i++) {
         // Fq::from_repr(message.to_repr()).unwrap() / a trapdoor that is an Fq: non-canonical reprs are refused (panic upstream)
-        if (!lt_modulus_fq(messages + 4 * i) || !lt_modulus_fq(trapdoors + 4 * i)) return BZH_E_RANGE;
+        if (!is_canonical(fe_from_u64<FqParams>(messages + 4 * i)) || !is_canonical(fe_from_u64<FqParams>(trapdoors + 4 * i))) return BZH_E_RANGE;
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));

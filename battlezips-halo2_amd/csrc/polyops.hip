@@ -13,6 +13,7 @@
 #include "block.cuh"
 #include "ctx.hpp"
 #include "field.cuh"
+#include "host_field.hpp"
 
 namespace bzh {
 
@@ -268,30 +269,15 @@ static int eval_poly_t(bzh_ctx* ctx, const uint32_t* coeffs, size_t n, size_t ba
     return BZH_OK;
 }
 
-#define BZH_FIELD_SWITCH(field, CALL)                     \
-    switch (field) {                                      \
-        case BZH_FIELD_FP: return CALL(FpParams);         \
-        case BZH_FIELD_FQ: return CALL(FqParams);         \
-        case BZH_FIELD_BN254_FR: return CALL(BnFrParams); \
-        case BZH_FIELD_BN254_FQ: return CALL(BnFqParams); \
-    }                                                     \
-    return BZH_E_ARG;
-
 int poly_batch_invert(bzh_ctx* ctx, int field, uint32_t* d, size_t count) {
-#define CALL(PP) batch_invert_t<PP>(ctx, d, count)
-    BZH_FIELD_SWITCH(field, CALL)
-#undef CALL
+    return with_field(field, [&](auto p) { return batch_invert_t<decltype(p)>(ctx, d, count); });
 }
 int poly_prefix_product(bzh_ctx* ctx, int field, uint32_t* d, size_t n, size_t batch) {
-#define CALL(PP) prefix_scan_t<PP, MulOp<PP>>(ctx, d, n, batch)
-    BZH_FIELD_SWITCH(field, CALL)
-#undef CALL
+    return with_field(field, [&](auto p) { return prefix_scan_t<decltype(p), MulOp<decltype(p)>>(ctx, d, n, batch); });
 }
 int poly_eval(bzh_ctx* ctx, int field, const uint32_t* coeffs, size_t n, size_t batch, const uint32_t* xs, size_t x_stride,
               uint32_t* out) {
-#define CALL(PP) eval_poly_t<PP>(ctx, coeffs, n, batch, xs, x_stride, out)
-    BZH_FIELD_SWITCH(field, CALL)
-#undef CALL
+    return with_field(field, [&](auto p) { return eval_poly_t<decltype(p)>(ctx, coeffs, n, batch, xs, x_stride, out); });
 }
 
 // ---------------------------------------------------------------------------
@@ -401,9 +387,7 @@ static int kate_t(bzh_ctx* ctx, const uint32_t* d_c, size_t n, size_t batch, con
     return BZH_OK;
 }
 int poly_kate_division(bzh_ctx* ctx, int field, const uint32_t* d_c, size_t n, size_t batch, const uint32_t* d_xs, uint32_t* d_q) {
-#define CALL(PP) kate_t<PP>(ctx, d_c, n, batch, d_xs, d_q)
-    BZH_FIELD_SWITCH(field, CALL)
-#undef CALL
+    return with_field(field, [&](auto p) { return kate_t<decltype(p)>(ctx, d_c, n, batch, d_xs, d_q); });
 }
 
 template <class P>
@@ -415,9 +399,7 @@ static int inner_t(bzh_ctx* ctx, const uint32_t* a, const uint32_t* b, size_t n,
     return BZH_OK;
 }
 int poly_inner_product(bzh_ctx* ctx, int field, const uint32_t* a, const uint32_t* b, size_t n, size_t batch, uint32_t* out) {
-#define CALL(PP) inner_t<PP>(ctx, a, b, n, batch, out)
-    BZH_FIELD_SWITCH(field, CALL)
-#undef CALL
+    return with_field(field, [&](auto p) { return inner_t<decltype(p)>(ctx, a, b, n, batch, out); });
 }
 
 template <class P>
@@ -432,9 +414,7 @@ static int fold_t(bzh_ctx* ctx, const uint32_t* in, size_t half, size_t batch, c
 }
 int poly_fold(bzh_ctx* ctx, int field, const uint32_t* in, size_t half, size_t batch, const uint32_t* u, size_t u_stride,
               uint32_t* out) {
-#define CALL(PP) fold_t<PP>(ctx, in, half, batch, u, u_stride, out)
-    BZH_FIELD_SWITCH(field, CALL)
-#undef CALL
+    return with_field(field, [&](auto p) { return fold_t<decltype(p)>(ctx, in, half, batch, u, u_stride, out); });
 }
 
 template <class P>
@@ -447,9 +427,7 @@ static int vec_mul_t(bzh_ctx* ctx, uint32_t* a, const uint32_t* b, size_t count)
     return BZH_OK;
 }
 int poly_vec_mul(bzh_ctx* ctx, int field, uint32_t* a, const uint32_t* b, size_t count) {
-#define CALL(PP) vec_mul_t<PP>(ctx, a, b, count)
-    BZH_FIELD_SWITCH(field, CALL)
-#undef CALL
+    return with_field(field, [&](auto p) { return vec_mul_t<decltype(p)>(ctx, a, b, count); });
 }
 
 }  // namespace bzh

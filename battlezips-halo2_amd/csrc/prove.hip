@@ -41,6 +41,7 @@
 #include "ctx.hpp"
 #include "curve.cuh"
 #include "fe29.cuh"
+#include "host_field.hpp"
 
 // the table of quotient kernels generated at build time (quotient_builtin.hip); absent (null) in the generator's own link
 extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __attribute__((weak));
@@ -58,7 +59,7 @@ namespace {
 // degree (in units of n - 1: every column polynomial has degree < n) and tree multiplications of the quotient's terms
 template <class C>
 static int quotient_histogram_t(const uint8_t* circuit, size_t circuit_len, uint32_t* polys, uint32_t* muls) {
-    using SF = typename bzh::CurveScalar<C>::SF;
+    using SF = typename bzh::CurveInfo<C>::SF;
     bzh_pk pk;
     bzh::ParsedKey<SF> po;
     const int rc = bzh::pk_parse_t<C>(circuit, circuit_len, pk, po);
@@ -97,11 +98,8 @@ int bzh_pk_create(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* circuit, si
     if (!ctx || !srs || !circuit || !out || srs->device != ctx->device) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    switch (srs->curve) {
-        case BZH_CURVE_VESTA: return bzh::pk_create_t<bzh::VestaCurve>(ctx, srs, circuit, circuit_len, out);
-        case BZH_CURVE_PALLAS: return bzh::pk_create_t<bzh::PallasCurve>(ctx, srs, circuit, circuit_len, out);
-    }
-    return BZH_E_ARG;  // BN254 has no cube root of unity in Fr's multiplicative generator convention used here
+    // (not BN254: no cube root of unity in Fr's multiplicative generator convention used here)
+    return bzh::with_pasta_curve(srs->curve, [&](auto c) { return bzh::pk_create_t<decltype(c)>(ctx, srs, circuit, circuit_len, out); });
 }
 
 namespace {
@@ -184,15 +182,11 @@ int bzh_quotient_source_for_circuit(int curve, const uint8_t* circuit, size_t ci
                                     uint64_t* program_hash) {
     if (!circuit || !len) return BZH_E_ARG;
     bzh_pk pk;
-    int rc = BZH_E_ARG;
-    if (curve == BZH_CURVE_VESTA) {
-        bzh::ParsedKey<bzh::CurveScalar<bzh::VestaCurve>::SF> po;
-        rc = bzh::pk_parse_t<bzh::VestaCurve>(circuit, circuit_len, pk, po);
-    } else if (curve == BZH_CURVE_PALLAS) {
-        bzh::ParsedKey<bzh::CurveScalar<bzh::PallasCurve>::SF> po;
-        rc = bzh::pk_parse_t<bzh::PallasCurve>(circuit, circuit_len, pk, po);
-    }
-    if (rc) return rc;
+    BZH_TRY(bzh::with_pasta_curve(curve, [&](auto c) {
+        using C = decltype(c);
+        bzh::ParsedKey<typename bzh::CurveInfo<C>::SF> po;
+        return bzh::pk_parse_t<C>(circuit, circuit_len, pk, po);
+    }));
     if (!pk.q_ok) return BZH_E_RANGE;
     if (program_hash) *program_hash = pk.q_hash;
     // two flavours of the same program: saturated limbs (namespace bzh_q_<hash>) and unsaturated 9 x 29-bit limbs (bzh_q29_<hash>)
@@ -201,9 +195,7 @@ int bzh_quotient_source_for_circuit(int curve, const uint8_t* circuit, size_t ci
 
 int bzh_quotient_degree_histogram(int curve, const uint8_t* circuit, size_t circuit_len, uint32_t* polys, uint32_t* muls) {
     if (!circuit || !polys || !muls) return BZH_E_ARG;
-    if (curve == BZH_CURVE_VESTA) return quotient_histogram_t<bzh::VestaCurve>(circuit, circuit_len, polys, muls);
-    if (curve == BZH_CURVE_PALLAS) return quotient_histogram_t<bzh::PallasCurve>(circuit, circuit_len, polys, muls);
-    return BZH_E_ARG;
+    return bzh::with_pasta_curve(curve, [&](auto c) { return quotient_histogram_t<decltype(c)>(circuit, circuit_len, polys, muls); });
 }
 
 int bzh_pk_quotient_select(bzh_pk* pk, int flavour) {
@@ -311,10 +303,11 @@ int bzh_verify_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* ins
             BZH_HIP_TRY(ctx, hipMemcpyAsync(&m[i * 8], pk->srs->d_xy + idx[i] * 16, 64, hipMemcpyDeviceToHost, ctx->stream));
         BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         std::vector<uint64_t> canon(24);
-        for (int i = 0; i < 6; i++) {
-            if (pk->curve == BZH_CURVE_VESTA) bzh::h_store<bzh::VestaCurve::Base>(&canon[i * 4], bzh::fe_from_mont(bzh::h_load<bzh::VestaCurve::Base>(&m[i * 4])));
-            else bzh::h_store<bzh::PallasCurve::Base>(&canon[i * 4], bzh::fe_from_mont(bzh::h_load<bzh::PallasCurve::Base>(&m[i * 4])));
-        }
+        bzh::with_pasta_curve(pk->curve, [&](auto c) {
+            using PB = typename decltype(c)::Base;
+            for (int i = 0; i < 6; i++) bzh::fe_to_u64<PB>(&canon[i * 4], bzh::fe_from_u64<PB>(&m[i * 4]), BZH_FORM_CANONICAL);
+            return BZH_OK;
+        });
         pk->srs_g0_u_w = std::move(canon);
     }
     if (memcmp(pk->srs_g0_u_w.data(), g0_u_w, 3 * 64) != 0) {
@@ -322,15 +315,9 @@ int bzh_verify_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* ins
         return BZH_E_ARG;
     }
     lkp.unlock();
-    int rc = BZH_E_ARG;
-    switch (pk->curve) {
-        case BZH_CURVE_VESTA:
-            rc = bzh::verify_batch_t<bzh::VestaCurve>(ctx, pk, batch, instances, instance_rows, proofs, proof_stride, proof_lens, g0_u_w, results);
-            break;
-        case BZH_CURVE_PALLAS:
-            rc = bzh::verify_batch_t<bzh::PallasCurve>(ctx, pk, batch, instances, instance_rows, proofs, proof_stride, proof_lens, g0_u_w, results);
-            break;
-    }
+    const int rc = bzh::with_pasta_curve(pk->curve, [&](auto c) {
+        return bzh::verify_batch_t<decltype(c)>(ctx, pk, batch, instances, instance_rows, proofs, proof_stride, proof_lens, g0_u_w, results);
+    });
     (void)hipStreamSynchronize(ctx->stream);
     return rc;
 }
@@ -358,15 +345,9 @@ static int prove_batch_entry(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint6
         if (form == BZH_FORM_CANONICAL && (rc = bzh::field_convert(ctx, pk->field, (uint32_t*)staged, elems, 1))) return rc;
         d_adv = (const uint32_t*)staged;
     }
-    switch (pk->curve) {
-        case BZH_CURVE_VESTA:
-            return bzh::prove_batch_t<bzh::VestaCurve>(ctx, pk, batch, d_adv, instances, instance_rows, rng, rng_stride, proofs, proof_stride,
-                                                       proof_lens);
-        case BZH_CURVE_PALLAS:
-            return bzh::prove_batch_t<bzh::PallasCurve>(ctx, pk, batch, d_adv, instances, instance_rows, rng, rng_stride, proofs, proof_stride,
-                                                        proof_lens);
-    }
-    return BZH_E_ARG;
+    return bzh::with_pasta_curve(pk->curve, [&](auto c) {
+        return bzh::prove_batch_t<decltype(c)>(ctx, pk, batch, d_adv, instances, instance_rows, rng, rng_stride, proofs, proof_stride, proof_lens);
+    });
 }
 
 int bzh_prove_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice, int form, int mem, const uint64_t* instances,

@@ -1,5 +1,5 @@
 // Part of the whole-proof translation unit (csrc/prove.hip includes the parts in order; they share one anonymous namespace):
-// small device kernels of the prover and the host-side field helpers (portable Fe<P> arithmetic).
+// small device kernels of the prover (the host-side field helpers are csrc/host_field.hpp).
 #pragma once
 namespace bzh {
 
@@ -69,59 +69,3 @@ __global__ void __launch_bounds__(256) k_chacha20_rows(const uint32_t* __restric
     uint4* o = reinterpret_cast<uint4*>(raw + (b * count + i) * 16);
     for (int k = 0; k < 4; k++) o[k] = make_uint4(out[4 * k], out[4 * k + 1], out[4 * k + 2], out[4 * k + 3]);
 }
-
-// ---------------------------------------------------------------------------
-// host field helpers (portable Fe<P> arithmetic, Montgomery form unless noted)
-// ---------------------------------------------------------------------------
-template <class P>
-static Fe<P> h_load(const uint64_t* p) {
-    Fe<P> v;
-    for (int i = 0; i < 4; i++) {
-        v.l[2 * i] = (uint32_t)p[i];
-        v.l[2 * i + 1] = (uint32_t)(p[i] >> 32);
-    }
-    return v;
-}
-template <class P>
-static void h_store(uint64_t* p, const Fe<P>& v) {
-    for (int i = 0; i < 4; i++) p[i] = (uint64_t)v.l[2 * i] | ((uint64_t)v.l[2 * i + 1] << 32);
-}
-template <class P>
-static Fe<P> h_from_bytes(const uint8_t* b) {  // canonical little-endian -> Montgomery
-    uint64_t l[4];
-    memcpy(l, b, 32);
-    return fe_to_mont(h_load<P>(l));
-}
-template <class P>
-static Fe<P> h_pow_u64(Fe<P> base, uint64_t e) {
-    Fe<P> acc = fe_one<P>();
-    for (; e; e >>= 1) {
-        if (e & 1) acc = fe_mul(acc, base);
-        base = fe_sqr(base);
-    }
-    return acc;
-}
-// Field::random: 64 bytes little-endian mod p (Montgomery out)
-template <class P>
-static Fe<P> h_from_u512(const uint8_t* b) {
-    uint64_t lo[4], hi[4];
-    memcpy(lo, b, 32);
-    memcpy(hi, b + 32, 32);
-    const Fe<P> r2 = fe_r2<P>();
-    return fe_add(fe_mul(h_load<P>(lo), r2), fe_mul(fe_mul(h_load<P>(hi), r2), r2));
-}
-
-template <class P>
-struct FieldMeta;
-template <>
-struct FieldMeta<FpParams> {
-    static constexpr unsigned S = 32;
-    static constexpr uint32_t gen = 5;
-    static constexpr int id = BZH_FIELD_FP;
-};
-template <>
-struct FieldMeta<FqParams> {
-    static constexpr unsigned S = 32;
-    static constexpr uint32_t gen = 5;
-    static constexpr int id = BZH_FIELD_FQ;
-};

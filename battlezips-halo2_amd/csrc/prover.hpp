@@ -5,7 +5,7 @@
 // ---------------------------------------------------------------------------
 template <class C>
 struct Prover {
-    using SF = typename CurveScalar<C>::SF;
+    using SF = typename CurveInfo<C>::SF;
     using PB = typename C::Base;
     bzh_ctx* ctx;
     bzh_pk& pk;
@@ -80,14 +80,14 @@ struct Prover {
         char* dev = (char*)arena.alloc(total);
         if (!dev) return BZH_E_OOM;
         char* slot = nullptr;
-        PV_TRY(h2d_stage(ctx, total, &slot));
+        BZH_TRY(h2d_stage(ctx, total, &slot));
         memcpy(slot, cv, cv_bytes);
         memcpy(slot + o_prog, ops, op_bytes);
         if (ncols) {
             memcpy(slot + o_ptrs, ptrs, ncols * 8);
             memcpy(slot + o_strides, strides, ncols * 8);
         }
-        PV_TRY(h2d_commit(ctx, dev, slot, total));
+        BZH_TRY(h2d_commit(ctx, dev, slot, total));
         out.consts = (uint32_t*)dev;
         out.prog = dev + o_prog;
         out.ptrs = dev + o_ptrs;
@@ -115,7 +115,7 @@ struct Prover {
     }
     // seeded mode: the next `count` 64-byte draws of every proof, generated on the device (B x count x 16 words)
     int seed_rows(size_t count, uint32_t* raw) {
-        PV_TRY(seed_sync());
+        BZH_TRY(seed_sync());
         hipLaunchKernelGGL(k_chacha20_rows, dim3((unsigned)((count + 255) / 256), (unsigned)B), dim3(256), 0, st, d_seed_keys, seed_ctr, count, raw);
         BZH_HIP_TRY(ctx, hipGetLastError());
         seed_ctr += count;
@@ -127,26 +127,26 @@ struct Prover {
         uint32_t* raw = (uint32_t*)arena.alloc(B * count * 64);
         if (!raw) return BZH_E_OOM;
         if (seeded) {
-            PV_TRY(seed_rows(count, raw));
+            BZH_TRY(seed_rows(count, raw));
             return random_field(ctx, field, raw, B * count, dst);
         }
         char* stage = nullptr;  // one upload for the whole batch, assembled in pinned memory
-        PV_TRY(h2d_stage(ctx, B * count * 64, &stage));
+        BZH_TRY(h2d_stage(ctx, B * count * 64, &stage));
         for (size_t b = 0; b < B; b++) {
             memcpy(stage + b * count * 64, rng[b], count * 64);
             rng[b] += count * 64;
         }
-        PV_TRY(h2d_commit(ctx, raw, stage, B * count * 64));
+        BZH_TRY(h2d_commit(ctx, raw, stage, B * count * 64));
         return random_field(ctx, field, raw, B * count, dst);
     }
     Fe<SF> squeeze(size_t b) {
         uint64_t ch[4];
         bzh_transcript_squeeze_challenge(T[b], ch);
-        return fe_to_mont(h_load<SF>(ch));
+        return fe_to_mont(fe_from_u64<SF>(ch));
     }
     void write_scalar(size_t b, const Fe<SF>& v) {
         uint64_t s[4];
-        h_store<SF>(s, fe_from_mont(v));
+        fe_to_u64<SF>(s, fe_from_mont(v));
         bzh_transcript_write_scalar(T[b], s);
     }
 
@@ -181,37 +181,21 @@ struct Prover {
         uint32_t* bl = dalloc(count);
         uint32_t* d_out = dalloc(count * 3);
         if (!sc || !bl || !d_out) return BZH_E_OOM;
-        PV_TRY(upload(bl, blinds.data(), count));
+        BZH_TRY(upload(bl, blinds.data(), count));
         if (shift) {
             hipLaunchKernelGGL((k_commit_shift<SF>), dim3((unsigned)((n + 3 + 255) / 256), (unsigned)count), dim3(256), 0, st, polys, pitch, n,
                                (size_t)shift_row, bl, sc);
             BZH_HIP_TRY(ctx, hipGetLastError());
         } else {
-            PV_TRY(zero(sc, count * cols));
-            PV_TRY(copy2d(sc, cols, polys, pitch, n, count));
-            PV_TRY(copy2d(sc + (n + 1) * 8, cols, bl, 1, 1, count));
+            BZH_TRY(zero(sc, count * cols));
+            BZH_TRY(copy2d(sc, cols, polys, pitch, n, count));
+            BZH_TRY(copy2d(sc + (n + 1) * 8, cols, bl, 1, 1, count));
         }
-        PV_TRY(msm_run(ctx, lagrange ? pk.srs_lagrange : pk.srs, sc, cols, count, BZH_FORM_MONTGOMERY, d_out));
+        BZH_TRY(msm_run(ctx, lagrange ? pk.srs_lagrange : pk.srs, sc, cols, count, BZH_FORM_MONTGOMERY, d_out));
         std::vector<uint64_t> jac(count * 12);
-        PV_TRY(d2h_async(ctx, jac.data(), d_out, count * 96));
-        PV_TRY(d2h_finish(ctx));
-        // Jacobian (Montgomery) -> affine canonical, one inversion
-        std::vector<Fe<PB>> pre(count + 1);
-        pre[0] = fe_one<PB>();
-        for (size_t i = 0; i < count; i++) {
-            const Fe<PB> Z = h_load<PB>(&jac[i * 12 + 8]);
-            pre[i + 1] = fe_is_zero(Z) ? pre[i] : fe_mul(pre[i], Z);
-        }
-        Fe<PB> inv = fe_inv(pre[count]);
-        for (size_t i = count; i-- > 0;) {
-            const Fe<PB> Z = h_load<PB>(&jac[i * 12 + 8]);
-            if (fe_is_zero(Z)) continue;
-            const Fe<PB> zi = fe_mul(inv, pre[i]);
-            inv = fe_mul(inv, Z);
-            const Fe<PB> zi2 = fe_sqr(zi), zi3 = fe_mul(zi2, zi);
-            h_store<PB>(&xy[i * 8], fe_from_mont(fe_mul(h_load<PB>(&jac[i * 12]), zi2)));
-            h_store<PB>(&xy[i * 8 + 4], fe_from_mont(fe_mul(h_load<PB>(&jac[i * 12 + 4]), zi3)));
-        }
+        BZH_TRY(d2h_async(ctx, jac.data(), d_out, count * 96));
+        BZH_TRY(d2h_finish(ctx));
+        h_jac_to_affine<PB>(jac.data(), count, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, xy.data());
         return BZH_OK;
     }
     // evaluate `count` polynomials (contiguous, n coefficients each) at one point each
@@ -222,10 +206,10 @@ struct Prover {
         uint32_t* xs = dalloc(count);
         uint32_t* res = dalloc(count);
         if (!xs || !res) return BZH_E_OOM;
-        PV_TRY(upload(xs, points.data(), count));
-        PV_TRY(poly_eval(ctx, field, stacked, n, count, xs, 1, res));
-        PV_TRY(d2h_async(ctx, out.data(), res, count * 32));
-        PV_TRY(d2h_finish(ctx));
+        BZH_TRY(upload(xs, points.data(), count));
+        BZH_TRY(poly_eval(ctx, field, stacked, n, count, xs, 1, res));
+        BZH_TRY(d2h_async(ctx, out.data(), res, count * 32));
+        BZH_TRY(d2h_finish(ctx));
         return BZH_OK;
     }
 
@@ -264,7 +248,7 @@ struct Prover {
                 }
             }
         ProgramArgs pa;
-        PV_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), pg.ops.size() * sizeof(bzh_expr_op), reg.ptr.data(), reg.stride.data(), ncols, pa));
+        BZH_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), pg.ops.size() * sizeof(bzh_expr_op), reg.ptr.data(), reg.stride.data(), ncols, pa));
         uint32_t* d_consts = pa.consts;
         char *d_prog = pa.prog, *d_ptrs = pa.ptrs, *d_strides = pa.strides;
         int nslots = pg.result_slot + 1;
@@ -322,7 +306,7 @@ struct Prover {
                 memcpy(&cv[(b * nc + i) * 12], w.l, 36);
             }
         ProgramArgs pa;
-        PV_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), 0, ptrs.data(), strides.data(), ptrs.size(), pa));
+        BZH_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), 0, ptrs.data(), strides.data(), ptrs.size(), pa));
         if (ctx->profiling) {
             double cols_read = 0;
             for (size_t i = 0; i < strides.size() - pk.hoist_cols; i++) cols_read += strides[i] ? (double)B : 1.0;
@@ -366,7 +350,7 @@ struct Prover {
                 }
             }
         ProgramArgs pa;
-        PV_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), pg.ops.size() * sizeof(ExprOp2), ptrs.data(), strides.data(), ncols, pa));
+        BZH_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), pg.ops.size() * sizeof(ExprOp2), ptrs.data(), strides.data(), ncols, pa));
         uint32_t* d_consts = pa.consts;
         char *d_prog = pa.prog, *d_ptrs = pa.ptrs, *d_strides = pa.strides;
         if (ctx->profiling) {   // the quotient pass reads every extended column once and writes h: per-proof columns
@@ -408,7 +392,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
     std::vector<uint64_t> xy;
     std::vector<Fe<SF>> blinds;
     for (size_t b = 0; b < B; b++) {
-        PV_TRY(bzh_transcript_new(field, &T[b]));
+        BZH_TRY(bzh_transcript_new(field, &T[b]));
         bzh_transcript_common_scalar(T[b], pk.vk_repr);
     }
 
@@ -418,19 +402,19 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
     uint32_t* inst_polys = dalloc(B * std::max(ni, 1) * n);
     if (!inst || !inst_polys) return BZH_E_OOM;
     if (ni) {
-        PV_TRY(zero(inst, B * ni * n));
+        BZH_TRY(zero(inst, B * ni * n));
         if (inst_rows) {
             std::vector<Fe<SF>> hv(B * ni * inst_rows);
-            for (size_t i = 0; i < hv.size(); i++) hv[i] = fe_to_mont(h_load<SF>(instances + 4 * i));
+            for (size_t i = 0; i < hv.size(); i++) hv[i] = fe_to_mont(fe_from_u64<SF>(instances + 4 * i));
             uint32_t* tmp = dalloc(hv.size());
             if (!tmp) return BZH_E_OOM;
-            PV_TRY(upload(tmp, hv.data(), hv.size()));
-            PV_TRY(copy2d(inst, n, tmp, inst_rows, inst_rows, B * ni));
+            BZH_TRY(upload(tmp, hv.data(), hv.size()));
+            BZH_TRY(copy2d(inst, n, tmp, inst_rows, inst_rows, B * ni));
         }
-        PV_TRY(to_coeff(inst_polys, inst, B * ni));
+        BZH_TRY(to_coeff(inst_polys, inst, B * ni));
         blinds.assign(B * ni, fe_one<SF>());
-        if (pk.srs_lagrange) PV_TRY(commit(inst, n, B * ni, blinds, xy, true));
-        else PV_TRY(commit(inst_polys, n, B * ni, blinds, xy));
+        if (pk.srs_lagrange) BZH_TRY(commit(inst, n, B * ni, blinds, xy, true));
+        else BZH_TRY(commit(inst_polys, n, B * ni, blinds, xy));
         for (size_t b = 0; b < B; b++)
             for (int i = 0; i < ni; i++) bzh_transcript_common_point(T[b], &xy[(b * ni + i) * 8]);
     }
@@ -444,15 +428,15 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
     {
         uint32_t* rows = dalloc(B * na * bf1);
         if (!rows) return BZH_E_OOM;
-        PV_TRY(draw_rows(na * bf1, rows));
-        PV_TRY(copy2d(adv + usable * 8, n, rows, bf1, bf1, B * na));
+        BZH_TRY(draw_rows(na * bf1, rows));
+        BZH_TRY(copy2d(adv + usable * 8, n, rows, bf1, bf1, B * na));
     }
     std::vector<Fe<SF>> adv_blinds(B * na);
     for (size_t b = 0; b < B; b++)
         for (int i = 0; i < na; i++) adv_blinds[b * na + i] = draw(b);
-    PV_TRY(to_coeff(adv_polys, adv, B * na));
-    if (pk.srs_lagrange) PV_TRY(commit(adv, n, B * na, adv_blinds, xy, true));
-    else PV_TRY(commit(adv_polys, n, B * na, adv_blinds, xy));
+    BZH_TRY(to_coeff(adv_polys, adv, B * na));
+    if (pk.srs_lagrange) BZH_TRY(commit(adv, n, B * na, adv_blinds, xy, true));
+    else BZH_TRY(commit(adv_polys, n, B * na, adv_blinds, xy));
     for (size_t b = 0; b < B; b++) {
         for (int i = 0; i < na; i++) bzh_transcript_write_point(T[b], C::id, &xy[(b * na + i) * 8]);
         env[b][SY_THETA] = squeeze(b);
@@ -463,7 +447,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         inst_cosets = ext_alloc(B * std::max(ni, 1));
         adv_cosets = ext_alloc(B * na);
         if (!inst_cosets || !adv_cosets) return BZH_E_OOM;
-        PV_TRY(to_extended(inst_cosets, inst_polys, B * ni));
+        BZH_TRY(to_extended(inst_cosets, inst_polys, B * ni));
         return to_extended(adv_cosets, adv_polys, B * na);
     };
     auto lag_registry = [&](Cols& reg) {
@@ -490,7 +474,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         lag_registry(reg);
         for (int side = 0; side < 2; side++) {
             const std::vector<int>& es = side ? pk.lookups[li].second : pk.lookups[li].first;
-            PV_TRY(run(key(20 + side, li), [&](EPool& ep) {
+            BZH_TRY(run(key(20 + side, li), [&](EPool& ep) {
                 std::vector<int> terms;
                 for (int e : es) terms.push_back(lower(pk, e, ep, reg, 1));
                 return ep.horner(terms, ep.sym(SY_THETA));
@@ -499,23 +483,23 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         // compressed columns come back through pinned memory; the permuted pair is assembled in a pinned slot in the
         // device layout (B, 2, n) (rows past `usable` zero until the blinding rows land) and goes up in one piece
         char *ah_c = nullptr, *sh_c = nullptr, *as_c = nullptr;
-        PV_TRY(pin_big_reserve(ctx, 4 * B * n * 32 + ((size_t)3 << 20)));
-        PV_TRY(pin_big_take(ctx, B * n * 32, &ah_c));
-        PV_TRY(pin_big_take(ctx, B * n * 32, &sh_c));
-        PV_TRY(pin_big_take(ctx, B * 2 * n * 32, &as_c));
+        BZH_TRY(pin_big_reserve(ctx, 4 * B * n * 32 + ((size_t)3 << 20)));
+        BZH_TRY(pin_big_take(ctx, B * n * 32, &ah_c));
+        BZH_TRY(pin_big_take(ctx, B * n * 32, &sh_c));
+        BZH_TRY(pin_big_take(ctx, B * 2 * n * 32, &as_c));
         // the host sorts canonical integers: convert on the device (copies; the Montgomery originals feed the grand product)
         uint32_t* canon = dalloc(2 * B * n);
         if (!canon) return BZH_E_OOM;
         BZH_HIP_TRY(ctx, hipMemcpyAsync(canon, d.a_c, B * n * 32, hipMemcpyDeviceToDevice, st));
         BZH_HIP_TRY(ctx, hipMemcpyAsync(canon + B * n * 8, d.s_c, B * n * 32, hipMemcpyDeviceToDevice, st));
-        PV_TRY(field_convert(ctx, field, canon, 2 * B * n, 0));
-        PV_TRY(xfer_launch(ctx, ah_c, canon, B * n * 32, hipMemcpyDeviceToHost));
-        PV_TRY(xfer_launch(ctx, sh_c, canon + B * n * 8, B * n * 32, hipMemcpyDeviceToHost));
+        BZH_TRY(field_convert(ctx, field, canon, 2 * B * n, 0));
+        BZH_TRY(xfer_launch(ctx, ah_c, canon, B * n * 32, hipMemcpyDeviceToHost));
+        BZH_TRY(xfer_launch(ctx, sh_c, canon + B * n * 8, B * n * 32, hipMemcpyDeviceToHost));
         BZH_HIP_TRY(ctx, hipStreamSynchronize(st));
         const uint64_t* ah = (const uint64_t*)ah_c;
         const uint64_t* sh = (const uint64_t*)sh_c;
         mark(" lk:compress+d2h");
-        PV_TRY(extend_witness());
+        BZH_TRY(extend_witness());
         mark(" lk:extend_witness");
         uint64_t* as = (uint64_t*)as_c;
         for (size_t v = 0; v < 2 * B; v++) memset(as + (v * n + usable) * 4, 0, (n - usable) * 32);
@@ -536,29 +520,29 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
                 if (rc) return rc;
         }
         mark(" lk:sort");
-        PV_TRY(h2d_commit(ctx, d.as, as_c, B * 2 * n * 32));
-        PV_TRY(field_convert(ctx, field, d.as, B * 2 * n, 1));  // back to Montgomery form (the zero rows stay zero)
+        BZH_TRY(h2d_commit(ctx, d.as, as_c, B * 2 * n * 32));
+        BZH_TRY(field_convert(ctx, field, d.as, B * 2 * n, 1));  // back to Montgomery form (the zero rows stay zero)
         mark(" lk:h2d");
         {
             uint32_t* rows = dalloc(B * 2 * bf1);
             if (!rows) return BZH_E_OOM;
-            PV_TRY(draw_rows(2 * bf1, rows));
-            PV_TRY(copy2d(d.as + usable * 8, n, rows, bf1, bf1, B * 2));
+            BZH_TRY(draw_rows(2 * bf1, rows));
+            BZH_TRY(copy2d(d.as + usable * 8, n, rows, bf1, bf1, B * 2));
         }
         d.blinds.resize(B * 2);
         for (size_t b = 0; b < B; b++) {
             d.blinds[2 * b] = draw(b);
             d.blinds[2 * b + 1] = draw(b);
         }
-        PV_TRY(to_coeff(d.polys, d.as, B * 2));
-        if (pk.srs_lagrange) PV_TRY(commit(d.as, n, B * 2, d.blinds, xy, true));
-        else PV_TRY(commit(d.polys, n, B * 2, d.blinds, xy));
+        BZH_TRY(to_coeff(d.polys, d.as, B * 2));
+        if (pk.srs_lagrange) BZH_TRY(commit(d.as, n, B * 2, d.blinds, xy, true));
+        else BZH_TRY(commit(d.polys, n, B * 2, d.blinds, xy));
         for (size_t b = 0; b < B; b++) {
             bzh_transcript_write_point(T[b], C::id, &xy[(2 * b) * 8]);
             bzh_transcript_write_point(T[b], C::id, &xy[(2 * b + 1) * 8]);
         }
     }
-    PV_TRY(extend_witness());
+    BZH_TRY(extend_witness());
     for (size_t b = 0; b < B; b++) {
         env[b][SY_BETA] = squeeze(b);
         env[b][SY_GAMMA] = squeeze(b);
@@ -584,10 +568,10 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
     std::vector<Fe<SF>> z_blinds(B * std::max(nz, 1));
     auto invert_and_scan_all = [&]() -> int {
         mark("  fp:exprs");
-        PV_TRY(poly_batch_invert(ctx, field, den_all, (size_t)nz * B * n));
+        BZH_TRY(poly_batch_invert(ctx, field, den_all, (size_t)nz * B * n));
         mark("  fp:invert");
-        PV_TRY(poly_vec_mul(ctx, field, zt_all, den_all, (size_t)nz * B * n));
-        PV_TRY(poly_prefix_product(ctx, field, zt_all, n, (size_t)nz * B));
+        BZH_TRY(poly_vec_mul(ctx, field, zt_all, den_all, (size_t)nz * B * n));
+        BZH_TRY(poly_prefix_product(ctx, field, zt_all, n, (size_t)nz * B));
         mark("  fp:mul+scan");
         return BZH_OK;
     };
@@ -598,8 +582,8 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
                                zs + ((size_t)prev_slot * n + usable) * 8, (size_t)nz * n);
         uint32_t* rows = dalloc(B * bf);
         if (!rows) return BZH_E_OOM;
-        PV_TRY(draw_rows(bf, rows));
-        PV_TRY(copy2d(zt + (n - bf) * 8, n, rows, bf, bf, B));
+        BZH_TRY(draw_rows(bf, rows));
+        BZH_TRY(copy2d(zt + (n - bf) * 8, n, rows, bf, bf, B));
         for (size_t b = 0; b < B; b++) z_blinds[b * nz + slot] = draw(b);
         return copy2d(zs + (size_t)slot * n * 8, (size_t)nz * n, zt, n, n, B);
     };
@@ -618,7 +602,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
             reg.add(key(K_IDENT, gj), pk.ident + gj * n * 8, 0);
         }
         for (int which = 0; which < 2; which++) {  // 0: denominator, 1: numerator
-            PV_TRY(run(key(30 + which, i), [&](EPool& ep) {
+            BZH_TRY(run(key(30 + which, i), [&](EPool& ep) {
                 int acc = -1;
                 for (size_t gj = c0; gj < c1; gj++) {
                     const int v = ep.query(lag_col(reg, pk.perm_columns[gj]));
@@ -638,42 +622,42 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         reg.add(key(K_MISC, M_SC), lk[li].s_c, n);
         reg.add(key(K_MISC, M_A), lk[li].as, 2 * n);
         reg.add(key(K_MISC, M_S), lk[li].as + n * 8, 2 * n);
-        PV_TRY(run(key(32, li), [&](EPool& ep) {
+        BZH_TRY(run(key(32, li), [&](EPool& ep) {
             return ep.mul(ep.add(ep.query(0), ep.sym(SY_BETA)), ep.add(ep.query(1), ep.sym(SY_GAMMA)));
         }, reg, n, zt));
-        PV_TRY(run(key(33, li), [&](EPool& ep) {
+        BZH_TRY(run(key(33, li), [&](EPool& ep) {
             return ep.mul(ep.add(ep.query(2), ep.sym(SY_BETA)), ep.add(ep.query(3), ep.sym(SY_GAMMA)));
         }, reg, n, den));
         mark(" gp:lookup_product");
     }
     if (nz) {
-        PV_TRY(invert_and_scan_all());
+        BZH_TRY(invert_and_scan_all());
         // blinding rows and blinds in the order the products are made upstream: permutation sets, then lookups
-        for (int i = 0; i < nsets; i++) PV_TRY(finish_product(i, i ? i - 1 : -1));
-        for (int li = 0; li < nl; li++) PV_TRY(finish_product(nsets + li, -1));
-        PV_TRY(to_coeff(z_polys, zs, B * nz));
-        if (pk.srs_lagrange) PV_TRY(commit(zs, n, B * nz, z_blinds, xy, true, (long)usable - 1));
-        else PV_TRY(commit(z_polys, n, B * nz, z_blinds, xy));
+        for (int i = 0; i < nsets; i++) BZH_TRY(finish_product(i, i ? i - 1 : -1));
+        for (int li = 0; li < nl; li++) BZH_TRY(finish_product(nsets + li, -1));
+        BZH_TRY(to_coeff(z_polys, zs, B * nz));
+        if (pk.srs_lagrange) BZH_TRY(commit(zs, n, B * nz, z_blinds, xy, true, (long)usable - 1));
+        else BZH_TRY(commit(z_polys, n, B * nz, z_blinds, xy));
         for (size_t b = 0; b < B; b++)
             for (int i = 0; i < nz; i++) bzh_transcript_write_point(T[b], C::id, &xy[(b * nz + i) * 8]);
         mark(" gp:commit");
-        PV_TRY(to_extended(z_cosets, z_polys, B * nz));
+        BZH_TRY(to_extended(z_cosets, z_polys, B * nz));
         mark(" gp:extend_z");
     }
     for (auto& d : lk) {
         d.cosets = ext_alloc(B * 2);
         if (!d.cosets) return BZH_E_OOM;
-        PV_TRY(to_extended(d.cosets, d.polys, B * 2));
+        BZH_TRY(to_extended(d.cosets, d.polys, B * 2));
     }
 
     mark("grand_products");
     // ---- vanishing argument ----------------------------------------------------------------------
     uint32_t* random_poly = dalloc(B * n);
     if (!random_poly) return BZH_E_OOM;
-    PV_TRY(draw_rows(n, random_poly));
+    BZH_TRY(draw_rows(n, random_poly));
     std::vector<Fe<SF>> random_blinds(B);
     for (size_t b = 0; b < B; b++) random_blinds[b] = draw(b);
-    PV_TRY(commit(random_poly, n, B, random_blinds, xy));
+    BZH_TRY(commit(random_poly, n, B, random_blinds, xy));
     const Fe<SF> delta = [&] {
         Fe<SF> d;
         memcpy(d.l, pk.delta, 32);
@@ -714,9 +698,9 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
                 return ep.mul(ep.horner(terms, ep.sym(SY_Y)), tinv);
             }, reg, en, h);
         }
-        PV_TRY(qrc);
+        BZH_TRY(qrc);
     }
-    PV_TRY(ntt_run(ctx, field, h, pk.ek, B, pk.eomega, pk.zeta, 1, BZH_FORM_MONTGOMERY));
+    BZH_TRY(ntt_run(ctx, field, h, pk.ek, B, pk.eomega, pk.zeta, 1, BZH_FORM_MONTGOMERY));
     uint32_t* d_flag = (uint32_t*)arena.alloc(256);
     if (!d_flag) return BZH_E_OOM;
     uint32_t h_flag = 0;
@@ -725,7 +709,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         const size_t words = (en - (size_t)npieces * n) * 8;
         hipLaunchKernelGGL(k_any_nonzero, dim3((unsigned)((words + 255) / 256), (unsigned)B), dim3(256), 0, st,
                            h + (size_t)npieces * n * 8, words, en * 8, d_flag);
-        PV_TRY(d2h_async(ctx, &h_flag, d_flag, 4));  // lands at the commit's d2h_finish
+        BZH_TRY(d2h_async(ctx, &h_flag, d_flag, 4));  // lands at the commit's d2h_finish
     }
     std::vector<Fe<SF>> h_blinds(B * npieces);
     for (size_t b = 0; b < B; b++)
@@ -734,8 +718,8 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         // pieces of proof b: h[b][i*n .. (i+1)*n) -> (B * npieces) rows; piece rows are n apart inside a proof, proofs en apart
         uint32_t* pieces = dalloc(B * npieces * n);
         if (!pieces) return BZH_E_OOM;
-        PV_TRY(copy2d(pieces, (size_t)npieces * n, h, en, (size_t)npieces * n, B));
-        PV_TRY(commit(pieces, n, B * npieces, h_blinds, xy));
+        BZH_TRY(copy2d(pieces, (size_t)npieces * n, h, en, (size_t)npieces * n, B));
+        BZH_TRY(commit(pieces, n, B * npieces, h_blinds, xy));
     }
     if (h_flag) {
         ctx->last_error = "quotient has higher degree than expected: a witness does not satisfy the constraints";
@@ -746,7 +730,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
     {
         uint64_t t[4];
         memcpy(t, pk.omega, 32);
-        omega_m = h_load<SF>(t);
+        omega_m = fe_from_u64<SF>(t);
     }
     const Fe<SF> omega_inv = fe_inv(omega_m);
     for (size_t b = 0; b < B; b++) {
@@ -787,8 +771,8 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         char* stage = (char*)arena.alloc(J * 16 + 512);
         if (!stage) return BZH_E_OOM;
         char* d_ss = stage + ((J * 8 + 255) & ~(size_t)255);
-        PV_TRY(h2d_small(ctx, stage, ps.data(), J * 8));
-        PV_TRY(h2d_small(ctx, d_ss, ss.data(), J * 8));
+        BZH_TRY(h2d_small(ctx, stage, ps.data(), J * 8));
+        BZH_TRY(h2d_small(ctx, d_ss, ss.data(), J * 8));
         hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((2 * n + 255) / 256), (unsigned)J, (unsigned)B), dim3(256), 0, st, (uint4*)dst,
                            (const uint4* const*)stage, (const size_t*)d_ss, n, J);
         BZH_HIP_TRY(ctx, hipGetLastError());
@@ -819,11 +803,11 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         ArenaScope scope(arena);   // `gathered` is read by evals() (which ends in a stream sync) and by nothing else
         uint32_t* gathered = dalloc(B * J * n);
         if (!gathered) return BZH_E_OOM;
-        PV_TRY(gather(srcs, gathered));
+        BZH_TRY(gather(srcs, gathered));
         std::vector<Fe<SF>> pts(B * J), vals;
         for (size_t b = 0; b < B; b++)
             for (size_t j = 0; j < J; j++) pts[b * J + j] = rot(b, jobs[j].second);
-        PV_TRY(evals(gathered, B * J, pts, vals));
+        BZH_TRY(evals(gathered, B * J, pts, vals));
         for (size_t b = 0; b < B; b++)
             for (size_t j = 0; j < J; j++) write_scalar(b, vals[b * J + j]);
     }
@@ -835,7 +819,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
     {
         Cols reg;
         for (int i = 0; i < npieces; i++) reg.add(key(K_MISC, M_H0 + i), h + (size_t)i * n * 8, en);
-        PV_TRY(run(key(41, 0), [&](EPool& ep) {
+        BZH_TRY(run(key(41, 0), [&](EPool& ep) {
             std::vector<int> t;
             for (int i = npieces - 1; i >= 0; i--) t.push_back(ep.query(i));
             return ep.horner(t, ep.sym(SY_XN));
@@ -892,14 +876,14 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
                 reg.add(cids[c], w.first, w.second);
             }
             uint32_t* outp = prev == acc_a ? acc_b : acc_a;
-            PV_TRY(run(key(50 + si, s0), [&](EPool& ep) {
+            BZH_TRY(run(key(50 + si, s0), [&](EPool& ep) {
                 std::vector<int> t;
                 for (size_t c = 0; c < reg.ptr.size(); c++) t.push_back(ep.query((int)c));
                 return ep.horner(t, ep.sym(SY_X1));
             }, reg, n, outp));
             prev = outp;
         }
-        PV_TRY(copy2d(q_polys + si * n * 8, nq * n, prev, n, n, B));
+        BZH_TRY(copy2d(q_polys + si * n * 8, nq * n, prev, n, n, B));
     }
     // evaluations of the q polynomials at their own points, remainders r(X), quotients by prod (X - point)
     {
@@ -916,8 +900,8 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
             ArenaScope scope(arena);   // `gathered` lives until evals() returns (stream sync)
             uint32_t* gathered = dalloc(B * J2 * n);
             if (!gathered) return BZH_E_OOM;
-            PV_TRY(gather(srcs, gathered));
-            PV_TRY(evals(gathered, B * J2, pts, ev));
+            BZH_TRY(gather(srcs, gathered));
+            BZH_TRY(evals(gathered, B * J2, pts, ev));
         }
         size_t maxpts = 1;
         for (auto& rs : pk.rot_sets) maxpts = std::max(maxpts, rs.size());
@@ -938,20 +922,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
                 o2 += np;
             }
         }
-        {
-            std::vector<Fe<SF>> pre(dinv.size() + 1);
-            pre[0] = fe_one<SF>();
-            for (size_t i = 0; i < dinv.size(); i++) {
-                if (fe_is_zero(dinv[i])) return BZH_E_ARG;   // two opening points of one set coincide: not a valid domain
-                pre[i + 1] = fe_mul(pre[i], dinv[i]);
-            }
-            Fe<SF> inv = fe_inv(pre[dinv.size()]);
-            for (size_t i = dinv.size(); i-- > 0;) {
-                const Fe<SF> d = dinv[i];
-                dinv[i] = fe_mul(inv, pre[i]);
-                inv = fe_mul(inv, d);
-            }
-        }
+        if (!h_batch_invert(dinv.data(), dinv.size())) return BZH_E_ARG;   // two opening points of one set coincide: not a valid domain
         for (size_t b = 0; b < B; b++) {
             size_t o2 = 0;
             for (size_t si = 0; si < nq; si++) {
@@ -981,10 +952,10 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         uint32_t* k_a = dalloc(B * nq * n);
         uint32_t* k_b = dalloc(B * nq * n);
         if (!rcols || !rs_dev || !f_parts || !k_a || !k_b) return BZH_E_OOM;
-        PV_TRY(zero(rcols, B * nq * n));
-        PV_TRY(zero(f_parts, B * nq * n));
-        PV_TRY(upload(rs_dev, r_small.data(), r_small.size()));
-        PV_TRY(copy2d(rcols, n, rs_dev, maxpts, maxpts, B * nq));
+        BZH_TRY(zero(rcols, B * nq * n));
+        BZH_TRY(zero(f_parts, B * nq * n));
+        BZH_TRY(upload(rs_dev, r_small.data(), r_small.size()));
+        BZH_TRY(copy2d(rcols, n, rs_dev, maxpts, maxpts, B * nq));
         // (q_si - r_si) / prod_(r in set si) (X - x w^r): one division per point, chained within a set, independent between sets.
         // The sets are ordered by the number of their points (most first) and step t divides every set that still has a t-th
         // point in ONE launch: all of them hold n - t coefficients at that step and they are a prefix of the order, so the
@@ -1003,14 +974,14 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
             for (size_t t = 0; t < steps; t++)
                 for (size_t pos = 0; pos < nq && pk.rot_sets[order[pos]].size() > t; pos++)
                     for (size_t b = 0; b < B; b++) xv[at++] = rot(b, pk.rot_sets[order[pos]][t]);
-            PV_TRY(upload(d_xall, xv.data(), xv.size()));
+            BZH_TRY(upload(d_xall, xv.data(), xv.size()));
         }
         for (size_t pos = 0; pos < nq; pos++) {
             const size_t si = order[pos];
             Cols reg;
             reg.add(key(K_MISC, M_Q), q_polys + si * n * 8, nq * n);
             reg.add(key(K_MISC, M_R), rcols + si * n * 8, nq * n);
-            PV_TRY(run(key(42, 0), [&](EPool& ep) { return ep.sub(ep.query(0), ep.query(1)); }, reg, n, k_a + pos * B * n * 8));
+            BZH_TRY(run(key(42, 0), [&](EPool& ep) { return ep.sub(ep.query(0), ep.query(1)); }, reg, n, k_a + pos * B * n * 8));
         }
         {
             uint32_t* cur = k_a;
@@ -1019,16 +990,16 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
             for (size_t t = 0; t < steps; t++) {
                 size_t active = 0;
                 while (active < nq && pk.rot_sets[order[active]].size() > t) active++;
-                PV_TRY(poly_kate_division(ctx, field, cur, len, active * B, d_xall + x_at * 8, nxt));
+                BZH_TRY(poly_kate_division(ctx, field, cur, len, active * B, d_xall + x_at * 8, nxt));
                 x_at += active * B;
                 std::swap(cur, nxt);
                 len--;
                 for (size_t pos = 0; pos < active; pos++)   // the sets whose last point this was
                     if (pk.rot_sets[order[pos]].size() == t + 1)
-                        PV_TRY(copy2d(f_parts + order[pos] * n * 8, nq * n, cur + pos * B * len * 8, len, len, B));
+                        BZH_TRY(copy2d(f_parts + order[pos] * n * 8, nq * n, cur + pos * B * len * 8, len, len, B));
             }
             for (size_t pos = 0; pos < nq; pos++)   // a set without points (not produced by the key builder): q - r itself
-                if (pk.rot_sets[order[pos]].empty()) PV_TRY(copy2d(f_parts + order[pos] * n * 8, nq * n, k_a + pos * B * n * 8, n, n, B));
+                if (pk.rot_sets[order[pos]].empty()) BZH_TRY(copy2d(f_parts + order[pos] * n * 8, nq * n, k_a + pos * B * n * 8, n, n, B));
         }
         mark("multiopen_q_kate");
         // f = sum_si x2^(..) f_si (Horner), commit, x3, q evaluations, x4, the opened polynomial
@@ -1036,11 +1007,11 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         uint32_t* p_poly = dalloc(B * n);
         if (!f_poly || !p_poly) return BZH_E_OOM;
         if (nq == 1) {
-            PV_TRY(copy2d(f_poly, n, f_parts, n, n, B));
+            BZH_TRY(copy2d(f_poly, n, f_parts, n, n, B));
         } else {
             Cols reg;
             for (size_t si = 0; si < nq; si++) reg.add(key(K_MISC, M_H0 + si), f_parts + si * n * 8, nq * n);
-            PV_TRY(run(key(43, 0), [&](EPool& ep) {
+            BZH_TRY(run(key(43, 0), [&](EPool& ep) {
                 std::vector<int> t;
                 for (size_t si = 0; si < nq; si++) t.push_back(ep.query((int)si));
                 return ep.horner(t, ep.sym(SY_X2));
@@ -1048,7 +1019,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         }
         std::vector<Fe<SF>> f_blinds(B), x3s(B);
         for (size_t b = 0; b < B; b++) f_blinds[b] = draw(b);
-        PV_TRY(commit(f_poly, n, B, f_blinds, xy));
+        BZH_TRY(commit(f_poly, n, B, f_blinds, xy));
         for (size_t b = 0; b < B; b++) {
             bzh_transcript_write_point(T[b], C::id, &xy[b * 8]);
             x3s[b] = squeeze(b);
@@ -1056,7 +1027,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         std::vector<Fe<SF>> p3(B * nq), v3;
         for (size_t b = 0; b < B; b++)
             for (size_t si = 0; si < nq; si++) p3[b * nq + si] = x3s[b];
-        PV_TRY(evals(q_polys, B * nq, p3, v3));
+        BZH_TRY(evals(q_polys, B * nq, p3, v3));
         for (size_t b = 0; b < B; b++) {
             for (size_t si = 0; si < nq; si++) write_scalar(b, v3[b * nq + si]);
             env[b][SY_X4] = squeeze(b);
@@ -1065,7 +1036,7 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
             Cols reg;
             reg.add(key(K_MISC, M_F), f_poly, n);
             for (size_t si = 0; si < nq; si++) reg.add(key(K_MISC, M_H0 + si), q_polys + si * n * 8, nq * n);
-            PV_TRY(run(key(44, 0), [&](EPool& ep) {
+            BZH_TRY(run(key(44, 0), [&](EPool& ep) {
                 std::vector<int> t;
                 for (size_t c = 0; c <= nq; c++) t.push_back(ep.query((int)c));
                 return ep.horner(t, ep.sym(SY_X4));
@@ -1075,8 +1046,8 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         for (size_t b = 0; b < B; b++) {
             Fe<SF> acc = f_blinds[b];
             for (size_t si = 0; si < nq; si++) acc = fe_add(fe_mul(acc, env[b][SY_X4]), q_blinds[b * nq + si]);
-            h_store<SF>(&p_blinds[4 * b], fe_from_mont(acc));
-            h_store<SF>(&x3c[4 * b], fe_from_mont(x3s[b]));
+            fe_to_u64<SF>(&p_blinds[4 * b], fe_from_mont(acc));
+            fe_to_u64<SF>(&x3c[4 * b], fe_from_mont(x3s[b]));
         }
         mark("multiopen_f_p");
         // the opening draws from each proof's own cursor: a zero stride is not possible, so pass proof 0's cursor and the
@@ -1085,19 +1056,19 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
         if (seeded) {
             uint32_t* raw = (uint32_t*)arena.alloc(B * need);
             if (!raw) return BZH_E_OOM;
-            PV_TRY(seed_rows(need / 64, raw));
-            PV_TRY(ipa_open(ctx, pk.srs, p_poly, B, p_blinds.data(), x3c.data(), nullptr, need, T.data(), out_v.data(), raw));
+            BZH_TRY(seed_rows(need / 64, raw));
+            BZH_TRY(ipa_open(ctx, pk.srs, p_poly, B, p_blinds.data(), x3c.data(), nullptr, need, T.data(), out_v.data(), raw));
         } else {
             std::vector<uint8_t> ipa_rng(B * need);
             for (size_t b = 0; b < B; b++) memcpy(&ipa_rng[b * need], rng[b], need);
-            PV_TRY(ipa_open(ctx, pk.srs, p_poly, B, p_blinds.data(), x3c.data(), ipa_rng.data(), need, T.data(), out_v.data()));
+            BZH_TRY(ipa_open(ctx, pk.srs, p_poly, B, p_blinds.data(), x3c.data(), ipa_rng.data(), need, T.data(), out_v.data()));
         }
     }
     mark("ipa");
     for (size_t b = 0; b < B; b++) {
         const uint8_t* data = nullptr;
         size_t plen = 0;
-        PV_TRY(bzh_transcript_proof(T[b], &data, &plen));
+        BZH_TRY(bzh_transcript_proof(T[b], &data, &plen));
         if (plen > proof_stride) return BZH_E_ARG;
         memcpy(proofs + b * proof_stride, data, plen);
         proof_lens[b] = plen;

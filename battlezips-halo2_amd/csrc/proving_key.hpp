@@ -192,23 +192,6 @@ static int lower(const bzh_pk& pk, int i, EPool& ep, const Cols& reg, int rot_sc
     }
 }
 
-#define PV_TRY(expr)           \
-    do {                       \
-        int rc__ = (expr);     \
-        if (rc__) return rc__; \
-    } while (0)
-
-template <class C>
-struct CurveScalar;
-template <>
-struct CurveScalar<VestaCurve> {
-    using SF = FpParams;
-};
-template <>
-struct CurveScalar<PallasCurve> {
-    using SF = FqParams;
-};
-
 // ---------------------------------------------------------------------------
 // keygen
 // ---------------------------------------------------------------------------
@@ -440,9 +423,9 @@ struct ParsedKey {
 // extended domain), the permutation cycles and the multiopen structure, and compile the quotient program.  No device work:
 // this is also what the build-time kernel generator runs (bzh_quotient_source_for_circuit).
 template <class C>
-static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typename CurveScalar<C>::SF>& po) {
-    using SF = typename CurveScalar<C>::SF;
-    using FM = FieldMeta<SF>;
+static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typename CurveInfo<C>::SF>& po) {
+    using SF = typename CurveInfo<C>::SF;
+    using FM = FieldInfo<SF>;
     Reader r{blob, blob + len};
     const uint32_t magic = r.u32();
     if (magic != 0x31435A42u && magic != 0x32435A42u) return BZH_E_ARG;  // "BZC1" / "BZC2"
@@ -581,25 +564,11 @@ static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typ
     if ((size_t)pk.npieces * n > pk.en) return BZH_E_ARG;
 
     // domain constants
-    uint32_t e[8];
-    {  // (p - 1) >> S
-        uint32_t pm1[8];
-        for (int i = 0; i < 8; i++) pm1[i] = SF::mod(i);
-        pm1[0] -= 1;  // p is odd
-        for (int i = 0; i < 8; i++) {
-            const unsigned s = FM::S, src = i + s / 32;
-            const uint64_t lo = src < 8 ? pm1[src] : 0, hi = src + 1 < 8 ? pm1[src + 1] : 0;
-            e[i] = (s % 32) ? (uint32_t)(((lo | (hi << 32)) >> (s % 32)) & 0xffffffffu) : (uint32_t)lo;
-        }
-    }
     const Fe<SF> gen = fe_from_u32<SF>(FM::gen);
-    const Fe<SF> root = fe_pow(gen, e);
-    auto pow2 = [](Fe<SF> v, unsigned times) {
-        for (unsigned i = 0; i < times; i++) v = fe_sqr(v);
-        return v;
-    };
-    const Fe<SF> omega = pow2(root, FM::S - pk.k), eomega = pow2(root, FM::S - pk.ek);
-    const Fe<SF> delta = pow2(gen, FM::S);
+    const Fe<SF> root = h_root_of_unity<SF>();
+    const Fe<SF> omega = h_omega(root, pk.k), eomega = h_omega(root, pk.ek);
+    Fe<SF> delta = gen;  // gen^(2^S)
+    for (unsigned i = 0; i < FM::S; i++) delta = fe_sqr(delta);
     Fe<SF> zeta;
     {  // g^((p-1)/3)
         uint32_t q[8];
@@ -615,9 +584,9 @@ static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typ
         if (rem) return BZH_E_RANGE;  // no cube root of unity: the coset fast path needs 3 | p - 1
         zeta = fe_pow(gen, q);
     }
-    h_store<SF>(pk.omega, omega);
-    h_store<SF>(pk.eomega, eomega);
-    h_store<SF>(pk.zeta, zeta);
+    fe_to_u64<SF>(pk.omega, omega);
+    fe_to_u64<SF>(pk.eomega, eomega);
+    fe_to_u64<SF>(pk.zeta, zeta);
     memcpy(pk.delta, delta.l, 32);
     po.omega = omega, po.eomega = eomega, po.delta = delta, po.zeta = zeta;
 
@@ -723,11 +692,11 @@ static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typ
 // l_0 / l_last / l_blind, X and 1 / (X^n - 1) on the extended coset, the hoisted columns of the quotient program.
 template <class C>
 static int pk_create_t(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* blob, size_t len, bzh_pk** out) {
-    using SF = typename CurveScalar<C>::SF;
+    using SF = typename CurveInfo<C>::SF;
     std::unique_ptr<bzh_pk> pkp(new bzh_pk());
     bzh_pk& pk = *pkp;
     ParsedKey<SF> po;
-    PV_TRY(pk_parse_t<C>(blob, len, pk, po));
+    BZH_TRY(pk_parse_t<C>(blob, len, pk, po));
     pk.device = ctx->device;
     pk.srs = srs;
     if (srs->n != pk.n + 2 || srs->curve != C::id) return BZH_E_ARG;
@@ -780,38 +749,38 @@ static int pk_create_t(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* blob, 
         if (!count) return BZH_OK;
         return ntt_run_padded(ctx, pk.field, dst, polys, pk.k, pk.ek, count, pk.eomega, pk.zeta);
     };
-    PV_TRY(up(pk.fixed, fixed_h.data(), nf * n));
-    PV_TRY(to_coeff(pk.fixed_polys, pk.fixed, nf));
-    PV_TRY(to_extended(pk.fixed_cosets, pk.fixed_polys, nf));
+    BZH_TRY(up(pk.fixed, fixed_h.data(), nf * n));
+    BZH_TRY(to_coeff(pk.fixed_polys, pk.fixed, nf));
+    BZH_TRY(to_extended(pk.fixed_cosets, pk.fixed_polys, nf));
     for (size_t j = 0; j < m; j++)
         for (size_t rr = 0; rr < n; rr++) host[j * n + rr] = fe_mul(dpow[j], wp[rr]);
-    PV_TRY(up(pk.ident, host.data(), m * n));
+    BZH_TRY(up(pk.ident, host.data(), m * n));
     for (size_t j = 0; j < m; j++)
         for (size_t rr = 0; rr < n; rr++) host[j * n + rr] = fe_mul(dpow[map_c[j * n + rr]], wp[map_r[j * n + rr]]);
-    PV_TRY(up(pk.sigma, host.data(), m * n));
-    PV_TRY(to_coeff(pk.sigma_polys, pk.sigma, m));
-    PV_TRY(to_extended(pk.sigma_cosets, pk.sigma_polys, m));
+    BZH_TRY(up(pk.sigma, host.data(), m * n));
+    BZH_TRY(to_coeff(pk.sigma_polys, pk.sigma, m));
+    BZH_TRY(to_extended(pk.sigma_cosets, pk.sigma_polys, m));
     for (size_t i = 0; i < 3 * n; i++) host[i] = fe_zero<SF>();
     host[0] = fe_one<SF>();
     host[n + pk.usable] = fe_one<SF>();
     for (size_t i = pk.usable + 1; i < n; i++) host[2 * n + i] = fe_one<SF>();
-    PV_TRY(up(l_tmp, host.data(), 3 * n));
-    PV_TRY(ntt_run(ctx, pk.field, l_tmp, pk.k, 3, pk.omega, nullptr, 1, BZH_FORM_MONTGOMERY));
-    PV_TRY(to_extended(pk.l0, l_tmp, 3));  // l0, l_last, l_blind are consecutive
+    BZH_TRY(up(l_tmp, host.data(), 3 * n));
+    BZH_TRY(ntt_run(ctx, pk.field, l_tmp, pk.k, 3, pk.omega, nullptr, 1, BZH_FORM_MONTGOMERY));
+    BZH_TRY(to_extended(pk.l0, l_tmp, 3));  // l0, l_last, l_blind are consecutive
     {
         Fe<SF> x = zeta;
         for (size_t i = 0; i < en; i++) {
             host[i] = x;
             x = fe_mul(x, eomega);
         }
-        PV_TRY(up(pk.x_col, host.data(), en));
+        BZH_TRY(up(pk.x_col, host.data(), en));
         std::vector<Fe<SF>> tinv(pk.ext);
         for (size_t i = 0; i < pk.ext; i++) tinv[i] = fe_inv(fe_sub(h_pow_u64(host[i], n), fe_one<SF>()));
         for (size_t i = 0; i < en; i++) host[i] = tinv[i % pk.ext];
-        PV_TRY(up(pk.tinv_col, host.data(), en));
+        BZH_TRY(up(pk.tinv_col, host.data(), en));
     }
 
-    PV_TRY(materialize_hoist<SF>(ctx, pk));
+    BZH_TRY(materialize_hoist<SF>(ctx, pk));
     pk.q_builtin = nullptr;
     if (pk.q_ok) {
         size_t nb = 0;

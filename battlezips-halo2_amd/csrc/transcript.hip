@@ -12,30 +12,10 @@
 #include <vector>
 
 #include "blake2b.hpp"
-#include "curve.cuh"
+#include "host_field.hpp"
 #include "../../include/bzh2.h"
 
-namespace {
-
 using bzh::Blake2b;
-
-template <class P>
-void reduce_wide(const uint8_t d[64], uint64_t out[4]) {
-    using namespace bzh;
-    Fe<P> lo, hi;
-    for (int i = 0; i < 8; i++) {
-        uint32_t a, b;
-        memcpy(&a, d + 4 * i, 4);
-        memcpy(&b, d + 32 + 4 * i, 4);
-        lo.l[i] = a;
-        hi.l[i] = b;
-    }
-    // x = lo + hi * 2^256 (mod p):  lo mod p = from_mont(to_mont(lo));  hi * R mod p = to_mont(hi)
-    Fe<P> r = fe_add(fe_from_mont(fe_to_mont(lo)), fe_to_mont(hi));
-    for (int i = 0; i < 4; i++) out[i] = (uint64_t)r.l[2 * i] | ((uint64_t)r.l[2 * i + 1] << 32);
-}
-
-}  // namespace
 
 struct bzh_transcript {
     Blake2b state;
@@ -97,13 +77,10 @@ int bzh_transcript_squeeze_challenge(bzh_transcript* t, uint64_t* out_canonical)
     t->state.update(&zero, 1);
     uint8_t d[64];
     t->state.finalize(d);
-    switch (t->field) {
-        case BZH_FIELD_FP: reduce_wide<bzh::FpParams>(d, out_canonical); break;
-        case BZH_FIELD_FQ: reduce_wide<bzh::FqParams>(d, out_canonical); break;
-        case BZH_FIELD_BN254_FR: reduce_wide<bzh::BnFrParams>(d, out_canonical); break;
-        case BZH_FIELD_BN254_FQ: reduce_wide<bzh::BnFqParams>(d, out_canonical); break;
-    }
-    return BZH_OK;
+    return bzh::with_field(t->field, [&](auto p) {
+        bzh::fe_to_u64(out_canonical, bzh::h_from_u512<decltype(p)>(d), BZH_FORM_CANONICAL);
+        return BZH_OK;
+    });
 }
 int bzh_transcript_proof(const bzh_transcript* t, const uint8_t** data, size_t* len) {
     if (!t || !data || !len) return BZH_E_ARG;

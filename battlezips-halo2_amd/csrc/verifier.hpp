@@ -8,7 +8,7 @@
 // ---------------------------------------------------------------------------
 template <class C>
 struct ProofView {
-    using SF = typename CurveScalar<C>::SF;
+    using SF = typename CurveInfo<C>::SF;
     // outputs of the host pass: left-side linear combination and the right side's (c, u_j)
     std::vector<uint64_t> lc_pts, lc_scal, cu;
     bool ok = false;
@@ -47,7 +47,7 @@ static Fe<SF> cx_eval(const bzh_pk& pk, int i, const std::vector<Fe<SF>>& adv, c
 template <class C>
 static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t* proof, size_t len, size_t nl_cap,
                         ProofView<C>& out) {
-    using SF = typename CurveScalar<C>::SF;
+    using SF = typename CurveInfo<C>::SF;
     const int na = pk.na, ni = pk.ni, nsets = pk.nsets, nl = pk.nl, npieces = pk.npieces;
     const size_t n = pk.n, m = pk.perm_columns.size();
     const unsigned k = pk.k;
@@ -90,16 +90,15 @@ static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t
         }
         memcpy(l, proof + off, 32);
         off += 32;
-        Fe<SF> v = h_load<SF>(l), t = v;
-        fe_cond_sub_p(t, 0);
-        if (!fe_eq(t, v)) bad = true;  // non-canonical encoding
+        const Fe<SF> v = fe_from_u64<SF>(l);
+        if (!is_canonical(v)) bad = true;
         bzh_transcript_common_scalar(T, l);
         return fe_to_mont(v);
     };
     auto squeeze = [&]() {
         uint64_t ch[4];
         bzh_transcript_squeeze_challenge(T, ch);
-        return fe_to_mont(h_load<SF>(ch));
+        return fe_to_mont(fe_from_u64<SF>(ch));
     };
     bzh_transcript_common_scalar(T, pk.vk_repr);
     for (int i = 0; i < ni; i++) bzh_transcript_common_point(T, inst_xy + 8 * i);
@@ -148,12 +147,12 @@ static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t
     {
         uint64_t t[4];
         memcpy(t, pk.omega, 32);
-        omega = h_load<SF>(t);
+        omega = fe_from_u64<SF>(t);
     }
     Fe<SF> nfe = fe_zero<SF>();
     {
         uint64_t t[4] = {(uint64_t)n, 0, 0, 0};
-        nfe = fe_to_mont(h_load<SF>(t));
+        nfe = fe_to_mont(fe_from_u64<SF>(t));
     }
     const Fe<SF> xn1 = fe_sub(xn, one);
     if (fe_is_zero(xn1)) return false;
@@ -340,13 +339,8 @@ static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t
     uint64_t cl[4], fl[4];
     memcpy(cl, proof + off, 32);
     memcpy(fl, proof + off + 32, 32);
-    Fe<SF> cc = h_load<SF>(cl), ff = h_load<SF>(fl);
-    {
-        Fe<SF> t = cc, t2 = ff;
-        fe_cond_sub_p(t, 0);
-        fe_cond_sub_p(t2, 0);
-        if (!fe_eq(t, cc) || !fe_eq(t2, ff)) return false;
-    }
+    const Fe<SF> cc = fe_from_u64<SF>(cl), ff = fe_from_u64<SF>(fl);
+    if (!is_canonical(cc) || !is_canonical(ff)) return false;
     const Fe<SF> cm = fe_to_mont(cc), fm = fe_to_mont(ff);
     std::vector<Fe<SF>> xp(k ? k : 1);
     if (k) {
@@ -355,16 +349,8 @@ static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t
     }
     Fe<SF> b0 = one;
     for (unsigned j = 0; j < k; j++) b0 = fe_mul(b0, fe_add(one, fe_mul(us[j], xp[k - 1 - j])));
-    // batch-invert the u_j
-    std::vector<Fe<SF>> pre(k + 1);
-    pre[0] = one;
-    for (unsigned j = 0; j < k; j++) pre[j + 1] = fe_mul(pre[j], us[j]);
-    Fe<SF> inv = fe_inv(pre[k]);
-    std::vector<Fe<SF>> uinv(k);
-    for (unsigned j = k; j-- > 0;) {
-        uinv[j] = fe_mul(inv, pre[j]);
-        inv = fe_mul(inv, us[j]);
-    }
+    std::vector<Fe<SF>> uinv = us;
+    h_batch_invert(uinv.data(), k);  // (none of the u_j is zero: checked above)
     for (unsigned j = 0; j < k; j++) {
         lc.push_back({&pts[Ls[j] * 8], uinv[j]});
         lc.push_back({&pts[Rs[j] * 8], us[j]});
@@ -377,16 +363,16 @@ static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t
     size_t o = 0;
     for (auto& t : lc) {
         memcpy(&out.lc_pts[o * 8], t.pt, 64);
-        h_store<SF>(&out.lc_scal[o * 4], fe_from_mont(t.s));
+        fe_to_u64<SF>(&out.lc_scal[o * 4], fe_from_mont(t.s));
         o++;
     }
     // scalars of G_0 (-v), U (-c b0 z), W (-f): points filled in by the caller (slots nl_cap-3 .. nl_cap-1)
-    h_store<SF>(&out.lc_scal[(nl_cap - 3) * 4], fe_from_mont(fe_neg(final_v)));
-    h_store<SF>(&out.lc_scal[(nl_cap - 2) * 4], fe_from_mont(fe_neg(fe_mul(fe_mul(cm, b0), z))));
-    h_store<SF>(&out.lc_scal[(nl_cap - 1) * 4], fe_from_mont(fe_neg(fm)));
+    fe_to_u64<SF>(&out.lc_scal[(nl_cap - 3) * 4], fe_from_mont(fe_neg(final_v)));
+    fe_to_u64<SF>(&out.lc_scal[(nl_cap - 2) * 4], fe_from_mont(fe_neg(fe_mul(fe_mul(cm, b0), z))));
+    fe_to_u64<SF>(&out.lc_scal[(nl_cap - 1) * 4], fe_from_mont(fe_neg(fm)));
     out.cu.assign((size_t)(k + 1) * 4, 0);
-    h_store<SF>(&out.cu[0], fe_from_mont(cm));
-    for (unsigned j = 0; j < k; j++) h_store<SF>(&out.cu[(j + 1) * 4], fe_from_mont(us[j]));
+    fe_to_u64<SF>(&out.cu[0], fe_from_mont(cm));
+    for (unsigned j = 0; j < k; j++) fe_to_u64<SF>(&out.cu[(j + 1) * 4], fe_from_mont(us[j]));
     out.ok = true;
     return true;
 }
@@ -394,7 +380,7 @@ static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t
 template <class C>
 static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* instances, size_t inst_rows, const uint8_t* proofs,
                           size_t proof_stride, const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
-    using SF = typename CurveScalar<C>::SF;
+    using SF = typename CurveInfo<C>::SF;
     Arena& arena = pk->arena_for(ctx, ctx->device);
     arena.reset();
     Prover<C> pv(ctx, *pk, batch, arena);
@@ -407,9 +393,9 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
         if (!pk->vk_ready) {  // verifying key: commitments to the fixed and permutation polynomials, blind 1
             const size_t nf = pk->nf, m = pk->perm_columns.size();
             blinds.assign(nf, fe_one<SF>());
-            PV_TRY(pv.commit(pk->fixed_polys, n, nf, blinds, pk->fixed_commitments));
+            BZH_TRY(pv.commit(pk->fixed_polys, n, nf, blinds, pk->fixed_commitments));
             blinds.assign(m, fe_one<SF>());
-            PV_TRY(pv.commit(pk->sigma_polys, n, m, blinds, pk->sigma_commitments));
+            BZH_TRY(pv.commit(pk->sigma_polys, n, m, blinds, pk->sigma_commitments));
             pk->vk_ready = true;
         }
     }
@@ -419,18 +405,18 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
         uint32_t* inst = pv.dalloc(B * ni * n);
         uint32_t* inst_polys = pv.dalloc(B * ni * n);
         if (!inst || !inst_polys) return BZH_E_OOM;
-        PV_TRY(pv.zero(inst, B * ni * n));
+        BZH_TRY(pv.zero(inst, B * ni * n));
         if (inst_rows) {
             std::vector<Fe<SF>> hv(B * ni * inst_rows);
-            for (size_t i = 0; i < hv.size(); i++) hv[i] = fe_to_mont(h_load<SF>(instances + 4 * i));
+            for (size_t i = 0; i < hv.size(); i++) hv[i] = fe_to_mont(fe_from_u64<SF>(instances + 4 * i));
             uint32_t* tmp = pv.dalloc(hv.size());
             if (!tmp) return BZH_E_OOM;
-            PV_TRY(pv.upload(tmp, hv.data(), hv.size()));
-            PV_TRY(pv.copy2d(inst, n, tmp, inst_rows, inst_rows, B * ni));
+            BZH_TRY(pv.upload(tmp, hv.data(), hv.size()));
+            BZH_TRY(pv.copy2d(inst, n, tmp, inst_rows, inst_rows, B * ni));
         }
-        PV_TRY(pv.to_coeff(inst_polys, inst, B * ni));
+        BZH_TRY(pv.to_coeff(inst_polys, inst, B * ni));
         blinds.assign(B * ni, fe_one<SF>());
-        PV_TRY(pv.commit(inst_polys, n, B * ni, blinds, inst_xy));
+        BZH_TRY(pv.commit(inst_polys, n, B * ni, blinds, inst_xy));
     }
     // host pass, one thread per proof
     const size_t ncommit = (size_t)pk->na + 3 * pk->nl + pk->nsets + 1 + pk->npieces + 1 + pk->nf + pk->perm_columns.size() + ni;
@@ -463,7 +449,7 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
         memcpy(&cu[j * (kk + 1) * 4], v.cu.data(), (kk + 1) * 32);
     }
     std::vector<int> ok(Bl, 0);
-    PV_TRY(ipa_check_batch(ctx, pk->srs, Bl, nl_cap, lc_pts.data(), lc_scal.data(), cu.data(), ok.data()));
+    BZH_TRY(ipa_check_batch(ctx, pk->srs, Bl, nl_cap, lc_pts.data(), lc_scal.data(), cu.data(), ok.data()));
     for (size_t j = 0; j < Bl; j++) results[live[j]] = ok[j];
     return BZH_OK;
 }
