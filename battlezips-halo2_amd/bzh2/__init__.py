@@ -426,7 +426,7 @@ Context.vec_mul = _ctx_vec_mul
 
 # ---- transcript (host) ---------------------------------------------------------------------------
 EXPORTS += ["bzh_pk_quotient_select", "bzh_pk_quotient_selected", "bzh_quotient_source_for_circuit", "bzh_builtin_quotients",
-            "bzh_quotient_degree_histogram"]
+            "bzh_quotient_degree_histogram", "bzh_pk_lookup_select", "bzh_pk_lookup_selected"]
 EXPORTS += ["bzh_record_stride", "bzh_record_encode", "bzh_record_decode", "bzh_record_to_json", "bzh_record_from_json"]
 EXPORTS += ["bzh_transcript_new", "bzh_transcript_free", "bzh_transcript_common_point", "bzh_transcript_common_scalar",
             "bzh_transcript_write_point", "bzh_transcript_write_scalar", "bzh_transcript_squeeze_challenge",
@@ -632,6 +632,57 @@ def _ctx_kate_division_batch(self, field: int, coeffs, xs, form: int = FORM_CANO
 
 
 Context.kate_division_batch = _ctx_kate_division_batch
+
+
+EXPORTS += ["bzh_permute_expression_pair_batch"]
+
+
+def _bind_permute_batch():
+    L = load()
+    vp = ctypes.c_void_p
+    L.bzh_permute_expression_pair_batch.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                    ctypes.c_int, vp, vp, ctypes.POINTER(ctypes.c_int32)]
+    return L
+
+
+def _ctx_permute_expression_pair_batch(self, field: int, input_vals, table_vals, usable_rows: int, form: int = FORM_CANONICAL,
+                                       check: bool = True, out=None):
+    """lookup::prover::permute_expression_pair for `batch` pairs on the device (bzh_permute_expression_pair_batch).
+    input_vals / table_vals: (batch, stride, 4) uint64 in `form`; returns (permuted_input, permuted_table, status): the
+    outputs have the inputs' shape with rows usable_rows .. stride zero, status is (batch,) int32 -- 0, or E_RANGE for a pair
+    with an input value missing from its table.  check=True raises BzhError on such a pair; check=False hands the status
+    words and the other pairs' results back.  out: a pair of C-contiguous uint64 arrays of that shape to write into."""
+    a = np.ascontiguousarray(input_vals, dtype=np.uint64)
+    t = np.ascontiguousarray(table_vals, dtype=np.uint64)
+    if a.ndim != 3 or a.shape != t.shape or a.shape[2] != 4:
+        raise BzhError(E_ARG, "bzh_permute_expression_pair_batch", "input and table must both be (batch, stride, 4)")
+    batch, stride = a.shape[0], a.shape[1]
+    oa, ot = (np.zeros_like(a), np.zeros_like(t)) if out is None else out
+    if any(o.shape != a.shape or o.dtype != np.uint64 or not o.flags.c_contiguous for o in (oa, ot)):
+        raise BzhError(E_ARG, "bzh_permute_expression_pair_batch", "out arrays must match the inputs")
+    status = np.zeros(batch, dtype=np.int32)
+    rc = _bind_permute_batch().bzh_permute_expression_pair_batch(self.handle, field, _vp(a), _vp(t), stride, usable_rows, batch, form, MEM_HOST,
+                                                                  _vp(oa), _vp(ot), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    if rc != OK and (check or rc != E_RANGE):
+        self._check(rc, "bzh_permute_expression_pair_batch")
+    return oa, ot, status
+
+
+def _ctx_permute_expression_pair_batch_device(self, field: int, input_ptr: int, table_ptr: int, stride: int, usable_rows: int, batch: int,
+                                              out_input_ptr: int, out_table_ptr: int, form: int = FORM_MONTGOMERY, check: bool = True):
+    """Device-pointer form: every array is batch x stride elements in HBM; returns the (batch,) int32 status words."""
+    vp = ctypes.c_void_p
+    status = np.zeros(batch, dtype=np.int32)
+    rc = _bind_permute_batch().bzh_permute_expression_pair_batch(self.handle, field, vp(input_ptr), vp(table_ptr), stride, usable_rows, batch,
+                                                                  form, MEM_DEVICE, vp(out_input_ptr), vp(out_table_ptr),
+                                                                  status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    if rc != OK and (check or rc != E_RANGE):
+        self._check(rc, "bzh_permute_expression_pair_batch")
+    return status
+
+
+Context.permute_expression_pair_batch = _ctx_permute_expression_pair_batch
+Context.permute_expression_pair_batch_device = _ctx_permute_expression_pair_batch_device
 
 
 def permute_expression_pair(field: int, input_vals, table_vals, usable_rows: int, form: int = FORM_CANONICAL):

@@ -46,6 +46,7 @@ def rng_expand(seed: bytes, first_draw: int, draws: int) -> bytes:
 
 
 QUOTIENT_INTERPRETER, QUOTIENT_BUILTIN, QUOTIENT_MODULE = 0, 1, 2
+LOOKUP_HOST, LOOKUP_DEVICE = 0, 1
 
 _QUOTIENT_CODE = {}   # source hash -> code object (several keys of one circuit in a process share one compilation)
 
@@ -178,6 +179,20 @@ class NativeProvingKey:
         L = _bind()
         L.bzh_pk_quotient_select.argtypes = [_VP, ctypes.c_int]
         self.ctx._check(L.bzh_pk_quotient_select(self.handle, flavour), "bzh_pk_quotient_select")
+
+    # ---- where the lookup argument's columns are permuted ----------------------------------------------------
+    def lookup_selected(self) -> int:
+        """LOOKUP_HOST (pinned round trip + host sorts) or LOOKUP_DEVICE (csrc/lookup_permute.hip on the ctx's stream)"""
+        L = _bind()
+        L.bzh_pk_lookup_selected.argtypes = [_VP, ctypes.POINTER(ctypes.c_int)]
+        w = ctypes.c_int()
+        self.ctx._check(L.bzh_pk_lookup_selected(self.handle, ctypes.byref(w)), "bzh_pk_lookup_selected")
+        return w.value
+
+    def lookup_select(self, where: int):
+        L = _bind()
+        L.bzh_pk_lookup_select.argtypes = [_VP, ctypes.c_int]
+        self.ctx._check(L.bzh_pk_lookup_select(self.handle, where), "bzh_pk_lookup_select")
 
     def compile_quotient(self, cache_dir: str | None = None) -> bool:
         """Make the key run its quotient program as compiled code.  The reference's circuits have a kernel inside libbzh2.so

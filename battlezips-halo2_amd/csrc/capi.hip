@@ -665,6 +665,42 @@ int bzh_permute_expression_pair(int field, const uint64_t* input, const uint64_t
     return with_field(field, [&](auto p) { return permute_pair_host<decltype(p)>(input, table, usable_rows, form, out_input, out_table); });
 }
 
+int bzh_permute_expression_pair_batch(bzh_ctx* ctx, int field, const uint64_t* input, const uint64_t* table, size_t stride, size_t usable_rows,
+                                      size_t batch, int form, int mem, uint64_t* out_input, uint64_t* out_table, int32_t* status) {
+    BZH_POLY_PROLOGUE(!input || !table || !out_input || !out_table || !usable_rows || usable_rows > stride || !batch || batch > 32767 ||
+                      stride >> 31);
+    void* ws = nullptr;
+    if ((rc = ws_ensure(ctx, 1, lookup_permute_ws_bytes(usable_rows, batch), &ws))) return rc;
+    const size_t total = batch * stride;
+    const uint32_t *d_in = (const uint32_t*)input, *d_tab = (const uint32_t*)table;
+    uint32_t *d_oa = (uint32_t*)out_input, *d_os = (uint32_t*)out_table;
+    Stager s{ctx, field, BZH_FORM_MONTGOMERY};  // (raw copies: the kernels read and write either form)
+    if (mem == BZH_MEM_HOST) {
+        uint32_t *di, *dt;
+        if ((rc = s.begin(4 * total * 32 + 1024))) return rc;
+        if ((rc = s.in(input, total, &di))) return rc;
+        if ((rc = s.in(table, total, &dt))) return rc;
+        d_in = di;
+        d_tab = dt;
+        d_oa = s.carve(total * 32);
+        d_os = s.carve(total * 32);
+    }
+    int32_t* d_status = nullptr;
+    if ((rc = lookup_permute(ctx, field, d_in, d_tab, stride, usable_rows, batch, form, d_oa, d_os, stride, stride, ws, &d_status))) return rc;
+    std::vector<int32_t> st(batch, 0);
+    if ((rc = d2h_async(ctx, st.data(), d_status, batch * sizeof(int32_t)))) return rc;
+    if (mem == BZH_MEM_HOST) {
+        if ((rc = d2h_async(ctx, out_input, d_oa, total * 32))) return rc;
+        if ((rc = d2h_async(ctx, out_table, d_os, total * 32))) return rc;
+    }
+    if ((rc = d2h_finish(ctx))) return rc;
+    for (size_t b = 0; b < batch; b++) {
+        if (status) status[b] = st[b];
+        if (st[b]) rc = BZH_E_RANGE;
+    }
+    return rc;
+}
+
 int bzh_expr_eval_batch(bzh_ctx* ctx, int field, const bzh_expr_op* prog, size_t nops, const uint64_t* const* columns,
                         const size_t* column_strides, size_t ncols, const uint64_t* consts, size_t nconsts, size_t const_stride,
                         unsigned log_size, int result_slot, size_t batch, int form, int mem, uint64_t* out) {

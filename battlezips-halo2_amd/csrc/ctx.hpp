@@ -307,6 +307,13 @@ int poly_fold(bzh_ctx* ctx, int field, const uint32_t* in, size_t half, size_t b
               uint32_t* out);
 int poly_vec_mul(bzh_ctx* ctx, int field, uint32_t* a, const uint32_t* b, size_t count);
 int poly_kate_division(bzh_ctx* ctx, int field, const uint32_t* d_c, size_t n, size_t batch, const uint32_t* d_xs, uint32_t* d_q);
+// lookup_permute.hip: permute_expression_pair for `batch` (input, table) pairs on the device.  Vector b of d_in / d_tab starts at
+// element b * stride and is read in `form`; the permuted pair goes, in the same form, to d_out_a / d_out_s + b * out_stride
+// elements, rows [usable, rows) zero (rows <= out_stride).  d_ws: lookup_permute_ws_bytes() bytes.  *d_status: `batch` words
+// in d_ws, 0 or BZH_E_RANGE per pair, valid once the stream has run.
+size_t lookup_permute_ws_bytes(size_t usable, size_t batch);
+int lookup_permute(bzh_ctx* ctx, int field, const uint32_t* d_in, const uint32_t* d_tab, size_t stride, size_t usable, size_t batch, int form,
+                   uint32_t* d_out_a, uint32_t* d_out_s, size_t out_stride, size_t rows, void* d_ws, int32_t** d_status);
 // exprvm.hip
 int expr_eval(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint32_t* const* d_cols, const size_t* d_strides,
               const uint32_t* d_consts, size_t const_stride, size_t size, int result_slot, size_t batch, int nslots, uint32_t* d_out);

@@ -457,7 +457,11 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
     };
 
     mark("advice");
-    // ---- lookups: compress, permute (host sort), commit -------------------------------------------
+    // ---- lookups: compress, permute (host sort or device kernels: bzh_pk_lookup_select), commit -----
+    const bool lk_device = [&] {
+        std::lock_guard<std::mutex> g(pk.mu);
+        return pk.lk_select == BZH_LOOKUP_DEVICE;
+    }();
     struct Lk {
         uint32_t *a_c, *s_c, *as, *polys, *cosets;
         std::vector<Fe<SF>> blinds;  // (a, s) per proof
@@ -480,49 +484,68 @@ int Prover<C>::prove(const uint32_t* d_advice_in, const uint64_t* instances, siz
                 return ep.horner(terms, ep.sym(SY_THETA));
             }, reg, n, side ? d.s_c : d.a_c));
         }
-        // compressed columns come back through pinned memory; the permuted pair is assembled in a pinned slot in the
-        // device layout (B, 2, n) (rows past `usable` zero until the blinding rows land) and goes up in one piece
-        char *ah_c = nullptr, *sh_c = nullptr, *as_c = nullptr;
-        BZH_TRY(pin_big_reserve(ctx, 4 * B * n * 32 + ((size_t)3 << 20)));
-        BZH_TRY(pin_big_take(ctx, B * n * 32, &ah_c));
-        BZH_TRY(pin_big_take(ctx, B * n * 32, &sh_c));
-        BZH_TRY(pin_big_take(ctx, B * 2 * n * 32, &as_c));
-        // the host sorts canonical integers: convert on the device (copies; the Montgomery originals feed the grand product)
-        uint32_t* canon = dalloc(2 * B * n);
-        if (!canon) return BZH_E_OOM;
-        BZH_HIP_TRY(ctx, hipMemcpyAsync(canon, d.a_c, B * n * 32, hipMemcpyDeviceToDevice, st));
-        BZH_HIP_TRY(ctx, hipMemcpyAsync(canon + B * n * 8, d.s_c, B * n * 32, hipMemcpyDeviceToDevice, st));
-        BZH_TRY(field_convert(ctx, field, canon, 2 * B * n, 0));
-        BZH_TRY(xfer_launch(ctx, ah_c, canon, B * n * 32, hipMemcpyDeviceToHost));
-        BZH_TRY(xfer_launch(ctx, sh_c, canon + B * n * 8, B * n * 32, hipMemcpyDeviceToHost));
-        BZH_HIP_TRY(ctx, hipStreamSynchronize(st));
-        const uint64_t* ah = (const uint64_t*)ah_c;
-        const uint64_t* sh = (const uint64_t*)sh_c;
-        mark(" lk:compress+d2h");
-        BZH_TRY(extend_witness());
-        mark(" lk:extend_witness");
-        uint64_t* as = (uint64_t*)as_c;
-        for (size_t v = 0; v < 2 * B; v++) memset(as + (v * n + usable) * 4, 0, (n - usable) * 32);
-        {  // one sort per proof on host threads
-            // short-lived pool, capped: several provers (threads, ranks) run this at once on the same host
-            const size_t nthreads = std::min<size_t>({B, (size_t)host_thread_budget(), (size_t)8});
-            std::vector<int> rcs(B, BZH_OK);
-            std::vector<std::thread> th;
-            auto work = [&](size_t t) {
-                for (size_t b = t; b < B; b += nthreads)
-                    rcs[b] = bzh_permute_expression_pair(field, &ah[b * n * 4], &sh[b * n * 4], usable, BZH_FORM_CANONICAL,
-                                                         as + (b * 2) * n * 4, as + (b * 2 + 1) * n * 4);
-            };
-            for (size_t t = 1; t < nthreads; t++) th.emplace_back(work, t);
-            work(0);   // the calling thread takes a share (a single proof starts no thread at all)
-            for (auto& t : th) t.join();
-            for (int rc : rcs)
+        if (lk_device) {
+            // the permutation runs on the device (csrc/lookup_permute.hip), straight from the Montgomery columns into d.as in
+            // its (B, 2, n) layout; only the B status words come back
+            mark(" lk:compress");
+            std::vector<int32_t> lk_status(B, 0);
+            {
+                ArenaScope scope(arena);
+                void* ws = arena.alloc(lookup_permute_ws_bytes(usable, B));
+                if (!ws) return BZH_E_OOM;
+                int32_t* d_status = nullptr;
+                BZH_TRY(lookup_permute(ctx, field, d.a_c, d.s_c, n, usable, B, BZH_FORM_MONTGOMERY, d.as, d.as + n * 8, 2 * n, n, ws, &d_status));
+                BZH_TRY(d2h_async(ctx, lk_status.data(), d_status, B * sizeof(int32_t)));
+                BZH_TRY(d2h_finish(ctx));
+            }
+            for (int32_t rc : lk_status)
                 if (rc) return rc;
+            mark(" lk:permute");
+        } else {
+            // compressed columns come back through pinned memory; the permuted pair is assembled in a pinned slot in the
+            // device layout (B, 2, n) (rows past `usable` zero until the blinding rows land) and goes up in one piece
+            char *ah_c = nullptr, *sh_c = nullptr, *as_c = nullptr;
+            BZH_TRY(pin_big_reserve(ctx, 4 * B * n * 32 + ((size_t)3 << 20)));
+            BZH_TRY(pin_big_take(ctx, B * n * 32, &ah_c));
+            BZH_TRY(pin_big_take(ctx, B * n * 32, &sh_c));
+            BZH_TRY(pin_big_take(ctx, B * 2 * n * 32, &as_c));
+            // the host sorts canonical integers: convert on the device (copies; the Montgomery originals feed the grand product)
+            uint32_t* canon = dalloc(2 * B * n);
+            if (!canon) return BZH_E_OOM;
+            BZH_HIP_TRY(ctx, hipMemcpyAsync(canon, d.a_c, B * n * 32, hipMemcpyDeviceToDevice, st));
+            BZH_HIP_TRY(ctx, hipMemcpyAsync(canon + B * n * 8, d.s_c, B * n * 32, hipMemcpyDeviceToDevice, st));
+            BZH_TRY(field_convert(ctx, field, canon, 2 * B * n, 0));
+            BZH_TRY(xfer_launch(ctx, ah_c, canon, B * n * 32, hipMemcpyDeviceToHost));
+            BZH_TRY(xfer_launch(ctx, sh_c, canon + B * n * 8, B * n * 32, hipMemcpyDeviceToHost));
+            BZH_HIP_TRY(ctx, hipStreamSynchronize(st));
+            const uint64_t* ah = (const uint64_t*)ah_c;
+            const uint64_t* sh = (const uint64_t*)sh_c;
+            mark(" lk:compress+d2h");
+            BZH_TRY(extend_witness());
+            mark(" lk:extend_witness");
+            uint64_t* as = (uint64_t*)as_c;
+            for (size_t v = 0; v < 2 * B; v++) memset(as + (v * n + usable) * 4, 0, (n - usable) * 32);
+            {  // one sort per proof on host threads
+                // short-lived pool, capped: several provers (threads, ranks) run this at once on the same host
+                const size_t nthreads = std::min<size_t>({B, (size_t)host_thread_budget(), (size_t)8});
+                std::vector<int> rcs(B, BZH_OK);
+                std::vector<std::thread> th;
+                auto work = [&](size_t t) {
+                    for (size_t b = t; b < B; b += nthreads)
+                        rcs[b] = bzh_permute_expression_pair(field, &ah[b * n * 4], &sh[b * n * 4], usable, BZH_FORM_CANONICAL,
+                                                             as + (b * 2) * n * 4, as + (b * 2 + 1) * n * 4);
+                };
+                for (size_t t = 1; t < nthreads; t++) th.emplace_back(work, t);
+                work(0);   // the calling thread takes a share (a single proof starts no thread at all)
+                for (auto& t : th) t.join();
+                for (int rc : rcs)
+                    if (rc) return rc;
+            }
+            mark(" lk:sort");
+            BZH_TRY(h2d_commit(ctx, d.as, as_c, B * 2 * n * 32));
+            BZH_TRY(field_convert(ctx, field, d.as, B * 2 * n, 1));  // back to Montgomery form (the zero rows stay zero)
+            mark(" lk:h2d");
         }
-        mark(" lk:sort");
-        BZH_TRY(h2d_commit(ctx, d.as, as_c, B * 2 * n * 32));
-        BZH_TRY(field_convert(ctx, field, d.as, B * 2 * n, 1));  // back to Montgomery form (the zero rows stay zero)
-        mark(" lk:h2d");
         {
             uint32_t* rows = dalloc(B * 2 * bf1);
             if (!rows) return BZH_E_OOM;

@@ -52,6 +52,7 @@ struct bzh_pk {
     hipModule_t q_module = nullptr;
     hipFunction_t q_fn = nullptr;
     int q_select = BZH_QUOTIENT_INTERPRETER;
+    int lk_select = BZH_LOOKUP_HOST;   // BZH_LOOKUP_*: where the lookup argument's columns are permuted (bzh_pk_lookup_select)
     // multiopen structure: rotation sets and the commitments grouped under each
     std::vector<std::vector<int>> rot_sets;
     std::vector<std::vector<uint64_t>> groups;

@@ -202,6 +202,16 @@ int bzh_kate_division_batch(bzh_ctx* ctx, int field, const uint64_t* coeffs, siz
  * backwards, as upstream).  BZH_E_RANGE if an input value is missing from the table. */
 int bzh_permute_expression_pair(int field, const uint64_t* input, const uint64_t* table, size_t usable_rows, int form,
                                 uint64_t* out_input, uint64_t* out_table);
+/* The same for `batch` pairs on the device (csrc/lookup_permute.hip): vector b of every array starts at element b * stride,
+ * usable_rows <= stride.  Elements are read and written in `form` whichever `mem` is (Montgomery input is converted on the
+ * device); rows usable_rows .. stride of every output vector are written as zero.  Pairs whose values are all below 2^16 (range
+ * tables) are sorted by LDS histograms, any other pair by an LDS tile sort and co-rank merge passes; the choice is made on the
+ * device, per pair.  status (host, `batch` words, may be NULL): 0, or BZH_E_RANGE for a pair with an input value missing from
+ * its table -- the call then returns BZH_E_RANGE and the other pairs' outputs are still correct.  BZH_E_ARG: NULL ctx,
+ * usable_rows > stride, usable_rows = 0.  Returns when status is known (and, for BZH_MEM_HOST, the outputs are in place). */
+int bzh_permute_expression_pair_batch(bzh_ctx* ctx, int field, const uint64_t* input, const uint64_t* table, size_t stride,
+                                      size_t usable_rows, size_t batch, int form, int mem, uint64_t* out_input, uint64_t* out_table,
+                                      int32_t* status);
 
 /* ---- Fiat-Shamir transcript (host; halo2_proofs transcript::{Blake2bWrite, Challenge255}) --
  * What every create_proof caller builds first (benches/shot.rs:66-67, src/circuits/board.rs:911-912:
@@ -341,6 +351,13 @@ int bzh_pk_quotient_source(bzh_pk* pk, char* buf, size_t cap, size_t* len);
 int bzh_pk_set_quotient_module(bzh_ctx* ctx, bzh_pk* pk, const void* code_object, size_t len);
 int bzh_pk_quotient_select(bzh_pk* pk, int flavour);
 int bzh_pk_quotient_selected(bzh_pk* pk, int* flavour, int* builtin_available);
+/* Where bzh_prove_batch permutes the lookup argument's columns: BZH_LOOKUP_HOST moves the compressed columns to pinned host
+ * memory and sorts them on host threads (bzh_permute_expression_pair per proof); BZH_LOOKUP_DEVICE runs
+ * bzh_permute_expression_pair_batch's kernels on the ctx's stream and reads back one status word per proof.  Same proof bytes
+ * and statuses either way.  BZH_E_ARG: NULL key or an unknown value. */
+typedef enum { BZH_LOOKUP_HOST = 0, BZH_LOOKUP_DEVICE = 1 } bzh_lookup_where;
+int bzh_pk_lookup_select(bzh_pk* pk, int where);
+int bzh_pk_lookup_selected(bzh_pk* pk, int* where);
 /* Host only (no ctx, no GPU): the quotient program of a circuit blob as the source text of a BUILTIN kernel (namespace
  * bzh_q_<hash> with the kernel bzh_quotient_<hash> and a host function `launch`), and the program hash.  This is what the
  * build-time generator calls; BZH_E_RANGE if the circuit does not fit the evaluator (such circuits use the VM v1 fold). */
