@@ -322,6 +322,47 @@ def affine_compress(curve: int, xy: np.ndarray, form: int = FORM_CANONICAL) -> l
     return [bytes(r) for r in out]
 
 
+EXPORTS += ["bzh_batch_sqrt", "bzh_affine_decompress", "bzh_pk_verify_select", "bzh_pk_verify_selected"]
+POINT_OK, POINT_IDENTITY, POINT_INVALID = 0, 1, 2
+
+
+def _bind_sqrt():
+    L = load()
+    vp, u8p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8)
+    L.bzh_batch_sqrt.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, u8p]
+    L.bzh_affine_decompress.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, vp, u8p]
+    return L
+
+
+def batch_sqrt(field: int, data, form: int = FORM_CANONICAL, ctx=None):
+    """ff::Field::sqrt per element (bzh_batch_sqrt; the root pasta_curves 0.4.1 returns): (roots, status) -- status (n,) uint8,
+    1 = a square (its root is in `roots`), 0 = not a square (the element is handed back unchanged).  ctx None: on the host."""
+    a = np.ascontiguousarray(data, dtype=np.uint64).reshape(-1, 4).copy()
+    st = np.zeros(a.shape[0], dtype=np.uint8)
+    rc = _bind_sqrt().bzh_batch_sqrt(ctx.handle if ctx is not None else None, field, ctypes.c_void_p(a.ctypes.data), a.shape[0], form, MEM_HOST,
+                                     st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    if rc != OK:
+        raise BzhError(rc, "bzh_batch_sqrt")
+    return a, st
+
+
+def affine_decompress(curve: int, in32, form: int = FORM_CANONICAL, ctx=None, check: bool = False):
+    """pasta_curves from_bytes for a list of 32-byte strings (bzh_affine_decompress): (xy, status) -- xy (n, 8) uint64 in `form`,
+    status (n,) uint8 of POINT_OK / POINT_IDENTITY / POINT_INVALID (zeros in xy unless POINT_OK).  check=True passes no status
+    buffer: BzhError E_RANGE if any string is not a point.  ctx None: on the host."""
+    raw = b"".join(bytes(b) for b in in32)
+    assert len(raw) % 32 == 0
+    n = len(raw) // 32
+    buf = np.frombuffer(raw, dtype=np.uint8).copy() if n else np.zeros(0, dtype=np.uint8)
+    xy = np.zeros((n, 8), dtype=np.uint64)
+    st = np.zeros(n, dtype=np.uint8)
+    rc = _bind_sqrt().bzh_affine_decompress(ctx.handle if ctx is not None else None, curve, ctypes.c_void_p(buf.ctypes.data), n, form, MEM_HOST,
+                                            ctypes.c_void_p(xy.ctypes.data), None if check else st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    if rc != OK:
+        raise BzhError(rc, "bzh_affine_decompress")
+    return xy, st
+
+
 def field_omega(field: int, log_n: int, form: int = FORM_CANONICAL) -> np.ndarray:
     out = np.zeros(4, dtype=np.uint64)
     rc = load().bzh_field_omega(field, log_n, form, _u64(out))

@@ -47,6 +47,7 @@ def rng_expand(seed: bytes, first_draw: int, draws: int) -> bytes:
 
 QUOTIENT_INTERPRETER, QUOTIENT_BUILTIN, QUOTIENT_MODULE = 0, 1, 2
 LOOKUP_HOST, LOOKUP_DEVICE = 0, 1
+VERIFY_POINTS_HOST, VERIFY_POINTS_DEVICE = 0, 1
 
 _QUOTIENT_CODE = {}   # source hash -> code object (several keys of one circuit in a process share one compilation)
 
@@ -193,6 +194,20 @@ class NativeProvingKey:
         L = _bind()
         L.bzh_pk_lookup_select.argtypes = [_VP, ctypes.c_int]
         self.ctx._check(L.bzh_pk_lookup_select(self.handle, where), "bzh_pk_lookup_select")
+
+    # ---- where bzh_verify_batch decompresses the proofs' points ----------------------------------------------
+    def verify_selected(self) -> int:
+        """VERIFY_POINTS_HOST (inside the per-proof host pass) or VERIFY_POINTS_DEVICE (one k_decompress launch per batch)"""
+        L = _bind()
+        L.bzh_pk_verify_selected.argtypes = [_VP, ctypes.POINTER(ctypes.c_int)]
+        w = ctypes.c_int()
+        self.ctx._check(L.bzh_pk_verify_selected(self.handle, ctypes.byref(w)), "bzh_pk_verify_selected")
+        return w.value
+
+    def verify_select(self, where: int):
+        L = _bind()
+        L.bzh_pk_verify_select.argtypes = [_VP, ctypes.c_int]
+        self.ctx._check(L.bzh_pk_verify_select(self.handle, where), "bzh_pk_verify_select")
 
     def compile_quotient(self, cache_dir: str | None = None) -> bool:
         """Make the key run its quotient program as compiled code.  The reference's circuits have a kernel inside libbzh2.so

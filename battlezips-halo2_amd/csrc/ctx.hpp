@@ -66,6 +66,7 @@ struct bzh_ctx {
     };
     std::vector<PendingD2H> pending_d2h;
     uint32_t* ped_tbl = nullptr;   // bzh_pedersen_commit_batch's direct-lookup table of V and R (csrc/pedersen.hip), built on first use
+    uint32_t* sqrt_tbl[4] = {nullptr, nullptr, nullptr, nullptr};   // per field: g^(2^i), i <= S, for the square root (csrc/sqrt_decompress.hip), on first use
 };
 
 #define BZH_HIP_TRY(ctx, expr)                                                                    \
@@ -330,5 +331,10 @@ int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_
 int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
                     const uint64_t* cu, int* ok);
 bool point_decompress(int curve, const uint8_t* in, uint64_t* xy_canonical);
+// sqrt_decompress.hip (device pointers, 16-byte aligned; elements and points in `form`).  batch_sqrt_run: in place, d_status[i] = 1
+// for a square (root written), 0 otherwise (element untouched).  decompress_run: n x 32 bytes -> n affine points x || y and one
+// BZH_POINT_* byte each; zeros unless BZH_POINT_OK.
+int batch_sqrt_run(bzh_ctx* ctx, int field, uint32_t* d_data, size_t count, int form, uint8_t* d_status);
+int decompress_run(bzh_ctx* ctx, int curve, const uint32_t* d_in, size_t n, int form, uint32_t* d_out_xy, uint8_t* d_status);
 
 }  // namespace bzh

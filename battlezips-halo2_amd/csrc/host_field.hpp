@@ -172,40 +172,134 @@ template <class P>
 inline Fe<P> h_omega(unsigned log_n) {
     return h_omega(h_root_of_unity<P>(), log_n);
 }
-// square root (Tonelli-Shanks); false if a is a non-residue
+// ---------------------------------------------------------------------------
+// square root, host and device (csrc/sqrt_decompress.hip runs the same function, one lane per element)
+//
+// The root is the one pasta_curves 0.4.1's `sqrt` returns (circuit/hostfield.hpp states the choice): with p - 1 = 2^S T,
+// g = gen^T and t in [0, 2^S) such that u^T g^t = 1 -- t is even exactly when u is a square -- it is u^((T+1)/2) g^(t/2).
+//   * v = u^((T-1)/2) by 3-bit fixed windows over the compile-time exponent p >> (S + 1); then w = v u = u^((T+1)/2) and
+//     x = w v = u^T, so no inversion is needed.
+//   * t bit by bit from the bottom, in two halves (Pohlig-Hellman): x^(2^HI) has order dividing 2^LO and gives the low LO bits
+//     with chains of at most LO - 1 squarings; x g^(t_lo) then has order dividing 2^HI and gives the rest.  S = 32 costs
+//     16 + 2 * 120 squarings instead of 496.
+//   * every loop bound is a constant of the field; a set bit multiplies by g^(2^i) through a select.  No trip count and no
+//     branch depends on u, so a wave runs it in lockstep.
+// gpow: g^(2^i) for i <= S, 8 Montgomery limbs each (h_sqrt_table on the host; the ctx owns the device copy).
+// ---------------------------------------------------------------------------
+template <class P>
+BZH_HD Fe<P> fe_csel(bool c, const Fe<P>& a, const Fe<P>& b) {  // c ? a : b
+    Fe<P> r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.l[i] = c ? a.l[i] : b.l[i];
+    return r;
+}
+template <class P>
+struct SqrtExp {
+    static constexpr unsigned S = FieldInfo<P>::S;
+    // bit i of (T - 1) / 2 = (p - 1) >> (S + 1) = p >> (S + 1)
+    BZH_HD static constexpr unsigned bit(unsigned i) {
+        const unsigned j = i + S + 1;
+        return j < 256 ? (P::mod((int)(j >> 5)) >> (j & 31)) & 1u : 0u;
+    }
+    BZH_HD static constexpr unsigned digit(int w) { return bit(3 * w) | (bit(3 * w + 1) << 1) | (bit(3 * w + 2) << 2); }
+    static constexpr int top_window() {
+        int w = 85;
+        while (w > 0 && digit(w) == 0) w--;
+        return w;
+    }
+    static constexpr int top = top_window();
+};
+template <class P>
+BZH_HD Fe<P> fe_sqrt_window(const Fe<P> (&tb)[7], unsigned d) {  // tb[d - 1], d in 1..7, as selects (d is uniform)
+    Fe<P> r = tb[0];
+#pragma unroll
+    for (int j = 1; j < 7; j++) r = fe_csel(d == (unsigned)(j + 1), tb[j], r);
+    return r;
+}
+template <class P>
+BZH_HD Fe<P> fe_sqrt_gpow(const uint32_t* gpow, unsigned i) {
+    Fe<P> r;
+#pragma unroll
+    for (int k = 0; k < 8; k++) r.l[k] = gpow[8 * i + k];
+    return r;
+}
+// false: u is not a square (root is then unspecified).  Zero maps to zero.
+template <class P>
+BZH_HD bool fe_sqrt_ct(const Fe<P>& u, const uint32_t* gpow, Fe<P>& root) {
+    constexpr unsigned S = FieldInfo<P>::S, LO = S / 2, HI = S - LO;
+    Fe<P> tb[7];  // u^1 .. u^7
+    tb[0] = u;
+    tb[1] = fe_sqr(u);
+    tb[2] = fe_mul(tb[1], u);
+    tb[3] = fe_sqr(tb[1]);
+    tb[4] = fe_mul(tb[3], u);
+    tb[5] = fe_sqr(tb[2]);
+    tb[6] = fe_mul(tb[5], u);
+    Fe<P> v = fe_sqrt_window(tb, SqrtExp<P>::digit(SqrtExp<P>::top));
+#pragma unroll 1
+    for (int w = SqrtExp<P>::top - 1; w >= 0; w--) {
+        v = fe_sqr(fe_sqr(fe_sqr(v)));
+        const unsigned d = SqrtExp<P>::digit(w);
+        if (d) v = fe_mul(v, fe_sqrt_window(tb, d));
+    }
+    const Fe<P> one = fe_one<P>();
+    Fe<P> res = fe_mul(v, u);    // u^((T+1)/2)
+    Fe<P> cur = fe_mul(res, v);  // u^T, in the 2-Sylow subgroup; from here on cur = u^T g^(bits of t found so far)
+    bool odd = false;            // bit 0 of t
+    if constexpr (LO > 0) {
+        Fe<P> c0 = cur;  // cur^(2^HI)
+#pragma unroll 1
+        for (unsigned j = 0; j < HI; j++) c0 = fe_sqr(c0);
+#pragma unroll 1
+        for (unsigned i = 0; i < LO; i++) {
+            Fe<P> y = c0;
+#pragma unroll 1
+            for (unsigned j = i + 1; j < LO; j++) y = fe_sqr(y);
+            const bool bit = !fe_eq(y, one);  // y is 1 or -1
+            c0 = fe_csel(bit, fe_mul(c0, fe_sqrt_gpow<P>(gpow, HI + i)), c0);
+            cur = fe_csel(bit, fe_mul(cur, fe_sqrt_gpow<P>(gpow, i)), cur);
+            if (i == 0)
+                odd = bit;
+            else
+                res = fe_csel(bit, fe_mul(res, fe_sqrt_gpow<P>(gpow, i - 1)), res);
+        }
+    }
+#pragma unroll 1
+    for (unsigned i = 0; i < HI; i++) {
+        Fe<P> y = cur;
+#pragma unroll 1
+        for (unsigned j = i + 1; j < HI; j++) y = fe_sqr(y);
+        const bool bit = !fe_eq(y, one);
+        cur = fe_csel(bit, fe_mul(cur, fe_sqrt_gpow<P>(gpow, LO + i)), cur);
+        if (LO + i == 0)
+            odd = bit;
+        else
+            res = fe_csel(bit, fe_mul(res, fe_sqrt_gpow<P>(gpow, LO + i - 1)), res);
+    }
+    root = res;
+    return !odd || fe_is_zero(u);
+}
+// g^(2^i), i <= S, 8 Montgomery limbs each: made once per field
+template <class P>
+inline const uint32_t* h_sqrt_table() {
+    static const std::vector<uint32_t> tbl = [] {
+        std::vector<uint32_t> t((FieldInfo<P>::S + 1) * 8);
+        Fe<P> g = h_root_of_unity<P>();
+        for (unsigned i = 0; i <= FieldInfo<P>::S; i++) {
+            memcpy(&t[8 * i], g.l, 32);
+            g = fe_sqr(g);
+        }
+        return t;
+    }();
+    return tbl.data();
+}
+// square root with the root choice above; false if a is a non-residue
 template <class P>
 inline bool h_sqrt(const Fe<P>& a, Fe<P>& out) {
-    if (fe_is_zero(a)) {
-        out = a;
-        return true;
-    }
-    constexpr unsigned S = FieldInfo<P>::S;
-    uint32_t t[8], t1h[8];
-    h_pm1_shr<P>(S, t);          // t = (p - 1) / 2^S, odd
-    h_pm1_shr<P>(S + 1, t1h);    // (t + 1) / 2 = (t >> 1) + 1
-    for (int i = 0; i < 8 && ++t1h[i] == 0; i++) {
-    }
-    Fe<P> zgen = fe_pow(fe_from_u32<P>(FieldInfo<P>::gen), t);
-    Fe<P> x = fe_pow(a, t1h), b = fe_pow(a, t);
-    const Fe<P> one = fe_one<P>();
-    unsigned m = S;
-    while (!fe_eq(b, one)) {
-        unsigned i = 0;
-        Fe<P> b2 = b;
-        while (!fe_eq(b2, one)) {
-            b2 = fe_sqr(b2);
-            i++;
-            if (i >= m) return false;  // not a square
-        }
-        Fe<P> w = zgen;
-        for (unsigned k = 0; k + i + 1 < m; k++) w = fe_sqr(w);
-        zgen = fe_sqr(w);
-        x = fe_mul(x, w);
-        b = fe_mul(b, zgen);
-        m = i;
-    }
-    out = x;
-    return fe_eq(fe_sqr(x), a);
+    Fe<P> r;
+    if (!fe_sqrt_ct(a, h_sqrt_table<P>(), r)) return false;
+    out = r;
+    return true;
 }
 
 // ---------------------------------------------------------------------------

@@ -237,6 +237,20 @@ int bzh_pk_lookup_selected(bzh_pk* pk, int* where) {
     return BZH_OK;
 }
 
+int bzh_pk_verify_select(bzh_pk* pk, int where) {
+    if (!pk || (where != BZH_VERIFY_POINTS_HOST && where != BZH_VERIFY_POINTS_DEVICE)) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(pk->mu);
+    pk->vp_select = where;
+    return BZH_OK;
+}
+
+int bzh_pk_verify_selected(bzh_pk* pk, int* where) {
+    if (!pk) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(pk->mu);
+    if (where) *where = pk->vp_select;
+    return BZH_OK;
+}
+
 int bzh_pk_set_quotient_module(bzh_ctx* ctx, bzh_pk* pk, const void* code_object, size_t len) {
     if (!ctx || !pk || pk->device != ctx->device) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);

@@ -53,6 +53,8 @@ struct bzh_pk {
     hipFunction_t q_fn = nullptr;
     int q_select = BZH_QUOTIENT_INTERPRETER;
     int lk_select = BZH_LOOKUP_HOST;   // BZH_LOOKUP_*: where the lookup argument's columns are permuted (bzh_pk_lookup_select)
+    int vp_select = BZH_VERIFY_POINTS_HOST;   // BZH_VERIFY_POINTS_*: where bzh_verify_batch decompresses the proofs' points (bzh_pk_verify_select)
+    std::vector<uint32_t> vp_offsets;         // byte offset of every point of a proof, in read order (verify_point_offsets; made on first use)
     // multiopen structure: rotation sets and the commitments grouped under each
     std::vector<std::vector<int>> rot_sets;
     std::vector<std::vector<uint64_t>> groups;

@@ -43,10 +43,47 @@ static Fe<SF> cx_eval(const bzh_pk& pk, int i, const std::vector<Fe<SF>>& adv, c
     }
 }
 
+// Byte offsets of the points of a proof, in the order verify_host reads them.  They depend on the key only: the counts below
+// are the ones verify_host reads with, and its read_point checks every offset it arrives at against this list.
+static std::vector<uint32_t> verify_point_offsets(const bzh_pk& pk) {
+    std::vector<uint32_t> offs;
+    size_t off = 0;
+    auto points = [&](size_t c) {
+        for (; c; c--, off += 32) offs.push_back((uint32_t)off);
+    };
+    auto scalars = [&](size_t c) { off += 32 * c; };
+    const size_t nl = (size_t)pk.nl, nsets = (size_t)pk.nsets;
+    points((size_t)pk.na);          // advice
+    points(2 * nl);                 // permuted lookup inputs and tables
+    points(nsets);                  // permutation products
+    points(nl);                     // lookup products
+    points(1);                      // the vanishing argument's random polynomial
+    points((size_t)pk.npieces);     // h pieces
+    scalars(pk.instance_queries.size() + pk.advice_queries.size() + pk.fixed_queries.size() + 1 + pk.perm_columns.size());
+    scalars(nsets ? 3 * nsets - 1 : 0);
+    scalars(5 * nl);
+    points(1);                      // multiopen: f
+    scalars(pk.rot_sets.size());
+    points(1);                      // the opening's S
+    points(2 * (size_t)pk.k);       // L_j, R_j
+    return offs;
+}
+// the points of one proof decoded ahead of the host pass (BZH_VERIFY_POINTS_DEVICE): affine canonical, one BZH_POINT_* each
+struct PrePoints {
+    const uint32_t* offsets = nullptr;
+    size_t count = 0;
+    const uint64_t* xy = nullptr;
+    const uint8_t* status = nullptr;
+};
+// wall time a host pass spent decompressing points / in all (BZH_PROVE_TRACE only)
+struct HostPassTimes {
+    double decompress_ms = 0, total_ms = 0;
+};
+
 // host pass over one proof; inst_xy: this proof's instance commitments.  Returns false on any malformed input.
 template <class C>
 static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t* proof, size_t len, size_t nl_cap,
-                        ProofView<C>& out) {
+                        ProofView<C>& out, const PrePoints* pre = nullptr, HostPassTimes* times = nullptr) {
     using SF = typename CurveInfo<C>::SF;
     const int na = pk.na, ni = pk.ni, nsets = pk.nsets, nl = pk.nl, npieces = pk.npieces;
     const size_t n = pk.n, m = pk.perm_columns.size();
@@ -64,7 +101,22 @@ static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t
     auto read_point = [&]() -> size_t {  // index into pts (units of 8 u64)
         const size_t idx = pts.size() / 8;
         pts.resize(pts.size() + 8, 0);
-        if (off + 32 > len || !point_decompress(C::id, proof + off, &pts[idx * 8])) {
+        if (off + 32 > len) {
+            bad = true;
+            return idx;
+        }
+        bool ok;
+        if (pre && idx < pre->count && pre->offsets[idx] == off) {   // decoded on the device; INVALID and IDENTITY leave zeros
+            ok = pre->status[idx] == BZH_POINT_OK;
+            if (ok) memcpy(&pts[idx * 8], pre->xy + idx * 8, 64);
+        } else if (times) {
+            const auto t0 = std::chrono::steady_clock::now();
+            ok = point_decompress(C::id, proof + off, &pts[idx * 8]);
+            times->decompress_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        } else {
+            ok = point_decompress(C::id, proof + off, &pts[idx * 8]);
+        }
+        if (!ok) {
             bad = true;
             return idx;
         }
@@ -399,6 +451,54 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
             pk->vk_ready = true;
         }
     }
+    // BZH_PROVE_TRACE=1: where the call's wall time goes, on stderr (tools/ubench_verify_points.py reads these lines)
+    const bool trace = getenv("BZH_PROVE_TRACE") != nullptr;
+    auto t_last = std::chrono::steady_clock::now();
+    auto mark = [&](const char* name) {
+        if (!trace) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[bzh_verify_batch] %-22s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(now - t_last).count());
+        t_last = now;
+    };
+    // BZH_VERIFY_POINTS_DEVICE: the 32-byte strings of every point of every proof, gathered by the key's offset list, go up in
+    // one copy and through one k_decompress launch; points and statuses come back with the instance commitments' read-back.
+    std::vector<uint32_t> vp_offs;
+    {
+        std::lock_guard<std::mutex> lkv(pk->mu);
+        if (pk->vp_select == BZH_VERIFY_POINTS_DEVICE) {
+            if (pk->vp_offsets.empty()) pk->vp_offsets = verify_point_offsets(*pk);
+            vp_offs = pk->vp_offsets;
+        }
+    }
+    const size_t np = vp_offs.size(), np_all = B * np, np_pad = (np_all + 15) & ~(size_t)15;
+    std::vector<uint64_t> pre_xy;
+    std::vector<uint8_t> pre_st;
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    if (np) {
+        uint32_t* d_in = (uint32_t*)arena.alloc(np_all * 32);
+        uint32_t* d_xy = (uint32_t*)arena.alloc(np_all * 64);
+        uint8_t* d_st = (uint8_t*)arena.alloc(np_pad);
+        if (!d_in || !d_xy || !d_st) return BZH_E_OOM;
+        char* slot = nullptr;
+        BZH_TRY(h2d_stage(ctx, np_all * 32, &slot));
+        for (size_t b = 0; b < B; b++)
+            for (size_t i = 0; i < np; i++) {
+                char* dst = slot + (b * np + i) * 32;
+                if ((size_t)vp_offs[i] + 32 <= proof_lens[b])
+                    memcpy(dst, proofs + b * proof_stride + vp_offs[i], 32);
+                else
+                    memset(dst, 0, 32);   // past the end of a short proof: marked invalid below
+            }
+        BZH_TRY(h2d_commit(ctx, d_in, slot, np_all * 32));
+        if (trace && hipEventCreate(&ev_a) == hipSuccess && hipEventCreate(&ev_b) == hipSuccess) (void)hipEventRecord(ev_a, ctx->stream);
+        BZH_TRY(decompress_run(ctx, C::id, d_in, np_all, BZH_FORM_CANONICAL, d_xy, d_st));
+        if (ev_b) (void)hipEventRecord(ev_b, ctx->stream);
+        pre_xy.resize(np_all * 8);
+        pre_st.resize(np_pad);
+        BZH_TRY(d2h_async(ctx, pre_xy.data(), d_xy, np_all * 64));
+        BZH_TRY(d2h_async(ctx, pre_st.data(), d_st, np_pad));
+        mark("vp:stage+launch");
+    }
     // instance commitments of the whole batch (the verifier recomputes them, as upstream does for IPA)
     std::vector<uint64_t> inst_xy(B * std::max(ni, 1) * 8, 0);
     if (ni) {
@@ -418,19 +518,47 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
         blinds.assign(B * ni, fe_one<SF>());
         BZH_TRY(pv.commit(inst_polys, n, B * ni, blinds, inst_xy));
     }
+    mark("instance commitments");
+    if (np) {
+        BZH_TRY(d2h_finish(ctx));   // (already landed when a commitment was read back)
+        for (size_t b = 0; b < B; b++)
+            for (size_t i = 0; i < np; i++)
+                if ((size_t)vp_offs[i] + 32 > proof_lens[b]) pre_st[b * np + i] = BZH_POINT_INVALID;
+        if (ev_b) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ev_a, ev_b) == hipSuccess)
+                fprintf(stderr, "[bzh_verify_batch] %-22s %8.3f ms  (%zu points)\n", "vp:k_decompress", (double)ms, np_all);
+        }
+        if (ev_a) (void)hipEventDestroy(ev_a);
+        if (ev_b) (void)hipEventDestroy(ev_b);
+        mark("vp:read-back");
+    }
     // host pass, one thread per proof
     const size_t ncommit = (size_t)pk->na + 3 * pk->nl + pk->nsets + 1 + pk->npieces + 1 + pk->nf + pk->perm_columns.size() + ni;
     const size_t nl_cap = ncommit + 2 * (size_t)pk->k + 1 + 3 + 4;
     std::vector<ProofView<C>> views(B);
     {
         const size_t nthreads = std::min<size_t>({B, (size_t)host_thread_budget(), (size_t)32});
+        std::vector<HostPassTimes> times(trace ? nthreads : 0);
         std::vector<std::thread> th;
         for (size_t t = 0; t < nthreads; t++)
             th.emplace_back([&, t]() {
-                for (size_t b = t; b < B; b += nthreads)
-                    verify_host<C>(*pk, &inst_xy[b * std::max(ni, 1) * 8], proofs + b * proof_stride, proof_lens[b], nl_cap, views[b]);
+                const auto t0 = std::chrono::steady_clock::now();
+                for (size_t b = t; b < B; b += nthreads) {
+                    PrePoints pre{vp_offs.data(), np, np ? &pre_xy[b * np * 8] : nullptr, np ? &pre_st[b * np] : nullptr};
+                    verify_host<C>(*pk, &inst_xy[b * std::max(ni, 1) * 8], proofs + b * proof_stride, proof_lens[b], nl_cap, views[b],
+                                   np ? &pre : nullptr, trace ? &times[t] : nullptr);
+                }
+                if (trace) times[t].total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             });
         for (auto& t : th) t.join();
+        if (trace) {   // thread-summed split of the host pass: point decompression against everything else
+            double dec = 0, tot = 0;
+            for (auto& t : times) dec += t.decompress_ms, tot += t.total_ms;
+            fprintf(stderr, "[bzh_verify_batch] %-22s %8.3f ms  (sum over %zu threads)\n", "vp:host decompress", dec, nthreads);
+            fprintf(stderr, "[bzh_verify_batch] %-22s %8.3f ms  (sum over %zu threads)\n", "vp:host rest", tot - dec, nthreads);
+        }
+        mark("host pass");
     }
     // device pass over the proofs that parsed; the others are rejected outright
     std::vector<size_t> live;
@@ -451,5 +579,6 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
     std::vector<int> ok(Bl, 0);
     BZH_TRY(ipa_check_batch(ctx, pk->srs, Bl, nl_cap, lc_pts.data(), lc_scal.data(), cu.data(), ok.data()));
     for (size_t j = 0; j < Bl; j++) results[live[j]] = ok[j];
+    mark("ipa check");
     return BZH_OK;
 }

@@ -181,6 +181,13 @@ int bzh_field_convert(bzh_ctx* ctx, int field, uint64_t* data, size_t count, int
  * The prover's random polynomials (vanishing argument, IPA s(X)) are n draws each; `mem` applies to out. */
 int bzh_random_field(bzh_ctx* ctx, int field, const uint8_t* rng_bytes, size_t count, int form, int mem, uint64_t* out);
 int bzh_batch_invert(bzh_ctx* ctx, int field, uint64_t* data, size_t count, int form, int mem);
+/* ff::Field::sqrt for `count` elements in place, one lane each (csrc/sqrt_decompress.hip).  The root is the one pasta_curves
+ * 0.4.1's `sqrt` returns: with p - 1 = 2^S T, g = gen^T and t in [0, 2^S) such that u^T g^t = 1, it is u^((T+1)/2) g^(t/2)
+ * (the same formula with the generators 7 and 3 for the two BN254 fields).  status (may be NULL): 1 = a square (zero
+ * included), 0 = not a square: that element is left as it was.  Returns BZH_OK when the call ran; with status == NULL,
+ * BZH_E_RANGE if any element was not a square.  ctx == NULL with BZH_MEM_HOST runs on the host.  With BZH_MEM_DEVICE and a
+ * status buffer the call only enqueues; otherwise it returns when the statuses are known.  Device buffers: 16-byte aligned. */
+int bzh_batch_sqrt(bzh_ctx* ctx, int field, uint64_t* data, size_t count, int form, int mem, uint8_t* status);
 int bzh_prefix_product(bzh_ctx* ctx, int field, uint64_t* data, size_t n, size_t batch, int form, int mem);
 int bzh_eval_polynomial(bzh_ctx* ctx, int field, const uint64_t* coeffs, size_t n, size_t batch, const uint64_t* xs, size_t nx,
                         int form, int mem, uint64_t* out);
@@ -358,6 +365,14 @@ int bzh_pk_quotient_selected(bzh_pk* pk, int* flavour, int* builtin_available);
 typedef enum { BZH_LOOKUP_HOST = 0, BZH_LOOKUP_DEVICE = 1 } bzh_lookup_where;
 int bzh_pk_lookup_select(bzh_pk* pk, int where);
 int bzh_pk_lookup_selected(bzh_pk* pk, int* where);
+/* Where bzh_verify_batch decompresses the points of the proofs: BZH_VERIFY_POINTS_HOST inside the per-proof host pass, one
+ * square root at a time (every new key's default); BZH_VERIFY_POINTS_DEVICE gathers the 32-byte strings of the whole batch --
+ * their offsets in a proof depend on the key only --, decompresses them in one bzh_affine_decompress launch on the ctx's
+ * stream ahead of the instance commitments, and the host pass replays the transcript over the decoded points.  Same
+ * results[] either way.  BZH_E_ARG: NULL key or an unknown value. */
+typedef enum { BZH_VERIFY_POINTS_HOST = 0, BZH_VERIFY_POINTS_DEVICE = 1 } bzh_verify_points_where;
+int bzh_pk_verify_select(bzh_pk* pk, int where);
+int bzh_pk_verify_selected(bzh_pk* pk, int* where);
 /* Host only (no ctx, no GPU): the quotient program of a circuit blob as the source text of a BUILTIN kernel (namespace
  * bzh_q_<hash> with the kernel bzh_quotient_<hash> and a host function `launch`), and the program hash.  This is what the
  * build-time generator calls; BZH_E_RANGE if the circuit does not fit the evaluator (such circuits use the VM v1 fold). */
@@ -504,6 +519,13 @@ int bzh_jacobian_sum(int curve, const uint64_t* xyz, size_t n, int form, uint64_
 /* pasta_curves to_bytes: x little-endian, bit 255 = parity of canonical y, identity = 32 zero bytes.
  * xy in `form`; out: n * 32 bytes. */
 int bzh_affine_compress(int curve, const uint64_t* xy, size_t n, int form, uint8_t* out32);
+/* pasta_curves from_bytes for n points (Blake2bRead::read_point; one lane per point on the device, csrc/sqrt_decompress.hip):
+ * in32 = n x 32 bytes, out_xy = n affine points x || y in `form`, (0,0) = identity.
+ * status (may be NULL): BZH_POINT_OK = 0, BZH_POINT_IDENTITY = 1, BZH_POINT_INVALID = 2 (x >= p, not on the curve, sign
+ * bit on the identity; out = zeros).  Same return convention as bzh_batch_sqrt.  `mem` applies to in32, out_xy, status;
+ * ctx == NULL with BZH_MEM_HOST runs on the host. */
+typedef enum { BZH_POINT_OK = 0, BZH_POINT_IDENTITY = 1, BZH_POINT_INVALID = 2 } bzh_point_status;
+int bzh_affine_decompress(bzh_ctx* ctx, int curve, const uint8_t* in32, size_t n, int form, int mem, uint64_t* out_xy, uint8_t* status);
 /* root of unity of order 2^log_n used by halo2's EvaluationDomain for this field
  * (ROOT_OF_UNITY^(2^(S-log_n))); out: 4 limbs in `form`. */
 int bzh_field_omega(int field, unsigned log_n, int form, uint64_t* out);
