@@ -1,13 +1,13 @@
 """Params::new (halo2_proofs poly::commitment::Params; benches/shot.rs:58, benches/board.rs:51) through the C ABI
-(include/bzh2.h, csrc/params.hip): hash-to-curve SRS on the host, g_lagrange by a group FFT on the device, both cached
-on disk keyed by (curve, k)."""
+(include/bzh2.h, csrc/params.hip): hash-to-curve SRS on the host -- or, opt-in, on the device (csrc/hash_to_curve.hip) --,
+g_lagrange by a group FFT on the device, both cached on disk keyed by (curve, k)."""
 from __future__ import annotations
 
 import ctypes
 
 import numpy as np
 
-from . import CURVE_PALLAS, CURVE_VESTA, Bases, BzhError, Context, limbs_to_int, load
+from . import CURVE_PALLAS, CURVE_VESTA, FORM_CANONICAL, MEM_HOST, Bases, BzhError, Context, limbs_to_int, load
 
 _VP = ctypes.c_void_p
 
@@ -23,6 +23,12 @@ def _bind():
     L.bzh_params_free.argtypes = [_VP, _VP]
     L.bzh_params_bases.argtypes = [_VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP)]
     L.bzh_params_points.argtypes = [_VP, _VP, _VP, _VP, _VP, ctypes.POINTER(ctypes.c_int)]
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    L.bzh_hash_to_curve_batch.argtypes = [_VP, ctypes.c_int, ctypes.c_char_p, _VP, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                          _VP, u8p]
+    L.bzh_map_to_curve_batch.argtypes = [_VP, ctypes.c_int, _VP, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _VP, u8p]
+    L.bzh_params_generators_device.argtypes = [_VP, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _VP]
+    L.bzh_params_create_with.argtypes = [_VP, ctypes.c_uint, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_VP)]
     L._bzh_params_bound = True
     return L
 
@@ -46,6 +52,47 @@ def generators(k: int, threads: int = 0):
     return g, (limbs_to_int(w[:4]), limbs_to_int(w[4:])), (limbs_to_int(u[:4]), limbs_to_int(u[4:]))
 
 
+GENERATORS_HOST, GENERATORS_DEVICE = 0, 1
+_GENERATORS = {"host": GENERATORS_HOST, "device": GENERATORS_DEVICE}
+
+
+def hash_to_curve_batch(ctx, curve: int, domain_prefix: str, messages, form: int = FORM_CANONICAL):
+    """CurveExt::hash_to_curve(domain_prefix)(m) for a list of equally long byte strings (bzh_hash_to_curve_batch): (xy, status)
+    -- xy (n, 8) uint64 in `form`, status (n,) uint8 of POINT_OK / POINT_IDENTITY.  ctx=None runs on the host, a Context on its
+    device."""
+    messages = list(messages)
+    n = len(messages)
+    msg_len = len(messages[0]) if n else 0
+    if any(len(m) != msg_len for m in messages):
+        raise ValueError("hash_to_curve_batch: the messages of one call have one length")
+    buf = np.frombuffer(b"".join(messages), dtype=np.uint8).copy() if n * msg_len else np.zeros(1, dtype=np.uint8)
+    out, st = np.zeros((n, 8), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+    rc = _bind().bzh_hash_to_curve_batch(ctx.handle if ctx is not None else None, curve, domain_prefix.encode(), _VP(buf.ctypes.data), msg_len, n,
+                                         form, MEM_HOST, _VP(out.ctypes.data), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    if rc:
+        raise BzhError(rc, "bzh_hash_to_curve_batch")
+    return out, st
+
+
+def map_to_curve_batch(ctx, curve: int, u_pairs, form: int = FORM_CANONICAL):
+    """iso_map(swu(u0) + swu(u1)) for an (n, 8) uint64 array of pairs u0 || u1 in `form` (bzh_map_to_curve_batch): (xy, status)."""
+    u = np.ascontiguousarray(u_pairs, dtype=np.uint64).reshape(-1, 8)
+    n = u.shape[0]
+    out, st = np.zeros((n, 8), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+    rc = _bind().bzh_map_to_curve_batch(ctx.handle if ctx is not None else None, curve, _VP(u.ctypes.data), n, form, MEM_HOST,
+                                        _VP(out.ctypes.data), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    if rc:
+        raise BzhError(rc, "bzh_map_to_curve_batch")
+    return out, st
+
+
+def generators_device(ctx: Context, first: int, count: int, form: int = FORM_CANONICAL) -> np.ndarray:
+    """g[first : first + count] of Params::new made on the device (bzh_params_generators_device): (count, 8) uint64 in `form`."""
+    out = np.zeros((count, 8), dtype=np.uint64)
+    ctx._check(_bind().bzh_params_generators_device(ctx.handle, first, count, form, MEM_HOST, _VP(out.ctypes.data)), "bzh_params_generators_device")
+    return out
+
+
 def group_ifft(ctx: Context, g: np.ndarray) -> np.ndarray:
     g = np.ascontiguousarray(g, dtype=np.uint64)
     n = g.shape[0]
@@ -58,11 +105,14 @@ def group_ifft(ctx: Context, g: np.ndarray) -> np.ndarray:
 class Params:
     """Params::<vesta::Affine>::new(k): the two commitment-base tables live on the device."""
 
-    def __init__(self, ctx: Context, k: int, cache_dir: str | None = None, window_bits: int = 0):
+    def __init__(self, ctx: Context, k: int, cache_dir: str | None = None, window_bits: int = 0, generators: str = "host"):
+        """generators: who makes g on a cache miss -- "host" (threads) or "device" (csrc/hash_to_curve.hip); the same points."""
         L = _bind()
         h = _VP()
-        ctx._check(L.bzh_params_create(ctx.handle, k, None if cache_dir is None else cache_dir.encode(), window_bits, ctypes.byref(h)),
-                   "bzh_params_create")
+        if generators not in _GENERATORS:
+            raise ValueError("Params: generators is 'host' or 'device'")
+        ctx._check(L.bzh_params_create_with(ctx.handle, k, None if cache_dir is None else cache_dir.encode(), window_bits,
+                                            _GENERATORS[generators], ctypes.byref(h)), "bzh_params_create_with")
         self.ctx, self.handle, self.k, self.n = ctx, h, k, 1 << k
         g, gl = _VP(), _VP()
         L.bzh_params_bases(h, ctypes.byref(g), ctypes.byref(gl))

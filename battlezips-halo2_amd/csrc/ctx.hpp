@@ -336,5 +336,11 @@ bool point_decompress(int curve, const uint8_t* in, uint64_t* xy_canonical);
 // BZH_POINT_* byte each; zeros unless BZH_POINT_OK.
 int batch_sqrt_run(bzh_ctx* ctx, int field, uint32_t* d_data, size_t count, int form, uint8_t* d_status);
 int decompress_run(bzh_ctx* ctx, int curve, const uint32_t* d_in, size_t n, int form, uint32_t* d_out_xy, uint8_t* d_status);
+// hash_to_curve.hip: Params::new's g[first .. first + count) as Montgomery affine points and one BZH_POINT_* byte each, into device
+// memory (16-byte aligned); enqueues only, the caller holds ctx->mu.  ev: null, or three events recorded before k_hash_to_field,
+// between the two kernels and after k_map_to_curve.
+int h2c_generators_run(bzh_ctx* ctx, uint32_t first, size_t count, uint32_t* d_out_xy, uint8_t* d_status, hipEvent_t* ev = nullptr);
+// params.hip: the iso-curve and isogeny constants of hash_to_curve (Pallas / Vesta), canonical limbs: A, B, Z, x0, t, u, 1/9, 1/27
+int h2c_iso_constants(int curve, uint64_t out[8][4]);
 
 }  // namespace bzh

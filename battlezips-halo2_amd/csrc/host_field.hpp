@@ -223,7 +223,8 @@ BZH_HD Fe<P> fe_sqrt_gpow(const uint32_t* gpow, unsigned i) {
     for (int k = 0; k < 8; k++) r.l[k] = gpow[8 * i + k];
     return r;
 }
-// false: u is not a square (root is then unspecified).  Zero maps to zero.
+// false: u is not a square; root then holds r with r^2 = u / g (g = gpow[0]), which csrc/hash_to_curve.hpp's map uses.
+// Zero maps to zero.
 template <class P>
 BZH_HD bool fe_sqrt_ct(const Fe<P>& u, const uint32_t* gpow, Fe<P>& root) {
     constexpr unsigned S = FieldInfo<P>::S, LO = S / 2, HI = S - LO;

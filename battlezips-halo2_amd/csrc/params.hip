@@ -18,6 +18,7 @@
 #include <unistd.h>
 
 #include <atomic>
+#include <chrono>
 #include <cstdio>
 #include <memory>
 #include <string>
@@ -284,6 +285,24 @@ static std::string default_cache_dir() {
 
 }  // namespace
 
+namespace bzh {
+// the iso-curve and isogeny constants of hash_to_curve for csrc/hash_to_curve.hip, canonical limbs: A, B, Z, x0, t, u, 1/9, 1/27;
+// BZH_E_HIP if Iso<F>'s self-check fails
+template <class F>
+static int iso_constants_t(uint64_t out[8][4]) {
+    const Iso<F>& I = iso<F>();
+    if (!I.ok) return BZH_E_HIP;
+    const F* v[8] = {&I.a, &I.b, &I.z, &I.x0, &I.t, &I.u, &I.s2, &I.s3};
+    for (int i = 0; i < 8; i++) v[i]->to_limbs(out[i]);
+    return BZH_OK;
+}
+int h2c_iso_constants(int curve, uint64_t out[8][4]) {
+    if (curve == BZH_CURVE_PALLAS) return iso_constants_t<Fp>(out);
+    if (curve == BZH_CURVE_VESTA) return iso_constants_t<Fq>(out);
+    return BZH_E_ARG;
+}
+}  // namespace bzh
+
 struct bzh_params {
     unsigned k = 0;
     size_t n = 0;
@@ -292,6 +311,124 @@ struct bzh_params {
     bzh_bases *bases = nullptr, *bases_lagrange = nullptr;   // (g | u | w) and (g_lagrange | u | w), window tables
     bool from_cache = false;
 };
+
+// the inverse group FFT of the n = 2^k Montgomery affine points at d_g (device memory, left as it is) into the host array out_xy
+// (n x 8 canonical limbs); returns once out_xy is written.  The caller holds ctx->mu.
+static int group_ifft_device(bzh_ctx* ctx, const uint32_t* d_g, unsigned k, uint64_t* out_xy) {
+    using C = VestaCurve;
+    const size_t n = (size_t)1 << k;
+    // twiddles omega^-j (j < n / 2) and the scale n^-1, canonical, computed on the host in the scalar field (Fp)
+    uint64_t wl[4];
+    int rc = bzh_field_omega(BZH_FIELD_FP, k, BZH_FORM_CANONICAL, wl);
+    if (rc) return rc;
+    Fp omega, pw = Fp::one();
+    Fp::from_limbs(wl, &omega);
+    const Fp omega_inv = omega.inv();
+    std::vector<uint64_t> tw(std::max<size_t>(n / 2, 1) * 4 + 4);
+    for (size_t j = 0; j < n / 2; j++) {
+        pw.to_limbs(&tw[4 * j]);
+        pw = pw * omega_inv;
+    }
+    Fp::from_u64((uint64_t)n).inv().to_limbs(&tw[std::max<size_t>(n / 2, 1) * 4]);
+    uint32_t *d_work = nullptr, *d_tw = nullptr, *d_out = nullptr;
+    auto cleanup = [&] {
+        if (d_work) (void)hipFree(d_work);
+        if (d_tw) (void)hipFree(d_tw);
+        if (d_out) (void)hipFree(d_out);
+    };
+    hipError_t e = hipMalloc((void**)&d_work, n * 128);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_tw, tw.size() * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, n * 64);
+    if (e != hipSuccess) {
+        cleanup();
+        return BZH_E_OOM;
+    }
+    e = hipMemcpyAsync(d_tw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) {
+        cleanup();
+        return BZH_E_HIP;
+    }
+    hipLaunchKernelGGL((k_gfft_load<C>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_g, d_work, k);
+    for (size_t m = 1; m < n; m <<= 1) {
+        const size_t stride = n / (2 * m);
+        hipLaunchKernelGGL((k_gfft_stage<C>), dim3((unsigned)((n / 2 + 63) / 64)), dim3(64), 0, ctx->stream, d_work, n, m, d_tw, stride);
+    }
+    hipLaunchKernelGGL((k_gfft_finish<C>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_work, n,
+                       d_tw + std::max<size_t>(n / 2, 1) * 8, d_out);
+    e = hipGetLastError();
+    if (e == hipSuccess) {
+        rc = field_convert(ctx, BZH_FIELD_FQ, d_out, n * 2, 0);   // coordinates: Montgomery -> canonical
+        if (rc) {
+            (void)hipStreamSynchronize(ctx->stream);
+            cleanup();
+            return rc;
+        }
+        e = hipMemcpyAsync(out_xy, d_out, n * 64, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = es;
+    cleanup();
+    if (e != hipSuccess) {
+        ctx->last_error = std::string("bzh_group_ifft: ") + hipGetErrorString(e);
+        return BZH_E_HIP;
+    }
+    return BZH_OK;
+}
+
+// Params::new's g, w, u with g made on the device (csrc/hash_to_curve.hip) and handed to the group FFT where it lies; g comes
+// to the host once, after the FFT has read it.  Fills p->g, p->g_lagrange, p->w, p->u (canonical).
+static int params_generate_device(bzh_ctx* ctx, bzh_params* p, bool trace) {
+    const size_t n = p->n;
+    uint64_t wu[16];
+    const uint8_t msgs[2] = {1, 2};
+    BZH_TRY(bzh_hash_to_curve_batch(nullptr, BZH_CURVE_VESTA, "Halo2-Parameters", msgs, 1, 2, BZH_FORM_CANONICAL, BZH_MEM_HOST, wu, nullptr));
+    memcpy(p->w, wu, 64);
+    memcpy(p->u, wu + 8, 64);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t* d_g = nullptr;
+    uint8_t* d_st = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    auto cleanup = [&] {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (d_g) (void)hipFree(d_g);
+        if (d_st) (void)hipFree(d_st);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    };
+    if (hipMalloc((void**)&d_g, n * 64) != hipSuccess || hipMalloc((void**)&d_st, (n + 15) & ~(size_t)15) != hipSuccess) {
+        cleanup();
+        return BZH_E_OOM;
+    }
+    if (trace)
+        for (hipEvent_t& e : ev)
+            if (hipEventCreate(&e) != hipSuccess) e = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = h2c_generators_run(ctx, 0, n, d_g, d_st, (ev[0] && ev[1] && ev[2]) ? ev : nullptr);
+    std::vector<uint8_t> st(n);
+    if (!rc && hipMemcpyAsync(st.data(), d_st, n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = BZH_E_HIP;
+    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = BZH_E_HIP;
+    for (size_t i = 0; !rc && i < n; i++)
+        if (st[i] != BZH_POINT_OK) rc = BZH_E_RANGE;
+    if (!rc && trace) {
+        float hf = 0, mc = 0;
+        if (ev[0] && ev[1] && ev[2]) (void)hipEventElapsedTime(&hf, ev[0], ev[1]), (void)hipEventElapsedTime(&mc, ev[1], ev[2]);
+        fprintf(stderr, "[bzh_params_create] %-22s %8.3f ms\n", "pg:k_hash_to_field", hf);
+        fprintf(stderr, "[bzh_params_create] %-22s %8.3f ms\n", "pg:k_map_to_curve", mc);
+        fprintf(stderr, "[bzh_params_create] %-22s %8.3f ms\n", "generators",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    if (!rc) rc = group_ifft_device(ctx, d_g, p->k, p->g_lagrange.data());
+    if (!rc) rc = field_convert(ctx, BZH_FIELD_FQ, d_g, n * 2, 0);   // the FFT has read g: Montgomery -> canonical in place
+    if (!rc && hipMemcpyAsync(p->g.data(), d_g, n * 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = BZH_E_HIP;
+    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = BZH_E_HIP;
+    if (!rc && trace)
+        fprintf(stderr, "[bzh_params_create] %-22s %8.3f ms\n", "group_fft",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
+    cleanup();
+    return rc;
+}
 
 extern "C" {
 
@@ -359,72 +496,17 @@ int bzh_params_generators(unsigned k, uint64_t* g_xy, uint64_t* w_xy, uint64_t* 
 // g_lagrange = inverse group FFT of g, on the device: g_xy / out_xy host arrays of n x 8 canonical limbs
 int bzh_group_ifft(bzh_ctx* ctx, int curve, const uint64_t* g_xy, unsigned k, uint64_t* out_xy) {
     if (!ctx || !g_xy || !out_xy || curve != BZH_CURVE_VESTA || k > 24) return BZH_E_ARG;
-    using C = VestaCurve;
     const size_t n = (size_t)1 << k;
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // twiddles omega^-j (j < n / 2) and the scale n^-1, canonical, computed on the host in the scalar field (Fp)
-    uint64_t wl[4];
-    int rc = bzh_field_omega(BZH_FIELD_FP, k, BZH_FORM_CANONICAL, wl);
-    if (rc) return rc;
-    Fp omega, pw = Fp::one();
-    Fp::from_limbs(wl, &omega);
-    const Fp omega_inv = omega.inv();
-    std::vector<uint64_t> tw(std::max<size_t>(n / 2, 1) * 4 + 4);
-    for (size_t j = 0; j < n / 2; j++) {
-        pw.to_limbs(&tw[4 * j]);
-        pw = pw * omega_inv;
-    }
-    Fp::from_u64((uint64_t)n).inv().to_limbs(&tw[std::max<size_t>(n / 2, 1) * 4]);
-    uint32_t *d_g = nullptr, *d_work = nullptr, *d_tw = nullptr, *d_out = nullptr;
-    auto cleanup = [&] {
-        if (d_g) (void)hipFree(d_g);
-        if (d_work) (void)hipFree(d_work);
-        if (d_tw) (void)hipFree(d_tw);
-        if (d_out) (void)hipFree(d_out);
-    };
-    hipError_t e = hipMalloc((void**)&d_g, n * 64);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_work, n * 128);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_tw, tw.size() * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, n * 64);
-    if (e != hipSuccess) {
-        cleanup();
-        return BZH_E_OOM;
-    }
-    e = hipMemcpyAsync(d_g, g_xy, n * 64, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-        cleanup();
-        return BZH_E_HIP;
-    }
-    rc = bases_to_montgomery(ctx, curve, d_g, n);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    hipLaunchKernelGGL((k_gfft_load<C>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_g, d_work, k);
-    for (size_t m = 1; m < n; m <<= 1) {
-        const size_t stride = n / (2 * m);
-        hipLaunchKernelGGL((k_gfft_stage<C>), dim3((unsigned)((n / 2 + 63) / 64)), dim3(64), 0, ctx->stream, d_work, n, m, d_tw, stride);
-    }
-    hipLaunchKernelGGL((k_gfft_finish<C>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_work, n,
-                       d_tw + std::max<size_t>(n / 2, 1) * 8, d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-        rc = field_convert(ctx, BZH_FIELD_FQ, d_out, n * 2, 0);   // coordinates: Montgomery -> canonical
-        if (rc) {
-            cleanup();
-            return rc;
-        }
-        e = hipMemcpyAsync(out_xy, d_out, n * 64, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    cleanup();
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("bzh_group_ifft: ") + hipGetErrorString(e);
-        return BZH_E_HIP;
-    }
-    return BZH_OK;
+    uint32_t* d_g = nullptr;
+    if (hipMalloc((void**)&d_g, n * 64) != hipSuccess) return BZH_E_OOM;
+    int rc = hipMemcpyAsync(d_g, g_xy, n * 64, hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? BZH_OK : BZH_E_HIP;
+    if (!rc) rc = bases_to_montgomery(ctx, curve, d_g, n);
+    if (!rc) rc = group_ifft_device(ctx, d_g, k, out_xy);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);   // a failed call may have left work that reads d_g
+    (void)hipFree(d_g);
+    return rc;
 }
 
 int bzh_params_free(bzh_ctx* ctx, bzh_params* p) {
@@ -439,8 +521,23 @@ int bzh_params_free(bzh_ctx* ctx, bzh_params* p) {
 
 // Params::new(k), cached under cache_dir (NULL: next to the library, or $BZH_CACHE_DIR; "" disables the cache);
 // uploads (g | u | w) and (g_lagrange | u | w) with window tables of `window_bits` (0: the planner's).
+// generators_where picks who makes g on a cache miss: BZH_GENERATORS_HOST (bzh_params_generators, host threads) or
+// BZH_GENERATORS_DEVICE (csrc/hash_to_curve.hip; g goes to the group FFT without a host round trip).  Same points, same cache file.
 int bzh_params_create(bzh_ctx* ctx, unsigned k, const char* cache_dir, int window_bits, bzh_params** out) {
+    return bzh_params_create_with(ctx, k, cache_dir, window_bits, BZH_GENERATORS_HOST, out);
+}
+int bzh_params_create_with(bzh_ctx* ctx, unsigned k, const char* cache_dir, int window_bits, int generators_where, bzh_params** out) {
     if (!ctx || !out || k < 1 || k > 24) return BZH_E_ARG;
+    if (generators_where != BZH_GENERATORS_HOST && generators_where != BZH_GENERATORS_DEVICE) return BZH_E_ARG;
+    // BZH_PROVE_TRACE=1: where a cache miss's wall time goes, on stderr (tools/ubench_params.py reads these lines)
+    const bool trace = getenv("BZH_PROVE_TRACE") != nullptr;
+    auto t_last = std::chrono::steady_clock::now();
+    auto mark = [&](const char* name) {
+        if (!trace) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[bzh_params_create] %-22s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(now - t_last).count());
+        t_last = now;
+    };
     std::unique_ptr<bzh_params> p(new bzh_params());
     p->k = k;
     p->n = (size_t)1 << k;
@@ -459,11 +556,20 @@ int bzh_params_create(bzh_ctx* ctx, unsigned k, const char* cache_dir, int windo
             fclose(f);
         }
     }
-    if (!loaded) {
+    mark("cache");
+    if (!loaded && generators_where == BZH_GENERATORS_DEVICE) {
+        const int rc = params_generate_device(ctx, p.get(), trace);   // prints its own marks
+        if (rc) return rc;
+        t_last = std::chrono::steady_clock::now();
+    } else if (!loaded) {
         int rc = bzh_params_generators(k, p->g.data(), p->w, p->u, 0);
         if (rc) return rc;
+        mark("generators");
         rc = bzh_group_ifft(ctx, BZH_CURVE_VESTA, p->g.data(), k, p->g_lagrange.data());
         if (rc) return rc;
+        mark("group_fft");
+    }
+    if (!loaded) {
         if (!dir.empty()) {
             mkdir(dir.c_str(), 0755);
             const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
@@ -497,6 +603,11 @@ int bzh_params_create(bzh_ctx* ctx, unsigned k, const char* cache_dir, int windo
         }
         (which ? p->bases_lagrange : p->bases) = h;
     }
+    if (trace) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    mark("tables");
     *out = p.release();
     return BZH_OK;
 }

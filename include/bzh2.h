@@ -438,6 +438,32 @@ int bzh_params_free(bzh_ctx* ctx, bzh_params* p);
 int bzh_params_bases(const bzh_params* p, bzh_bases** g, bzh_bases** g_lagrange);
 int bzh_params_points(const bzh_params* p, uint64_t* g_xy, uint64_t* g_lagrange_xy, uint64_t* w_xy, uint64_t* u_xy, int* from_cache);
 
+/* ---- batched hash-to-curve (csrc/hash_to_curve.hip): one lane per message, two kernels (expand_message_xmd over BLAKE2b,
+ * then iso_map(swu(u0) + swu(u1))) around the functions the host path runs ------------------------------------------------
+ * The conventions are bzh_affine_decompress's: `mem` applies to msgs / u01, out_xy and status; device buffers are 16-byte
+ * aligned; ctx == NULL with BZH_MEM_HOST runs on the host; with BZH_MEM_DEVICE and a status buffer the call only enqueues.
+ * out_xy: n affine points x || y in `form`.  status (may be NULL): one bzh_point_status byte per message -- BZH_POINT_IDENTITY
+ * (and zeros) for a result at infinity, else BZH_POINT_OK; with status == NULL the call returns BZH_E_RANGE if any result is the
+ * identity.  n == 0 returns BZH_OK.
+ *   bzh_hash_to_curve_batch       CurveExt::hash_to_curve(domain_prefix)(msg_i) for n messages of msg_len bytes each
+ *                                 (contiguous), Pallas or Vesta.  BZH_E_ARG: another curve, msg_len > 128, a DST
+ *                                 (prefix + "-" + curve + "_XMD:BLAKE2b_SSWU_RO_") longer than 255 bytes, n > 2^28.
+ *   bzh_map_to_curve_batch        the map alone: u01 = n x 2 base-field elements (u0 || u1, `form`).  A u that is not below p:
+ *                                 host operands are checked first (BZH_E_RANGE, nothing is written); a lane of device operands
+ *                                 gets BZH_POINT_INVALID and zeros (BZH_E_RANGE when status == NULL).
+ *   bzh_params_generators_device  g[first .. first + count) of Params::new on the device (Vesta); nothing is uploaded.
+ *                                 BZH_E_RANGE if first + count > 2^32 (the message holds the index as a u32).
+ *   bzh_params_create_with        bzh_params_create with the maker of g on a cache miss chosen: BZH_GENERATORS_HOST is
+ *                                 bzh_params_create itself; BZH_GENERATORS_DEVICE makes g with the kernels above and hands it
+ *                                 to the group FFT on the device (g is read back once).  Same points, byte-identical cache file;
+ *                                 a cache hit ignores the argument.  BZH_E_ARG for any other value. */
+int bzh_hash_to_curve_batch(bzh_ctx* ctx, int curve, const char* domain_prefix, const uint8_t* msgs, size_t msg_len, size_t n, int form,
+                            int mem, uint64_t* out_xy, uint8_t* status);
+int bzh_map_to_curve_batch(bzh_ctx* ctx, int curve, const uint64_t* u01, size_t n, int form, int mem, uint64_t* out_xy, uint8_t* status);
+int bzh_params_generators_device(bzh_ctx* ctx, size_t first, size_t count, int form, int mem, uint64_t* g_xy);
+typedef enum { BZH_GENERATORS_HOST = 0, BZH_GENERATORS_DEVICE = 1 } bzh_generators_where;
+int bzh_params_create_with(bzh_ctx* ctx, unsigned k, const char* cache_dir, int window_bits, int generators_where, bzh_params** out);
+
 /* ---- circuits: the reference's ShotCircuit / BoardCircuit as data + their witness synthesis -------------------------
  * The reference-side interface this replaces is `impl Circuit<pallas::Base> for {ShotCircuit, BoardCircuit}`
  * (src/circuits/shot.rs:22-53, src/circuits/board.rs:21-51): `configure` -> ShotChip::configure / BoardChip::configure
