@@ -363,6 +363,76 @@ def affine_decompress(curve: int, in32, form: int = FORM_CANONICAL, ctx=None, ch
     return xy, st
 
 
+EXPORTS += ["bzh_batch_normalize", "bzh_affine_compress_batch", "bzh_batch_normalize_plan"]
+
+
+def _bind_normalize():
+    L = load()
+    vp, u8p, szp = ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_size_t)
+    L.bzh_batch_normalize.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+    L.bzh_affine_compress_batch.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, vp]
+    L.bzh_batch_normalize_plan.argtypes = [ctypes.c_size_t, szp, szp]
+    return L
+
+
+def batch_normalize_plan(n: int):
+    """(lanes, chain) of the launch bzh_batch_normalize makes for n points: lane t owns the points t, t + lanes, ..., at most
+    `chain` of them (bzh_batch_normalize_plan)."""
+    lanes, chain = ctypes.c_size_t(), ctypes.c_size_t()
+    rc = _bind_normalize().bzh_batch_normalize_plan(n, ctypes.byref(lanes), ctypes.byref(chain))
+    if rc != OK:
+        raise BzhError(rc, "bzh_batch_normalize_plan")
+    return lanes.value, chain.value
+
+
+def batch_normalize(curve: int, xyz, *, ctx=None, form: int = FORM_CANONICAL, mem: int = MEM_HOST, want_xy: bool = True,
+                    want_bytes: bool = False, want_status: bool = False, n: int | None = None, out_xy: int | None = None,
+                    out32: int | None = None, status: int | None = None):
+    """Curve::batch_normalize and to_bytes for Jacobian points in `form` (bzh_batch_normalize); ctx None: on the host.
+    MEM_HOST: xyz is an (n, 12) uint64 array; returns (xy, enc, status) -- xy (n, 8) uint64 in `form`, enc (n, 32) uint8, status
+    (n,) uint8 of POINT_OK / POINT_IDENTITY (zeros) --, None for what was not wanted.  A canonical coordinate that is not below p
+    raises BzhError E_RANGE before anything is computed (host operands are checked first).
+    MEM_DEVICE: xyz, out_xy, out32 and status are device pointers (ints, 16-byte aligned; out_xy or out32 may be None) and n the
+    number of points; with a status pointer the call only enqueues on the ctx's stream (ctx.sync()).  Returns None."""
+    L = _bind_normalize()
+    h = ctx.handle if ctx is not None else None
+    if mem == MEM_DEVICE:
+        assert n is not None
+        rc = L.bzh_batch_normalize(h, curve, ctypes.c_void_p(int(xyz)), n, form, mem, ctypes.c_void_p(out_xy) if out_xy else None,
+                                   ctypes.c_void_p(out32) if out32 else None, ctypes.c_void_p(status) if status else None)
+        if rc != OK:
+            raise BzhError(rc, "bzh_batch_normalize", load().bzh_last_error(h).decode() if h else "")
+        return None
+    a = np.ascontiguousarray(xyz, dtype=np.uint64).reshape(-1, 12)
+    cnt = a.shape[0]
+    xy = np.zeros((cnt, 8), dtype=np.uint64) if want_xy else None
+    enc = np.zeros((cnt, 32), dtype=np.uint8) if want_bytes else None
+    st = np.zeros(cnt, dtype=np.uint8) if want_status else None
+    rc = L.bzh_batch_normalize(h, curve, _vp(a), cnt, form, mem, *(None if o is None else _vp(o) for o in (xy, enc, st)))
+    if rc != OK:
+        raise BzhError(rc, "bzh_batch_normalize", load().bzh_last_error(h).decode() if h else "")
+    return xy, enc, st
+
+
+def affine_compress_batch(curve: int, xy, *, ctx=None, form: int = FORM_CANONICAL, mem: int = MEM_HOST, n: int | None = None,
+                          out32: int | None = None):
+    """to_bytes for affine points in `form` (bzh_affine_compress_batch): an (n, 32) uint8 array; ctx None: on the host.
+    MEM_DEVICE: xy and out32 are device pointers (ints, 16-byte aligned), n the number of points; enqueues only, returns None."""
+    L = _bind_normalize()
+    h = ctx.handle if ctx is not None else None
+    if mem == MEM_DEVICE:
+        assert n is not None
+        rc = L.bzh_affine_compress_batch(h, curve, ctypes.c_void_p(int(xy)), n, form, mem, ctypes.c_void_p(out32) if out32 else None)
+        enc = None
+    else:
+        a = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, 8)
+        enc = np.zeros((a.shape[0], 32), dtype=np.uint8)
+        rc = L.bzh_affine_compress_batch(h, curve, _vp(a), a.shape[0], form, mem, _vp(enc))
+    if rc != OK:
+        raise BzhError(rc, "bzh_affine_compress_batch", load().bzh_last_error(h).decode() if h else "")
+    return enc
+
+
 def field_omega(field: int, log_n: int, form: int = FORM_CANONICAL) -> np.ndarray:
     out = np.zeros(4, dtype=np.uint64)
     rc = load().bzh_field_omega(field, log_n, form, _u64(out))

@@ -552,6 +552,31 @@ int bzh_affine_compress(int curve, const uint64_t* xy, size_t n, int form, uint8
  * ctx == NULL with BZH_MEM_HOST runs on the host. */
 typedef enum { BZH_POINT_OK = 0, BZH_POINT_IDENTITY = 1, BZH_POINT_INVALID = 2 } bzh_point_status;
 int bzh_affine_decompress(bzh_ctx* ctx, int curve, const uint8_t* in32, size_t n, int form, int mem, uint64_t* out_xy, uint8_t* status);
+/* ---- Curve::batch_normalize / to_affine and GroupEncoding::to_bytes on the device (csrc/normalize_compress.hip): the
+ * outbound twin of bzh_affine_decompress, for the Jacobian points bzh_msm leaves in HBM -------------------------------
+ * The conventions are bzh_affine_decompress's: `mem` applies to every buffer of the call; device buffers are 16-byte
+ * aligned; ctx == NULL with BZH_MEM_HOST runs the same chain code on the host; with BZH_MEM_DEVICE and a status buffer the
+ * call only enqueues on the ctx's stream, otherwise it returns when the statuses are known.  n == 0 returns BZH_OK.
+ *   bzh_batch_normalize        n Jacobian points (X || Y || Z, 12 limbs, `form`) -> out_xy (n x 8 limbs, `form`) and / or
+ *                              out32 (n x 32 bytes, the to_bytes encoding bzh_affine_compress writes); either may be NULL, not
+ *                              both.  One launch: Montgomery's trick over the chain a lane owns (bzh_batch_normalize_plan),
+ *                              one inversion per lane.  status (may be NULL): one bzh_point_status byte per point.  Z = 0 is
+ *                              an ordinary value: (0, 0), 32 zero bytes, BZH_POINT_IDENTITY -- never an error.  A canonical
+ *                              coordinate that is not below p: host operands are checked first (BZH_E_RANGE, nothing is
+ *                              written); a lane of device operands gets BZH_POINT_INVALID and zeros (BZH_E_RANGE when
+ *                              status == NULL) and leaves its neighbours alone.  Montgomery operands are taken as given
+ *                              (reduced), and points are not checked to be on the curve, as upstream.  The outputs must not
+ *                              overlap xyz (they hold the chain's running products while the launch runs).
+ *                              BZH_E_ARG: unknown curve, form or mem, both outputs NULL, xyz NULL with n > 0, n > 2^28,
+ *                              BZH_MEM_DEVICE without a ctx or with a misaligned buffer.
+ *   bzh_affine_compress_batch  to_bytes for n affine points already in `form`, wherever they live: the bytes
+ *                              bzh_affine_compress gives.  With BZH_MEM_DEVICE the call only enqueues.
+ *   bzh_batch_normalize_plan   host only: the launch shape bzh_batch_normalize uses for n points -- lane t of `lanes` owns the
+ *                              points t, t + lanes, ... (at most `chain` of them). */
+int bzh_batch_normalize(bzh_ctx* ctx, int curve, const uint64_t* xyz, size_t n, int form, int mem, uint64_t* out_xy, uint8_t* out32,
+                        uint8_t* status);
+int bzh_affine_compress_batch(bzh_ctx* ctx, int curve, const uint64_t* xy, size_t n, int form, int mem, uint8_t* out32);
+int bzh_batch_normalize_plan(size_t n, size_t* lanes, size_t* chain);
 /* root of unity of order 2^log_n used by halo2's EvaluationDomain for this field
  * (ROOT_OF_UNITY^(2^(S-log_n))); out: 4 limbs in `form`. */
 int bzh_field_omega(int field, unsigned log_n, int form, uint64_t* out);
