@@ -249,8 +249,9 @@ BZH_HD Fe29<P> fe29_from_sat_reduced(const Fe<P>& v) {
     for (int i = 0; i < 9; i++) r.l[i] = t.l[i] + (fe29_bias<P, 1>(i) - (i < 6 ? e[i] : 0u));
     return fe29_carry(r);
 }
-// carried value < 128 p -> the same residue below 2 p (carried): the bits above 2^254 fold back as -top c, plus one p so that
-// nothing goes negative.  ~45 instructions; what keeps long chains of lazy additions / biased subtractions inside the product's
+// carried value < 128 p -> the same residue below 2 p + 2^207 (carried; top limb <= 2^23): the bits above 2^254 fold back as
+// -top c, plus one p so that nothing goes negative; limbs 0..7 of a carried input hold up to 2^232 + 2^207 between them, which is
+// what can stay above 2 p.  ~45 instructions; what keeps long chains of lazy additions / biased subtractions inside the product's
 // input range.
 template <class P>
 BZH_HD Fe29<P> fe29_fold(const Fe29<P>& a) {
