@@ -611,6 +611,8 @@ class Transcript:
 EXPORTS += ["bzh_ipa_open", "bzh_ipa_open_batch", "bzh_ipa_verify"]
 EXPORTS += ["bzh_pk_create", "bzh_pk_free", "bzh_pk_set_lagrange", "bzh_pk_quotient_stats", "bzh_pk_quotient_source", "bzh_pk_set_quotient_module", "bzh_pk_info", "bzh_prove_batch", "bzh_prove_batch_seeded", "bzh_rng_expand", "bzh_verify_batch",
             "bzh_vk_digest", "bzh_pk_vk_repr"]
+EXPORTS += ["bzh_vk_create", "bzh_vk_from_pk", "bzh_vk_write", "bzh_vk_read", "bzh_vk_info", "bzh_vk_vk_repr", "bzh_vk_device_bytes",
+            "bzh_pk_device_bytes", "bzh_vk_free", "bzh_verify_batch_vk"]
 # Params::new (bzh2/params.py)
 EXPORTS += ["bzh_hash_to_curve", "bzh_params_generators", "bzh_group_ifft", "bzh_params_create", "bzh_params_free", "bzh_params_bases",
             "bzh_params_points"]
@@ -809,3 +811,11 @@ def permute_expression_pair(field: int, input_vals, table_vals, usable_rows: int
     if rc != OK:
         raise BzhError(rc, "bzh_permute_expression_pair")
     return oa, ot
+
+
+def __getattr__(name):
+    # bzh2.NativeVerifyingKey: the verifying key of bzh2.native (which imports this module, hence resolved on first use)
+    if name == "NativeVerifyingKey":
+        from .native import NativeVerifyingKey
+        return NativeVerifyingKey
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

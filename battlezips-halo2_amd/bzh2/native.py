@@ -31,6 +31,18 @@ def _bind():
                                          _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.bzh_rng_expand.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_size_t, _VP]
     L.bzh_pk_vk_repr.argtypes = [_VP, _VP, ctypes.POINTER(ctypes.c_int)]
+    szp, u32p = ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32)
+    L.bzh_vk_create.argtypes = [_VP, _VP, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_VP)]
+    L.bzh_vk_from_pk.argtypes = [_VP, _VP, ctypes.POINTER(_VP)]
+    L.bzh_vk_write.argtypes = [_VP, _VP, ctypes.c_size_t, szp]
+    L.bzh_vk_read.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_VP)]
+    L.bzh_vk_info.argtypes = [_VP, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint), u32p, u32p, u32p, szp]
+    L.bzh_vk_vk_repr.argtypes = [_VP, _VP, ctypes.POINTER(ctypes.c_int)]
+    L.bzh_vk_device_bytes.argtypes = [_VP, szp, szp]
+    L.bzh_pk_device_bytes.argtypes = [_VP, szp, szp]
+    L.bzh_vk_free.argtypes = [_VP]
+    L.bzh_verify_batch_vk.argtypes = [_VP, _VP, _VP, _VP, ctypes.c_size_t, _VP, ctypes.c_size_t, _VP, ctypes.c_size_t,
+                                      ctypes.POINTER(ctypes.c_size_t), _VP, ctypes.POINTER(ctypes.c_int)]
     L._bzh_native_bound = True
     return L
 
@@ -237,6 +249,12 @@ class NativeProvingKey:
         self.ctx._check(_bind().bzh_pk_set_lagrange(self.handle, bases_lagrange.handle if bases_lagrange is not None else None),
                         "bzh_pk_set_lagrange")
 
+    def device_bytes(self):
+        """(key_bytes, workspace_bytes): device memory the key owns for its lifetime, and the per-ctx workspaces grown so far"""
+        kb, wb = ctypes.c_size_t(), ctypes.c_size_t()
+        self.ctx._check(_bind().bzh_pk_device_bytes(self.handle, ctypes.byref(kb), ctypes.byref(wb)), "bzh_pk_device_bytes")
+        return kb.value, wb.value
+
     def close(self):
         """bzh_pk_free.  Refused (BzhError, the key stays open) while a prove / verify call on the key is still running on
         another ctx: the key's workspaces and code belong to every ctx that uses it."""
@@ -307,3 +325,100 @@ class NativeProvingKey:
                                    _VP(proofs.ctypes.data), self.max_proof_bytes, lens)
         ctx._check(rc, "bzh_prove_batch")
         return [bytes(proofs[b, :lens[b]]) for b in range(B)]
+
+
+def _check(rc: int, where: str):
+    if rc:
+        raise BzhError(rc, where)
+
+
+def _g0_u_w(params):
+    gp, _, wp, up, _ = params.points(want_lagrange=False)
+    return np.ascontiguousarray(np.stack([gp[0], np.concatenate([int_to_limbs(up[0]), int_to_limbs(up[1])]),
+                                          np.concatenate([int_to_limbs(wp[0]), int_to_limbs(wp[1])])]))
+
+
+class NativeVerifyingKey:
+    """keygen_vk / pk.get_vk() / VerifyingKey::{write, read} (bzh_vk): host memory only, tied to no ctx and no device.  Make one
+    with create, from_pk or from_bytes; verify_batch takes the ctx and the SRS it runs against."""
+
+    def __init__(self, handle):
+        self.handle = handle
+        self.p = MODULI[CURVE_SCALAR_FIELD[self.info()["curve"]]]
+
+    @classmethod
+    def create(cls, ctx: Context, params_or_bases, blob: bytes) -> "NativeVerifyingKey":
+        """keygen_vk for a circuit blob against an SRS: a bzh2.params.Params, or a Bases table (g | u | w) with its window table"""
+        bases = getattr(params_or_bases, "bases", params_or_bases)
+        h = _VP()
+        ctx._check(_bind().bzh_vk_create(ctx.handle, bases.handle, bytes(blob), len(blob), ctypes.byref(h)), "bzh_vk_create")
+        return cls(h)
+
+    @classmethod
+    def from_pk(cls, pk: NativeProvingKey, ctx: Context | None = None) -> "NativeVerifyingKey":
+        ctx = ctx or pk.ctx
+        h = _VP()
+        ctx._check(_bind().bzh_vk_from_pk(ctx.handle, pk.handle, ctypes.byref(h)), "bzh_vk_from_pk")
+        return cls(h)
+
+    @classmethod
+    def from_bytes(cls, b: bytes) -> "NativeVerifyingKey":
+        """bzh_vk_read: host only; BzhError E_ARG / E_RANGE for anything but a well-formed "BZV1" key"""
+        h = _VP()
+        _check(_bind().bzh_vk_read(bytes(b), len(b), ctypes.byref(h)), "bzh_vk_read")
+        return cls(h)
+
+    def to_bytes(self) -> bytes:
+        L = _bind()
+        n = ctypes.c_size_t()
+        _check(L.bzh_vk_write(self.handle, None, 0, ctypes.byref(n)), "bzh_vk_write")
+        buf = (ctypes.c_uint8 * n.value)()
+        _check(L.bzh_vk_write(self.handle, buf, n.value, ctypes.byref(n)), "bzh_vk_write")
+        return bytes(buf)
+
+    def info(self) -> dict:
+        curve, k, mp = ctypes.c_int(), ctypes.c_uint(), ctypes.c_size_t()
+        ni, nf, npm = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        _check(_bind().bzh_vk_info(self.handle, ctypes.byref(curve), ctypes.byref(k), ctypes.byref(ni), ctypes.byref(nf), ctypes.byref(npm),
+                                   ctypes.byref(mp)), "bzh_vk_info")
+        return {"curve": curve.value, "k": k.value, "num_instance": ni.value, "num_fixed_commitments": nf.value,
+                "num_permutation_commitments": npm.value, "max_proof_bytes": mp.value}
+
+    def vk_repr(self):
+        """(the verifying-key digest the key absorbs first, whether it is still the library's placeholder)"""
+        out, ph = (ctypes.c_uint8 * 32)(), ctypes.c_int()
+        _check(_bind().bzh_vk_vk_repr(self.handle, out, ctypes.byref(ph)), "bzh_vk_vk_repr")
+        return int.from_bytes(bytes(out), "little"), bool(ph.value)
+
+    def device_bytes(self):
+        """(key_bytes, workspace_bytes): see NativeProvingKey.device_bytes; key_bytes is 0 for a verifying key"""
+        kb, wb = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(_bind().bzh_vk_device_bytes(self.handle, ctypes.byref(kb), ctypes.byref(wb)), "bzh_vk_device_bytes")
+        return kb.value, wb.value
+
+    def verify_batch(self, ctx: Context, params, instances, proofs, lagrange: bool = True, g0_u_w=None) -> list:
+        """plonk::verify_proof(&params, &vk, ..) for each (instances[b], proofs[b]); returns a list of bools.  params: a
+        bzh2.params.Params -- with lagrange its g_lagrange table commits the instance columns -- or a Bases table (g | u | w)
+        together with g0_u_w (3 x 8 canonical limbs)."""
+        L = _bind()
+        bases = getattr(params, "bases", params)
+        lag = getattr(params, "bases_lagrange", None) if lagrange else None
+        g0 = np.ascontiguousarray(g0_u_w, dtype=np.uint64) if g0_u_w is not None else _g0_u_w(params)
+        B = len(proofs)
+        inst, rows = NativeProvingKey._instances(self, instances)
+        stride = max(max(len(pr) for pr in proofs), 1)
+        buf = np.zeros((B, stride), dtype=np.uint8)
+        lens = (ctypes.c_size_t * B)(*[len(pr) for pr in proofs])
+        for b, pr in enumerate(proofs):
+            buf[b, :len(pr)] = np.frombuffer(pr, dtype=np.uint8)
+        res = (ctypes.c_int * B)()
+        rc = L.bzh_verify_batch_vk(ctx.handle, self.handle, bases.handle, lag.handle if lag is not None else None, B, _VP(inst.ctypes.data),
+                                   rows, _VP(buf.ctypes.data), stride, lens, _VP(g0.ctypes.data), res)
+        ctx._check(rc, "bzh_verify_batch_vk")
+        return [bool(v) for v in res]
+
+    def close(self):
+        """bzh_vk_free.  Refused (BzhError, the key stays open) while a verify_batch on the key is still running."""
+        if self.handle is not None:
+            _check(_bind().bzh_vk_free(self.handle), "bzh_vk_free")
+            self.handle = None

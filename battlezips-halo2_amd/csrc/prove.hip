@@ -47,10 +47,74 @@
 extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __attribute__((weak));
 
 #include "prove_kernels.cuh"     // opens namespace bzh { namespace {
+#include "key_shape.hpp"         // what both keys share: blob reader, arena, KeyShape and its parser (host only)
 #include "quotient_program.hpp"  // the compiler (host only)
 #include "proving_key.hpp"       // closes them around the global struct bzh_pk, reopens; keygen
+#include "verifying_key.hpp"     // likewise around bzh_vk; its byte format and host-only entry points
 #include "prover.hpp"
 #include "verifier.hpp"
+
+// pk.get_vk(): the commitments to the fixed and permutation polynomials (blind 1), computed once per key
+template <class C>
+static int pk_fill_vk(bzh_ctx* ctx, bzh_pk* pk) {
+    std::lock_guard<std::mutex> lkv(pk->mu);
+    if (pk->vk_ready) return BZH_OK;
+    Arena& arena = *pk->arenas[ctx];   // (the caller made it: arena_for)
+    ColumnCommitter<C> cc(ctx, *pk, arena);
+    BZH_TRY(cc.commit(pk->srs, pk->fixed_polys, (size_t)pk->nf, pk->fixed_commitments));
+    BZH_TRY(cc.commit(pk->srs, pk->sigma_polys, pk->perm_columns.size(), pk->sigma_commitments));
+    pk->vk_ready = true;
+    return BZH_OK;
+}
+
+// keygen_vk: the host half of keygen without the quotient program, then the fixed and permutation columns -- uploaded, taken
+// to coefficients, committed with blind 1 against `srs` -- out of a workspace that is released before this returns
+template <class C>
+static int vk_create_t(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* blob, size_t len, bzh_vk** out) {
+    using SF = typename CurveInfo<C>::SF;
+    bzh_pk pk;   // host fields only: nothing below allocates into it
+    ParsedKey<SF> po;
+    BZH_TRY(pk_parse_t<C>(blob, len, pk, po, false));
+    if (srs->n != pk.n + 2 || srs->curve != C::id) return BZH_E_ARG;
+    const size_t n = pk.n, nf = (size_t)pk.nf, m = pk.perm_columns.size();
+    std::unique_ptr<bzh_vk> vk(new bzh_vk());
+    vk->shape = static_cast<const KeyShape&>(pk);
+    vk->cs = std::move(pk.cs_bytes);
+    Arena arena;
+    arena.device = ctx->device;
+    struct Release {
+        bzh_ctx* ctx;
+        Arena& a;
+        ~Release() {
+            (void)hipStreamSynchronize(ctx->stream);
+            a.release();
+        }
+    } release{ctx, arena};
+    ColumnCommitter<C> cc(ctx, vk->shape, arena);
+    auto commit_columns = [&](const std::vector<Fe<SF>>& host, size_t count, std::vector<uint64_t>& xy) -> int {
+        xy.clear();
+        if (!count) return BZH_OK;
+        ArenaScope scope(arena);
+        uint32_t* lag = cc.dalloc(count * n);
+        uint32_t* polys = cc.dalloc(count * n);
+        if (!lag || !polys) return BZH_E_OOM;
+        for (size_t c = 0; c < count; c++) BZH_TRY(cc.upload(lag + c * n * 8, host.data() + c * n, n));   // column by column: the staging buffer stays small
+        BZH_TRY(cc.to_coeff(polys, lag, count));
+        return cc.commit(srs, polys, count, xy);
+    };
+    BZH_TRY(commit_columns(po.fixed_h, nf, vk->shape.fixed_commitments));
+    {   // the permutation polynomials' values: column j, row r -> delta^(column) omega^(row) of the cell the cycle maps it to
+        std::vector<Fe<SF>> wp(n), dpow(m ? m : 1), host(m * n);
+        wp[0] = fe_one<SF>();
+        for (size_t i = 1; i < n; i++) wp[i] = fe_mul(wp[i - 1], po.omega);
+        dpow[0] = fe_one<SF>();
+        for (size_t j = 1; j < m; j++) dpow[j] = fe_mul(dpow[j - 1], po.delta);
+        for (size_t i = 0; i < m * n; i++) host[i] = fe_mul(dpow[po.map_c[i]], wp[po.map_r[i]]);
+        BZH_TRY(commit_columns(host, m, vk->shape.sigma_commitments));
+    }
+    *out = vk.release();
+    return BZH_OK;
+}
 
 }  // namespace
 }  // namespace bzh
@@ -92,6 +156,39 @@ static int quotient_histogram_t(const uint8_t* circuit, size_t circuit_len, uint
 }  // namespace
 
 
+namespace {
+// one prove / verify call on a key (bzh_pk or bzh_vk): counted for the whole call, so that bzh_pk_set_quotient_module /
+// bzh_pk_free / bzh_vk_free can refuse
+template <class Key>
+struct KeyCallOf {
+    Key* pk;
+    explicit KeyCallOf(Key* p) : pk(p) {
+        std::lock_guard<std::mutex> lk(pk->mu);
+        pk->calls_in_flight++;
+    }
+    ~KeyCallOf() {
+        std::lock_guard<std::mutex> lk(pk->mu);
+        pk->calls_in_flight--;
+    }
+};
+using KeyCall = KeyCallOf<bzh_pk>;
+
+// G_0, U, W of a table (g | u | w), canonical affine: row 0 of a window table is the raw table
+static int srs_g0_u_w(bzh_ctx* ctx, const bzh_bases* srs, std::vector<uint64_t>& canon) {
+    uint64_t m[3 * 8];
+    const size_t idx[3] = {0, srs->n - 2, srs->n - 1};
+    for (int i = 0; i < 3; i++)
+        BZH_HIP_TRY(ctx, hipMemcpyAsync(&m[i * 8], srs->d_xy + idx[i] * 16, 64, hipMemcpyDeviceToHost, ctx->stream));
+    BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    canon.assign(24, 0);
+    return bzh::with_pasta_curve(srs->curve, [&](auto c) {
+        using PB = typename decltype(c)::Base;
+        for (int i = 0; i < 6; i++) bzh::fe_to_u64<PB>(&canon[i * 4], bzh::fe_from_u64<PB>(&m[i * 4]), BZH_FORM_CANONICAL);
+        return BZH_OK;
+    });
+}
+}  // namespace
+
 extern "C" {
 
 int bzh_pk_create(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* circuit, size_t circuit_len, bzh_pk** out) {
@@ -101,21 +198,6 @@ int bzh_pk_create(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* circuit, si
     // (not BN254: no cube root of unity in Fr's multiplicative generator convention used here)
     return bzh::with_pasta_curve(srs->curve, [&](auto c) { return bzh::pk_create_t<decltype(c)>(ctx, srs, circuit, circuit_len, out); });
 }
-
-namespace {
-// one prove / verify call on a key: counted for the whole call, so that bzh_pk_set_quotient_module / bzh_pk_free can refuse
-struct KeyCall {
-    bzh_pk* pk;
-    explicit KeyCall(bzh_pk* p) : pk(p) {
-        std::lock_guard<std::mutex> lk(pk->mu);
-        pk->calls_in_flight++;
-    }
-    ~KeyCall() {
-        std::lock_guard<std::mutex> lk(pk->mu);
-        pk->calls_in_flight--;
-    }
-};
-}  // namespace
 
 int bzh_pk_free(bzh_ctx* ctx, bzh_pk* pk) {
     if (!ctx || !pk) return BZH_E_ARG;
@@ -293,12 +375,7 @@ int bzh_pk_info(const bzh_pk* pk, size_t* rng_bytes_per_proof, size_t* max_proof
                 uint32_t* usable_rows) {
     if (!pk) return BZH_E_ARG;
     if (rng_bytes_per_proof) *rng_bytes_per_proof = pk->rng_bytes;
-    if (max_proof_bytes) {
-        const size_t points = (size_t)pk->na + 2 * pk->nl + pk->nsets + pk->nl + 1 + pk->npieces + 1 + 1 + 2 * (size_t)pk->k;
-        const size_t scalars = pk->instance_queries.size() + pk->advice_queries.size() + pk->fixed_queries.size() + 1 +
-                               pk->perm_columns.size() + 3 * (size_t)pk->nsets + 5 * (size_t)pk->nl + pk->rot_sets.size() + 2;
-        *max_proof_bytes = 32 * (points + scalars);
-    }
+    if (max_proof_bytes) *max_proof_bytes = pk->max_proof_bytes();
     if (num_advice) *num_advice = (uint32_t)pk->na;
     if (n_rows) *n_rows = (uint32_t)pk->n;
     if (usable_rows) *usable_rows = (uint32_t)pk->usable;
@@ -308,7 +385,7 @@ int bzh_pk_info(const bzh_pk* pk, size_t* rng_bytes_per_proof, size_t* max_proof
 int bzh_pk_vk_repr(const bzh_pk* pk, uint8_t* out_repr32, int* is_placeholder) {
     if (!pk) return BZH_E_ARG;
     if (out_repr32) memcpy(out_repr32, pk->vk_repr, 32);
-    if (is_placeholder) *is_placeholder = (pk->vk_repr[0] == BZH_VK_REPR_PLACEHOLDER && !pk->vk_repr[1] && !pk->vk_repr[2] && !pk->vk_repr[3]) ? 1 : 0;
+    if (is_placeholder) *is_placeholder = pk->vk_repr_is_placeholder() ? 1 : 0;
     return BZH_OK;
 }
 
@@ -325,26 +402,87 @@ int bzh_verify_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* ins
     // same SRS's, or every valid proof would be rejected without an error.  Row 0 of the window table is the raw SRS.
     std::unique_lock<std::mutex> lkp(pk->mu);
     if (pk->srs_g0_u_w.empty()) {
-        uint64_t m[3 * 8];
-        const size_t idx[3] = {0, pk->n, pk->n + 1};
-        for (int i = 0; i < 3; i++)
-            BZH_HIP_TRY(ctx, hipMemcpyAsync(&m[i * 8], pk->srs->d_xy + idx[i] * 16, 64, hipMemcpyDeviceToHost, ctx->stream));
-        BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<uint64_t> canon(24);
-        bzh::with_pasta_curve(pk->curve, [&](auto c) {
-            using PB = typename decltype(c)::Base;
-            for (int i = 0; i < 6; i++) bzh::fe_to_u64<PB>(&canon[i * 4], bzh::fe_from_u64<PB>(&m[i * 4]), BZH_FORM_CANONICAL);
-            return BZH_OK;
-        });
+        std::vector<uint64_t> canon;
+        BZH_TRY(srs_g0_u_w(ctx, pk->srs, canon));
         pk->srs_g0_u_w = std::move(canon);
     }
     if (memcmp(pk->srs_g0_u_w.data(), g0_u_w, 3 * 64) != 0) {
         ctx->last_error = "bzh_verify_batch: g0_u_w are not G_0, U, W of the SRS this key was built on";
         return BZH_E_ARG;
     }
+    const bool points_on_device = pk->vp_select == BZH_VERIFY_POINTS_DEVICE;
     lkp.unlock();
+    bzh::Arena& arena = pk->arena_for(ctx, ctx->device);
     const int rc = bzh::with_pasta_curve(pk->curve, [&](auto c) {
-        return bzh::verify_batch_t<decltype(c)>(ctx, pk, batch, instances, instance_rows, proofs, proof_stride, proof_lens, g0_u_w, results);
+        using C = decltype(c);
+        arena.reset();
+        BZH_TRY(bzh::pk_fill_vk<C>(ctx, pk));
+        return bzh::verify_batch_t<C>(ctx, *pk, pk->srs, nullptr, arena, points_on_device, batch, instances, instance_rows, proofs, proof_stride,
+                                      proof_lens, g0_u_w, results);
+    });
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
+int bzh_pk_device_bytes(const bzh_pk* pk, size_t* key_bytes, size_t* workspace_bytes) {
+    if (!pk) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(const_cast<bzh_pk*>(pk)->mu);
+    if (key_bytes) *key_bytes = pk->dev_bytes + pk->hoist_bytes + pk->key29_bytes;
+    size_t ws = 0;
+    for (auto& kv : pk->arenas) ws += kv.second->held();
+    if (workspace_bytes) *workspace_bytes = ws;
+    return BZH_OK;
+}
+
+int bzh_vk_create(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* circuit, size_t circuit_len, bzh_vk** out) {
+    if (!ctx || !srs || !circuit || !out || srs->device != ctx->device) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return bzh::with_pasta_curve(srs->curve, [&](auto c) { return bzh::vk_create_t<decltype(c)>(ctx, srs, circuit, circuit_len, out); });
+}
+
+int bzh_vk_from_pk(bzh_ctx* ctx, bzh_pk* pk, bzh_vk** out) {
+    if (!ctx || !pk || !out || pk->device != ctx->device) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KeyCall in_flight(pk);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    bzh::Arena& arena = pk->arena_for(ctx, ctx->device);
+    BZH_TRY(bzh::with_pasta_curve(pk->curve, [&](auto c) {
+        arena.reset();
+        return bzh::pk_fill_vk<decltype(c)>(ctx, pk);
+    }));
+    std::unique_ptr<bzh_vk> vk(new bzh_vk());
+    vk->shape = static_cast<const bzh::KeyShape&>(*pk);
+    vk->cs = pk->cs_bytes;
+    *out = vk.release();
+    return BZH_OK;
+}
+
+int bzh_verify_batch_vk(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch,
+                        const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
+                        const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
+    if (!ctx || !vk || !srs || !batch || batch > 4096 || !proofs || !proof_lens || !g0_u_w || !results) return BZH_E_ARG;
+    const bzh::KeyShape& key = vk->shape;
+    if (srs->device != ctx->device || srs->curve != key.curve || srs->n != key.n + 2) return BZH_E_ARG;
+    if (g_lagrange && (g_lagrange->device != ctx->device || g_lagrange->curve != key.curve || (g_lagrange->n != key.n + 2 && g_lagrange->n != key.n + 3)))
+        return BZH_E_ARG;
+    if ((key.ni && instance_rows && !instances) || instance_rows > key.usable) return BZH_E_ARG;
+    for (size_t b = 0; b < batch; b++)
+        if (proof_lens[b] > proof_stride) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KeyCallOf<const bzh_vk> in_flight(vk);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the key's commitments and G'_0 belong to one SRS: the three points the caller passes must be that table's
+    std::vector<uint64_t> canon;
+    BZH_TRY(srs_g0_u_w(ctx, srs, canon));
+    if (memcmp(canon.data(), g0_u_w, 3 * 64) != 0) {
+        ctx->last_error = "bzh_verify_batch_vk: g0_u_w are not G_0, U, W of srs";
+        return BZH_E_ARG;
+    }
+    bzh::Arena& arena = vk->arena_for(ctx, ctx->device);
+    const int rc = bzh::with_pasta_curve(key.curve, [&](auto c) {
+        return bzh::verify_batch_t<decltype(c)>(ctx, key, srs, g_lagrange, arena, false, batch, instances, instance_rows, proofs, proof_stride,
+                                                proof_lens, g0_u_w, results);
     });
     (void)hipStreamSynchronize(ctx->stream);
     return rc;

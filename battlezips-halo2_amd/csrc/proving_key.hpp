@@ -8,25 +8,17 @@
 // ---------------------------------------------------------------------------
 // the proving key
 // ---------------------------------------------------------------------------
-struct bzh_pk {
-    int curve = 0, field = 0, device = 0;
-    unsigned k = 0, ek = 0;
-    size_t n = 0, en = 0, ext = 0;
-    int na = 0, nf = 0, ni = 0, degree = 0, bf = 0, chunk_len = 0, nsets = 0, nl = 0, npieces = 0;
-    size_t usable = 0;
-    uint64_t vk_repr[4] = {0};
+// (the constraint system's shape, the multiopen structure and the vk commitments -- what the verifier reads -- are the KeyShape)
+struct bzh_pk : bzh::KeyShape {
+    int device = 0;
+    size_t en = 0, ext = 0;
     const bzh_bases* srs = nullptr;
     std::vector<uint64_t> srs_g0_u_w;           // G_0, U, W of `srs`, canonical affine, read back once (bzh_verify_batch checks its argument against these)
     const bzh_bases* srs_lagrange = nullptr;   // (g_lagrange | u | w): Params::commit_lagrange for the columns upstream commits in that basis
-    std::vector<bzh::CNode> cx;
-    std::vector<int> gates;
-    std::vector<std::pair<int, int>> perm_columns;  // (kind tag CX_*, index)
-    std::vector<std::pair<std::vector<int>, std::vector<int>>> lookups;
-    std::vector<std::pair<int, int>> advice_queries, fixed_queries, instance_queries;
-    uint64_t omega[4], eomega[4], zeta[4];  // Montgomery limbs for ntt_run
-    uint32_t delta[8];                      // Montgomery
+    uint64_t eomega[4], zeta[4];  // Montgomery limbs for ntt_run
     // device, one allocation
     void* dev = nullptr;
+    size_t dev_bytes = 0, hoist_bytes = 0, key29_bytes = 0;   // sizes of dev / hoist / key29 (bzh_pk_device_bytes)
     uint32_t *fixed = nullptr, *fixed_polys = nullptr, *fixed_cosets = nullptr, *sigma = nullptr, *ident = nullptr, *sigma_polys = nullptr,
              *sigma_cosets = nullptr, *l0 = nullptr, *l_last = nullptr, *l_blind = nullptr, *x_col = nullptr, *tinv_col = nullptr;
     std::map<uint64_t, bzh::Program> progs;
@@ -54,10 +46,6 @@ struct bzh_pk {
     int q_select = BZH_QUOTIENT_INTERPRETER;
     int lk_select = BZH_LOOKUP_HOST;   // BZH_LOOKUP_*: where the lookup argument's columns are permuted (bzh_pk_lookup_select)
     int vp_select = BZH_VERIFY_POINTS_HOST;   // BZH_VERIFY_POINTS_*: where bzh_verify_batch decompresses the proofs' points (bzh_pk_verify_select)
-    std::vector<uint32_t> vp_offsets;         // byte offset of every point of a proof, in read order (verify_point_offsets; made on first use)
-    // multiopen structure: rotation sets and the commitments grouped under each
-    std::vector<std::vector<int>> rot_sets;
-    std::vector<std::vector<uint64_t>> groups;
     // per-call workspaces: one grow-only arena per ctx that has used the key (several worker streams share ONE key)
     std::map<const bzh_ctx*, std::unique_ptr<bzh::Arena>> arenas;
     size_t rng_bytes = 0;
@@ -65,9 +53,10 @@ struct bzh_pk {
     // bzh_pk_set_quotient_module and bzh_pk_free refuse while it is non-zero -- they unload code / free arenas that a
     // call on ANOTHER ctx may be launching from
     int calls_in_flight = 0;
-    // verifying key: commitments to the fixed and permutation polynomials (computed at the first verification)
+    // verifying key: the KeyShape's commitments to the fixed and permutation polynomials are computed at the first verification
     bool vk_ready = false;
-    std::vector<uint64_t> fixed_commitments, sigma_commitments;  // affine canonical x || y
+    // the constraint-system part of the blob the key was made from, as bzh_vk keeps it (csrc/verifying_key.hpp)
+    std::vector<uint8_t> cs_bytes;
     // The key is immutable after bzh_pk_create except for caches filled on first use (programs, hoisted columns, the vk
     // commitments, G_0/U/W, the quotient module, the arena map): `mu` guards those in short sections.  Calls through different
     // ctxs run concurrently on one key; a call holds its ctx's mutex throughout (lock order: ctx->mu, then pk->mu).
@@ -85,83 +74,6 @@ struct bzh_pk {
 
 namespace bzh {
 namespace {
-
-static int cx_degree(const bzh_pk& pk, int i) {
-    const CNode& e = pk.cx[i];
-    switch (e.tag) {
-        case CX_CONST: return 0;
-        case CX_ADVICE:
-        case CX_FIXED:
-        case CX_INSTANCE: return 1;
-        case CX_NEG:
-        case CX_SCALE: return cx_degree(pk, e.a);
-        case CX_ADD: return std::max(cx_degree(pk, e.a), cx_degree(pk, e.b));
-        default: return cx_degree(pk, e.a) + cx_degree(pk, e.b);
-    }
-}
-struct Query3 {
-    int tag, col, rot;
-    bool operator==(const Query3& o) const { return tag == o.tag && col == o.col && rot == o.rot; }
-};
-static void cx_queries(const bzh_pk& pk, int i, std::vector<Query3>& out) {
-    const CNode& e = pk.cx[i];
-    if (e.tag >= CX_ADVICE && e.tag <= CX_INSTANCE) {
-        const Query3 q{e.tag, (int)e.col, e.rot};
-        if (std::find(out.begin(), out.end(), q) == out.end()) out.push_back(q);
-    } else if (e.tag == CX_NEG || e.tag == CX_SCALE) {
-        cx_queries(pk, e.a, out);
-    } else if (e.tag == CX_ADD || e.tag == CX_MUL) {
-        cx_queries(pk, e.a, out);
-        cx_queries(pk, e.b, out);
-    }
-}
-
-template <class SF>
-static int parse_expr(Reader& r, bzh_pk& pk, int depth = 0) {
-    if (depth > 4096) {
-        r.ok = false;
-        return -1;
-    }
-    CNode nd;
-    nd.tag = r.u8();
-    if (!r.ok) return -1;
-    switch (nd.tag) {
-        case CX_CONST: {
-            const uint8_t* b = r.bytes(32);
-            if (!b) return -1;
-            const Fe<SF> v = h_from_bytes<SF>(b);
-            memcpy(nd.val, v.l, 32);
-            break;
-        }
-        case CX_ADVICE:
-        case CX_FIXED:
-        case CX_INSTANCE:
-            nd.col = r.u32();
-            nd.rot = (int32_t)r.u32();
-            if ((nd.tag == CX_ADVICE && nd.col >= (uint32_t)pk.na) || (nd.tag == CX_FIXED && nd.col >= (uint32_t)pk.nf) ||
-                (nd.tag == CX_INSTANCE && nd.col >= (uint32_t)pk.ni))
-                r.ok = false;
-            break;
-        case CX_NEG: nd.a = parse_expr<SF>(r, pk, depth + 1); break;
-        case CX_ADD:
-        case CX_MUL:
-            nd.a = parse_expr<SF>(r, pk, depth + 1);
-            nd.b = parse_expr<SF>(r, pk, depth + 1);
-            break;
-        case CX_SCALE: {
-            nd.a = parse_expr<SF>(r, pk, depth + 1);
-            const uint8_t* b = r.bytes(32);
-            if (!b) return -1;
-            const Fe<SF> v = h_from_bytes<SF>(b);
-            memcpy(nd.val, v.l, 32);
-            break;
-        }
-        default: r.ok = false;
-    }
-    if (!r.ok) return -1;
-    pk.cx.push_back(nd);
-    return (int)pk.cx.size() - 1;
-}
 
 // circuit expression -> evaluator expression over `reg` (columns looked up by (kind, index))
 static int lower(const bzh_pk& pk, int i, EPool& ep, const Cols& reg, int rot_scale) {
@@ -385,6 +297,7 @@ static int materialize_hoist(bzh_ctx* ctx, bzh_pk& pk) {
     quotient_registry(pk, QuotientPtrs{}, reg);   // hoisted programs read key-owned columns only
     const size_t ncols = reg.ptr.size();
     BZH_HIP_TRY(ctx, hipMalloc((void**)&pk.hoist, pk.hoist_cols * size * 32));
+    pk.hoist_bytes = pk.hoist_cols * size * 32;
     size_t stage_bytes = 0;
     for (const Program& pg : pk.hoist_progs)
         stage_bytes = std::max(stage_bytes, std::max<size_t>(pg.consts.size(), 1) * 32 + pg.ops.size() * sizeof(bzh_expr_op) + ncols * 16 + 1024);
@@ -422,56 +335,27 @@ struct ParsedKey {
     Fe<SF> omega, eomega, delta, zeta;
 };
 
+// The constraint-system part of a circuit blob as a blob of its own: everything up to the copy constraints, no copy
+// constraints, `nf` empty fixed columns, then the query lists -- a valid circuit blob with the same shape (csrc/verifying_key.hpp).
+static std::vector<uint8_t> constraint_system_bytes(const uint8_t* blob, size_t head_end, size_t tail_begin, size_t tail_end, int nf) {
+    std::vector<uint8_t> cs(blob, blob + head_end);
+    cs.resize(cs.size() + 4 + 4 * (size_t)nf, 0);   // u32 ncopies = 0, nf x u32 len = 0
+    cs.insert(cs.end(), blob + tail_begin, blob + tail_end);
+    return cs;
+}
+
 // keygen, host half: parse the circuit blob, derive the constraint-system shape (queries, degree, blinding factors,
-// extended domain), the permutation cycles and the multiopen structure, and compile the quotient program.  No device work:
-// this is also what the build-time kernel generator runs (bzh_quotient_source_for_circuit).
+// extended domain), the permutation cycles and the multiopen structure, and compile the quotient program (with_quotient; keygen_vk
+// does without).  No device work: this is also what the build-time kernel generator runs (bzh_quotient_source_for_circuit).
 template <class C>
-static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typename CurveInfo<C>::SF>& po) {
+static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typename CurveInfo<C>::SF>& po, bool with_quotient = true) {
     using SF = typename CurveInfo<C>::SF;
     using FM = FieldInfo<SF>;
     Reader r{blob, blob + len};
-    const uint32_t magic = r.u32();
-    if (magic != 0x31435A42u && magic != 0x32435A42u) return BZH_E_ARG;  // "BZC1" / "BZC2"
-    const bool explicit_queries = magic == 0x32435A42u;
-    pk.curve = C::id;
-    pk.field = FM::id;
-    pk.k = r.u32();
-    pk.na = (int)r.u32();
-    pk.nf = (int)r.u32();
-    pk.ni = (int)r.u32();
-    const int min_degree = (int)r.u32();
-    const uint8_t* vk = r.bytes(32);
-    if (!r.ok || pk.k < 1 || pk.k > 24 || pk.na > 4096 || pk.nf > 4096 || pk.ni > 4096) return BZH_E_ARG;
-    {   // the vk digest is a scalar of the circuit field (upstream: C::Scalar::from_bytes_wide): refuse a non-canonical one
-        uint32_t w[8];
-        memcpy(w, vk, 32);
-        bool lt = false;
-        for (int i = 7; i >= 0 && !lt; i--) {
-            if (w[i] > SF::mod(i)) return BZH_E_RANGE;
-            lt = w[i] < SF::mod(i);
-        }
-        if (!lt) return BZH_E_RANGE;
-    }
-    memcpy(pk.vk_repr, vk, 32);
-    pk.n = (size_t)1 << pk.k;
-    const uint32_t ngates = r.u32();
-    for (uint32_t g = 0; g < ngates && r.ok; g++) pk.gates.push_back(parse_expr<SF>(r, pk));
-    const uint32_t nperm = r.u32();
-    for (uint32_t j = 0; j < nperm && r.ok; j++) {
-        const int kind = r.u8() + CX_ADVICE;
-        const int idx = (int)r.u32();
-        if (kind > CX_INSTANCE || idx < 0 || idx >= (kind == CX_ADVICE ? pk.na : (kind == CX_FIXED ? pk.nf : pk.ni))) return BZH_E_ARG;
-        pk.perm_columns.push_back({kind, idx});
-    }
-    const uint32_t nlk = r.u32();
-    for (uint32_t l = 0; l < nlk && r.ok; l++) {
-        const uint32_t m = r.u32();
-        if (!m || m > 64) return BZH_E_ARG;
-        std::vector<int> ins, tabs;
-        for (uint32_t i = 0; i < m && r.ok; i++) ins.push_back(parse_expr<SF>(r, pk));
-        for (uint32_t i = 0; i < m && r.ok; i++) tabs.push_back(parse_expr<SF>(r, pk));
-        pk.lookups.push_back({ins, tabs});
-    }
+    ShapeHead head;
+    BZH_TRY(shape_parse_head<C>(r, pk, head));
+    const size_t head_end = (size_t)(r.p - blob);
+    const uint32_t nperm = head.nperm;
     const uint32_t ncopies = r.u32();
     struct Copy {
         uint32_t lc, lr, rc, rr;
@@ -494,84 +378,18 @@ static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typ
         for (uint32_t i = 0; i < fl; i++) fixed_h[(size_t)f * n + i] = h_from_bytes<SF>(b + 32 * (size_t)i);
     }
     if (!r.ok) return BZH_E_ARG;
-
-    // shape: queries, degree, blinding factors (upstream ConstraintSystem).  "BZC2" carries the query lists in
-    // upstream's registration order (a query is registered when it is made: `enable_equality` registers the column's
-    // current-row query at once, before any gate of the reference's configure functions -- src/chips/board.rs:199,217
-    // before :275); "BZC1" derives them in first-use order: gates, lookups, then the permutation columns.
-    std::vector<Query3> used, qs;
-    for (int g : pk.gates) cx_queries(pk, g, used);
-    for (auto& lk : pk.lookups) {
-        for (int e : lk.first) cx_queries(pk, e, used);
-        for (int e : lk.second) cx_queries(pk, e, used);
-    }
-    for (auto& pc : pk.perm_columns) {
-        const Query3 q{pc.first, pc.second, 0};
-        if (std::find(used.begin(), used.end(), q) == used.end()) used.push_back(q);
-    }
-    if (explicit_queries) {
-        const int tags[3] = {CX_ADVICE, CX_FIXED, CX_INSTANCE};
-        const int limits[3] = {pk.na, pk.nf, pk.ni};
-        for (int t = 0; t < 3; t++) {
-            const uint32_t nq = r.u32();
-            if (!r.ok || nq > 65536) return BZH_E_ARG;
-            for (uint32_t i = 0; i < nq && r.ok; i++) {
-                const Query3 q{tags[t], (int)r.u32(), (int)r.u32()};
-                if (q.col < 0 || q.col >= limits[t] || q.rot < -(int)n || q.rot > (int)n) return BZH_E_ARG;
-                if (std::find(qs.begin(), qs.end(), q) != qs.end()) return BZH_E_ARG;
-                qs.push_back(q);
-            }
-        }
-        if (!r.ok) return BZH_E_ARG;
-        for (auto& q : used) {   // every cell the constraint system reads must be in the lists
-            if (std::find(qs.begin(), qs.end(), q) == qs.end()) return BZH_E_ARG;
-        }
-    } else {
-        qs = used;
-    }
-    std::map<int, int> per_col;
-    for (auto& q : qs) {
-        if (q.tag == CX_ADVICE) {
-            pk.advice_queries.push_back({q.col, q.rot});
-            per_col[q.col]++;
-        } else if (q.tag == CX_FIXED) {
-            pk.fixed_queries.push_back({q.col, q.rot});
-        } else {
-            pk.instance_queries.push_back({q.col, q.rot});
-        }
-    }
-    int deg = 3;
-    for (int g : pk.gates) deg = std::max(deg, cx_degree(pk, g));
-    for (auto& lk : pk.lookups) {
-        int di = 1, dt = 1;
-        for (int e : lk.first) di = std::max(di, cx_degree(pk, e));
-        for (int e : lk.second) dt = std::max(dt, cx_degree(pk, e));
-        deg = std::max(deg, std::max(4, 2 + di + dt));
-    }
-    pk.degree = std::max(deg, min_degree);
-    int maxq = 1;
-    for (auto& kv : per_col) maxq = std::max(maxq, kv.second);
-    pk.bf = std::max(3, maxq) + 2;
-    if ((size_t)pk.bf + 2 > n) return BZH_E_ARG;
-    pk.usable = n - (size_t)(pk.bf + 1);
-    pk.chunk_len = pk.degree - 2;
-    unsigned bl = 0;
-    for (int v = pk.degree - 2; v; v >>= 1) bl++;
-    pk.ek = pk.k + std::max(1u, bl);
-    if (pk.ek > FM::S) return BZH_E_RANGE;
+    const size_t tail_begin = (size_t)(r.p - blob);
+    BZH_TRY(shape_parse_tail<C>(r, pk, head));
+    pk.cs_bytes = constraint_system_bytes(blob, head_end, tail_begin, (size_t)(r.p - blob), pk.nf);
     pk.en = (size_t)1 << pk.ek;
     pk.ext = pk.en / n;
-    pk.nl = (int)pk.lookups.size();
-    pk.nsets = nperm ? (int)((nperm + pk.chunk_len - 1) / pk.chunk_len) : 0;
-    pk.npieces = pk.degree - 1;
-    if ((size_t)pk.npieces * n > pk.en) return BZH_E_ARG;
 
     // domain constants
     const Fe<SF> gen = fe_from_u32<SF>(FM::gen);
     const Fe<SF> root = h_root_of_unity<SF>();
     const Fe<SF> omega = h_omega(root, pk.k), eomega = h_omega(root, pk.ek);
-    Fe<SF> delta = gen;  // gen^(2^S)
-    for (unsigned i = 0; i < FM::S; i++) delta = fe_sqr(delta);
+    Fe<SF> delta;
+    memcpy(delta.l, pk.delta, 32);
     Fe<SF> zeta;
     {  // g^((p-1)/3)
         uint32_t q[8];
@@ -587,10 +405,8 @@ static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typ
         if (rem) return BZH_E_RANGE;  // no cube root of unity: the coset fast path needs 3 | p - 1
         zeta = fe_pow(gen, q);
     }
-    fe_to_u64<SF>(pk.omega, omega);
     fe_to_u64<SF>(pk.eomega, eomega);
     fe_to_u64<SF>(pk.zeta, zeta);
-    memcpy(pk.delta, delta.l, 32);
     po.omega = omega, po.eomega = eomega, po.delta = delta, po.zeta = zeta;
 
     // permutation cycles (upstream permutation::keygen::Assembly::copy)
@@ -626,55 +442,6 @@ static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typ
         std::swap(map_r[li], map_r[ri]);
     }
 
-    // multiopen structure (rotations stand in for the points: distinct rotations <-> distinct points x * omega^r)
-    {
-        struct Q {
-            uint64_t cid;
-            int rot;
-        };
-        std::vector<Q> q;
-        const int last_rot = -(pk.bf + 1);
-        for (auto& a : pk.instance_queries) q.push_back({key(K_INST, a.first), a.second});
-        for (auto& a : pk.advice_queries) q.push_back({key(K_ADV, a.first), a.second});
-        for (int i = 0; i < pk.nsets; i++) {
-            q.push_back({key(K_PZ, i), 0});
-            q.push_back({key(K_PZ, i), 1});
-            if (i != pk.nsets - 1) q.push_back({key(K_PZ, i), last_rot});
-        }
-        for (int i = 0; i < pk.nl; i++) {
-            q.push_back({key(K_LZ, i), 0});
-            q.push_back({key(K_LA, i), 0});
-            q.push_back({key(K_LS, i), 0});
-            q.push_back({key(K_LA, i), -1});
-            q.push_back({key(K_LZ, i), 1});
-        }
-        for (auto& a : pk.fixed_queries) q.push_back({key(K_FIX, a.first), a.second});
-        for (size_t j = 0; j < m; j++) q.push_back({key(K_SIGMA, j), 0});
-        q.push_back({key(K_MISC, M_H0), 0});
-        q.push_back({key(K_MISC, M_F), 0});  // the random polynomial
-        std::vector<uint64_t> order;
-        std::map<uint64_t, std::vector<int>> pts_of;
-        for (auto& e2 : q) {
-            auto it = pts_of.find(e2.cid);
-            if (it == pts_of.end()) {
-                order.push_back(e2.cid);
-                it = pts_of.insert({e2.cid, {}}).first;
-            }
-            if (std::find(it->second.begin(), it->second.end(), e2.rot) == it->second.end()) it->second.push_back(e2.rot);
-        }
-        for (uint64_t cid : order) {
-            std::vector<int> ks = pts_of[cid];
-            std::sort(ks.begin(), ks.end());
-            size_t si = 0;
-            for (; si < pk.rot_sets.size(); si++)
-                if (pk.rot_sets[si] == ks) break;
-            if (si == pk.rot_sets.size()) {
-                pk.rot_sets.push_back(ks);
-                pk.groups.push_back({});
-            }
-            pk.groups[si].push_back(cid);
-        }
-    }
     // randomness per proof: blinding rows and blinds in create_proof's draw order, then the IPA opening
     {
         const size_t bf1 = (size_t)pk.bf + 1;
@@ -687,7 +454,7 @@ static int pk_parse_t(const uint8_t* blob, size_t len, bzh_pk& pk, ParsedKey<typ
         draws += n + 1 + 2 * (size_t)pk.k;
         pk.rng_bytes = draws * 64;
     }
-    compile_quotient<SF>(pk);
+    if (with_quotient) compile_quotient<SF>(pk);
     return BZH_OK;
 }
 
@@ -711,6 +478,7 @@ static int pk_create_t(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* blob, 
     const size_t en = pk.en, nf = pk.nf;
     const size_t words = (2 * nf * n + nf * en + 3 * m * n + m * en + 3 * en + 2 * en + 3 * n) * 8;
     BZH_HIP_TRY(ctx, hipMalloc(&pk.dev, words * 4 + 256));
+    pk.dev_bytes = words * 4 + 256;
     uint32_t* cur = (uint32_t*)pk.dev;
     auto take = [&](size_t elems) {
         uint32_t* p = cur;
@@ -798,6 +566,7 @@ static int pk_create_t(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* blob, 
         if (pk.q_builtin29 && !getenv("BZH_QUOTIENT_SATURATED")) {
             const size_t cols29 = (size_t)pk.nf + m + 5 + pk.hoist_cols;
             BZH_HIP_TRY(ctx, hipMalloc((void**)&pk.key29, cols29 * 9 * en * 4));
+            pk.key29_bytes = cols29 * 9 * en * 4;
             const dim3 blk(256);
             uint32_t* d = pk.key29;
             auto conv = [&](const uint32_t* src, size_t ncols) {

@@ -1,20 +1,12 @@
-// Part of the whole-proof translation unit (csrc/prove.hip): the COMPILER -- circuit expressions as serialised, the evaluator's
-// expression pool (hash-consed DAG), the VM v1 compiler, the VM v2 quotient compiler (y-folding by gate, shared subexpressions,
-// hoisting), the program's hash and its straight-line HIP source, the column registry, the device arena and the blob reader.
+// Part of the whole-proof translation unit (csrc/prove.hip): the COMPILER -- the evaluator's expression pool (hash-consed DAG),
+// the VM v1 compiler, the VM v2 quotient compiler (y-folding by gate, shared subexpressions, hoisting), the program's hash and
+// its straight-line HIP source, the column registry.  (Circuit expressions as serialised, the registry keys, the device arena
+// and the blob reader: csrc/key_shape.hpp, included before this file.)
 // Host code only.  Included inside namespace bzh { namespace { (prove_kernels.cuh opens them).
 #pragma once
 // ---------------------------------------------------------------------------
-// circuit expressions (as serialised) and evaluator expressions (over a column registry)
+// evaluator expressions (over a column registry)
 // ---------------------------------------------------------------------------
-enum { CX_CONST = 0, CX_ADVICE = 1, CX_FIXED = 2, CX_INSTANCE = 3, CX_NEG = 4, CX_ADD = 5, CX_MUL = 6, CX_SCALE = 7 };
-struct CNode {
-    uint8_t tag;
-    uint32_t col = 0;
-    int32_t rot = 0;
-    uint32_t val[8] = {0};  // Montgomery
-    int a = -1, b = -1;
-};
-
 enum { EX_CONST, EX_SYMBOL, EX_QUERY, EX_NEG, EX_ADD, EX_MUL, EX_SCALE };
 struct ENode {
     uint8_t tag;
@@ -1045,104 +1037,4 @@ struct Cols {
     }
     int at(uint64_t key) const { return index.at(key); }
 };
-// registry keys
-enum { K_ADV = 1, K_FIX, K_INST, K_SIGMA, K_IDENT, K_PZ, K_LA, K_LS, K_LZ, K_MISC };
-enum { M_L0, M_LLAST, M_LBLIND, M_X, M_TINV, M_AC, M_SC, M_A, M_S, M_ACC, M_Q, M_R, M_F, M_H0 /* + i */ };
-static inline uint64_t key(int kind, uint64_t i) { return ((uint64_t)kind << 32) | i; }
 
-// device arena: grow-only blocks, reset at the start of every call
-struct Arena {
-    struct Block {
-        char* p;
-        size_t size, used;
-    };
-    std::vector<Block> blocks;
-    int device = 0;
-    size_t live = 0, peak = 0;  // bytes handed out and not released since the last reset, and their high-water mark
-    // A call's allocation sequence is deterministic, so after the first call of a given shape the arena is ONE block
-    // that every later call bumps through without touching hipMalloc (overflow blocks are merged at the next reset).
-    void reset() {
-        if (blocks.size() > 1) {
-            const size_t want = peak + (peak >> 4) + ((size_t)1 << 20);
-            release();
-            Block nb;
-            nb.size = want;
-            nb.used = 0;
-            if (hipMalloc((void**)&nb.p, nb.size) == hipSuccess) blocks.push_back(nb);
-        }
-        for (auto& b : blocks) b.used = 0;
-        live = peak = 0;
-    }
-    void release() {
-        for (auto& b : blocks) (void)hipFree(b.p);
-        blocks.clear();
-    }
-    void* alloc(size_t bytes) {
-        bytes = (bytes + 255) & ~(size_t)255;
-        live += bytes;
-        peak = std::max(peak, live);
-        for (auto& b : blocks)
-            if (b.size - b.used >= bytes) {
-                void* r = b.p + b.used;
-                b.used += bytes;
-                return r;
-            }
-        Block nb;
-        nb.size = std::max(bytes, (size_t)256 << 20);
-        if (hipMalloc((void**)&nb.p, nb.size) != hipSuccess) return nullptr;
-        nb.used = bytes;
-        blocks.push_back(nb);
-        return nb.p;
-    }
-    // Stack discipline for temporaries (a commitment's scalar vectors, gathered rows): everything allocated after mark() is
-    // handed back by pop().  Work on the buffers was enqueued on the ctx's one stream, so whatever reuses the memory runs
-    // after it.  While the arena is still a list of blocks (a key's first call) only the accounting moves: the merged block
-    // of the next call is sized by the high-water mark.
-    struct Mark {
-        size_t used, live;
-        bool single;
-    };
-    Mark mark() const { return Mark{blocks.size() == 1 ? blocks[0].used : 0, live, blocks.size() == 1}; }
-    void pop(const Mark& m) {
-        live = m.live;
-        if (m.single && blocks.size() == 1) blocks[0].used = m.used;
-    }
-};
-struct ArenaScope {
-    Arena& a;
-    Arena::Mark m;
-    explicit ArenaScope(Arena& ar) : a(ar), m(ar.mark()) {}
-    ~ArenaScope() { a.pop(m); }
-};
-
-struct Reader {
-    const uint8_t* p;
-    const uint8_t* end;
-    bool ok = true;
-    uint32_t u32() {
-        if (end - p < 4) {
-            ok = false;
-            return 0;
-        }
-        uint32_t v;
-        memcpy(&v, p, 4);
-        p += 4;
-        return v;
-    }
-    uint8_t u8() {
-        if (end - p < 1) {
-            ok = false;
-            return 0;
-        }
-        return *p++;
-    }
-    const uint8_t* bytes(size_t n) {
-        if ((size_t)(end - p) < n) {
-            ok = false;
-            return nullptr;
-        }
-        const uint8_t* r = p;
-        p += n;
-        return r;
-    }
-};

@@ -15,7 +15,7 @@ struct ProofView {
 };
 
 template <class SF>
-static Fe<SF> cx_eval(const bzh_pk& pk, int i, const std::vector<Fe<SF>>& adv, const std::vector<Fe<SF>>& fix,
+static Fe<SF> cx_eval(const KeyShape& pk, int i, const std::vector<Fe<SF>>& adv, const std::vector<Fe<SF>>& fix,
                       const std::vector<Fe<SF>>& inst) {
     const CNode& e = pk.cx[i];
     auto find = [](const std::vector<std::pair<int, int>>& qs, int col, int rot) -> size_t {
@@ -43,31 +43,6 @@ static Fe<SF> cx_eval(const bzh_pk& pk, int i, const std::vector<Fe<SF>>& adv, c
     }
 }
 
-// Byte offsets of the points of a proof, in the order verify_host reads them.  They depend on the key only: the counts below
-// are the ones verify_host reads with, and its read_point checks every offset it arrives at against this list.
-static std::vector<uint32_t> verify_point_offsets(const bzh_pk& pk) {
-    std::vector<uint32_t> offs;
-    size_t off = 0;
-    auto points = [&](size_t c) {
-        for (; c; c--, off += 32) offs.push_back((uint32_t)off);
-    };
-    auto scalars = [&](size_t c) { off += 32 * c; };
-    const size_t nl = (size_t)pk.nl, nsets = (size_t)pk.nsets;
-    points((size_t)pk.na);          // advice
-    points(2 * nl);                 // permuted lookup inputs and tables
-    points(nsets);                  // permutation products
-    points(nl);                     // lookup products
-    points(1);                      // the vanishing argument's random polynomial
-    points((size_t)pk.npieces);     // h pieces
-    scalars(pk.instance_queries.size() + pk.advice_queries.size() + pk.fixed_queries.size() + 1 + pk.perm_columns.size());
-    scalars(nsets ? 3 * nsets - 1 : 0);
-    scalars(5 * nl);
-    points(1);                      // multiopen: f
-    scalars(pk.rot_sets.size());
-    points(1);                      // the opening's S
-    points(2 * (size_t)pk.k);       // L_j, R_j
-    return offs;
-}
 // the points of one proof decoded ahead of the host pass (BZH_VERIFY_POINTS_DEVICE): affine canonical, one BZH_POINT_* each
 struct PrePoints {
     const uint32_t* offsets = nullptr;
@@ -82,7 +57,7 @@ struct HostPassTimes {
 
 // host pass over one proof; inst_xy: this proof's instance commitments.  Returns false on any malformed input.
 template <class C>
-static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t* proof, size_t len, size_t nl_cap,
+static bool verify_host(const KeyShape& pk, const uint64_t* inst_xy, const uint8_t* proof, size_t len, size_t nl_cap,
                         ProofView<C>& out, const PrePoints* pre = nullptr, HostPassTimes* times = nullptr) {
     using SF = typename CurveInfo<C>::SF;
     const int na = pk.na, ni = pk.ni, nsets = pk.nsets, nl = pk.nl, npieces = pk.npieces;
@@ -429,28 +404,112 @@ static bool verify_host(const bzh_pk& pk, const uint64_t* inst_xy, const uint8_t
     return true;
 }
 
+
+// The device side of the verifier and of keygen_vk: columns of n Montgomery elements out of an arena, and their commitments
+// with blind 1 against a table the caller names -- the key itself is host data.
 template <class C>
-static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* instances, size_t inst_rows, const uint8_t* proofs,
+struct ColumnCommitter {
+    using SF = typename CurveInfo<C>::SF;
+    using PB = typename C::Base;
+    bzh_ctx* ctx;
+    const KeyShape& key;
+    Arena& arena;
+    hipStream_t st;
+    const size_t n;
+    ColumnCommitter(bzh_ctx* c, const KeyShape& ks, Arena& ar) : ctx(c), key(ks), arena(ar), st(c->stream), n(ks.n) {}
+
+    uint32_t* dalloc(size_t elems) { return (uint32_t*)arena.alloc(elems * 32); }
+    int zero(uint32_t* p, size_t elems) {
+        BZH_HIP_TRY(ctx, hipMemsetAsync(p, 0, elems * 32, st));
+        return BZH_OK;
+    }
+    int copy2d(uint32_t* dst, size_t dpitch, const uint32_t* src, size_t spitch, size_t width, size_t rows) {
+        if (!rows || !width) return BZH_OK;
+        BZH_HIP_TRY(ctx, hipMemcpy2DAsync(dst, dpitch * 32, src, spitch * 32, width * 32, rows, hipMemcpyDeviceToDevice, st));
+        return BZH_OK;
+    }
+    int upload(uint32_t* dst, const Fe<SF>* src, size_t elems) { return h2d_small(ctx, dst, src, elems * 32); }
+    int to_coeff(uint32_t* dst, const uint32_t* src, size_t count) {
+        if (!count) return BZH_OK;
+        BZH_HIP_TRY(ctx, hipMemcpyAsync(dst, src, count * n * 32, hipMemcpyDeviceToDevice, st));
+        return ntt_run(ctx, key.field, dst, key.k, count, key.omega, nullptr, 1, BZH_FORM_MONTGOMERY);
+    }
+    // Params::commit with blind 1 for `count` polynomials of n coefficients (contiguous) against srs = (g | u | w): affine
+    // canonical points out.  The scalar rows are (coefficients | 0 | 1), as the prover lays them out.
+    int commit(const bzh_bases* srs, const uint32_t* polys, size_t count, std::vector<uint64_t>& xy) {
+        xy.assign(count * 8, 0);
+        if (!count) return BZH_OK;
+        ArenaScope scope(arena);
+        const size_t cols = n + 2;
+        uint32_t* sc = dalloc(count * cols);
+        uint32_t* bl = dalloc(count);
+        uint32_t* d_out = dalloc(count * 3);
+        if (!sc || !bl || !d_out) return BZH_E_OOM;
+        const std::vector<Fe<SF>> ones(count, fe_one<SF>());
+        BZH_TRY(upload(bl, ones.data(), count));
+        BZH_TRY(zero(sc, count * cols));
+        BZH_TRY(copy2d(sc, cols, polys, n, n, count));
+        BZH_TRY(copy2d(sc + (n + 1) * 8, cols, bl, 1, 1, count));
+        BZH_TRY(msm_run(ctx, srs, sc, cols, count, BZH_FORM_MONTGOMERY, d_out));
+        std::vector<uint64_t> jac(count * 12);
+        BZH_TRY(d2h_async(ctx, jac.data(), d_out, count * 96));
+        BZH_TRY(d2h_finish(ctx));
+        h_jac_to_affine<PB>(jac.data(), count, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, xy.data());
+        return BZH_OK;
+    }
+    // Params::commit_lagrange with blind 1 for `count` columns of which only the first `len` rows are non-zero: `vals` holds
+    // count x len values (host, Montgomery), committed against the first len points of g_lagrange by ONE prefix MSM; W (w_xy,
+    // affine canonical) is added on the host.  Nothing of size n is allocated.
+    int commit_prefix(const bzh_bases* g_lagrange, const Fe<SF>* vals, size_t len, size_t count, const uint64_t* w_xy, std::vector<uint64_t>& xy) {
+        xy.assign(count * 8, 0);
+        if (!count) return BZH_OK;
+        std::vector<uint64_t> aff(count * 8, 0);   // the MSM's results, affine Montgomery ((0,0): identity)
+        if (len) {
+            ArenaScope scope(arena);
+            uint32_t* sc = dalloc(count * len);
+            uint32_t* d_out = dalloc(count * 3);
+            if (!sc || !d_out) return BZH_E_OOM;
+            BZH_TRY(upload(sc, vals, count * len));
+            BZH_TRY(msm_run(ctx, g_lagrange, sc, len, count, BZH_FORM_MONTGOMERY, d_out));
+            std::vector<uint64_t> jac(count * 12);
+            BZH_TRY(d2h_async(ctx, jac.data(), d_out, count * 96));
+            BZH_TRY(d2h_finish(ctx));
+            h_jac_to_affine<PB>(jac.data(), count, BZH_FORM_MONTGOMERY, BZH_FORM_MONTGOMERY, aff.data());
+        }
+        Affine<PB> w;
+        w.x = fe_from_u64<PB>(w_xy, BZH_FORM_CANONICAL);
+        w.y = fe_from_u64<PB>(w_xy + 4, BZH_FORM_CANONICAL);
+        std::vector<uint64_t> jac(count * 12);
+        for (size_t i = 0; i < count; i++) {
+            Xyzz<PB> acc = xyzz_identity<PB>();
+            Affine<PB> a;
+            a.x = fe_from_u64<PB>(&aff[8 * i]);
+            a.y = fe_from_u64<PB>(&aff[8 * i + 4]);
+            if (!aff_is_id(a)) xyzz_madd(acc, a);
+            xyzz_madd(acc, w);
+            Fe<PB> X, Y, Z;
+            xyzz_to_jacobian(acc, X, Y, Z);
+            fe_to_u64<PB>(&jac[12 * i], X);
+            fe_to_u64<PB>(&jac[12 * i + 4], Y);
+            fe_to_u64<PB>(&jac[12 * i + 8], Z);
+        }
+        h_jac_to_affine<PB>(jac.data(), count, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, xy.data());
+        return BZH_OK;
+    }
+};
+
+// verify_proof for a batch.  key: what the verifier reads of a key (a bzh_pk's or a bzh_vk's); srs: (g | u | w) with its window
+// table; g_lagrange: (g_lagrange | u | w), or null for instance commitments through the coefficient basis; arena: the (key,
+// ctx) workspace; points_on_device: BZH_VERIFY_POINTS_DEVICE.
+template <class C>
+static int verify_batch_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* srs, const bzh_bases* g_lagrange, Arena& arena,
+                          bool points_on_device, size_t batch, const uint64_t* instances, size_t inst_rows, const uint8_t* proofs,
                           size_t proof_stride, const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
     using SF = typename CurveInfo<C>::SF;
-    Arena& arena = pk->arena_for(ctx, ctx->device);
     arena.reset();
-    Prover<C> pv(ctx, *pk, batch, arena);
-    const size_t n = pk->n, B = batch;
-    const int ni = pk->ni;
-    std::vector<uint64_t> xy;
-    std::vector<Fe<SF>> blinds;
-    {
-        std::lock_guard<std::mutex> lkv(pk->mu);
-        if (!pk->vk_ready) {  // verifying key: commitments to the fixed and permutation polynomials, blind 1
-            const size_t nf = pk->nf, m = pk->perm_columns.size();
-            blinds.assign(nf, fe_one<SF>());
-            BZH_TRY(pv.commit(pk->fixed_polys, n, nf, blinds, pk->fixed_commitments));
-            blinds.assign(m, fe_one<SF>());
-            BZH_TRY(pv.commit(pk->sigma_polys, n, m, blinds, pk->sigma_commitments));
-            pk->vk_ready = true;
-        }
-    }
+    ColumnCommitter<C> pv(ctx, key, arena);
+    const size_t n = key.n, B = batch;
+    const int ni = key.ni;
     // BZH_PROVE_TRACE=1: where the call's wall time goes, on stderr (tools/ubench_verify_points.py reads these lines)
     const bool trace = getenv("BZH_PROVE_TRACE") != nullptr;
     auto t_last = std::chrono::steady_clock::now();
@@ -462,14 +521,8 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
     };
     // BZH_VERIFY_POINTS_DEVICE: the 32-byte strings of every point of every proof, gathered by the key's offset list, go up in
     // one copy and through one k_decompress launch; points and statuses come back with the instance commitments' read-back.
-    std::vector<uint32_t> vp_offs;
-    {
-        std::lock_guard<std::mutex> lkv(pk->mu);
-        if (pk->vp_select == BZH_VERIFY_POINTS_DEVICE) {
-            if (pk->vp_offsets.empty()) pk->vp_offsets = verify_point_offsets(*pk);
-            vp_offs = pk->vp_offsets;
-        }
-    }
+    static const std::vector<uint32_t> no_offsets;
+    const std::vector<uint32_t>& vp_offs = points_on_device ? key.vp_offsets : no_offsets;
     const size_t np = vp_offs.size(), np_all = B * np, np_pad = (np_all + 15) & ~(size_t)15;
     std::vector<uint64_t> pre_xy;
     std::vector<uint8_t> pre_st;
@@ -502,21 +555,25 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
     // instance commitments of the whole batch (the verifier recomputes them, as upstream does for IPA)
     std::vector<uint64_t> inst_xy(B * std::max(ni, 1) * 8, 0);
     if (ni) {
-        uint32_t* inst = pv.dalloc(B * ni * n);
-        uint32_t* inst_polys = pv.dalloc(B * ni * n);
-        if (!inst || !inst_polys) return BZH_E_OOM;
-        BZH_TRY(pv.zero(inst, B * ni * n));
-        if (inst_rows) {
-            std::vector<Fe<SF>> hv(B * ni * inst_rows);
-            for (size_t i = 0; i < hv.size(); i++) hv[i] = fe_to_mont(fe_from_u64<SF>(instances + 4 * i));
-            uint32_t* tmp = pv.dalloc(hv.size());
-            if (!tmp) return BZH_E_OOM;
-            BZH_TRY(pv.upload(tmp, hv.data(), hv.size()));
-            BZH_TRY(pv.copy2d(inst, n, tmp, inst_rows, inst_rows, B * ni));
+        std::vector<Fe<SF>> hv(B * ni * inst_rows);
+        for (size_t i = 0; i < hv.size(); i++) hv[i] = fe_to_mont(fe_from_u64<SF>(instances + 4 * i));
+        if (g_lagrange) {
+            // Params::commit_lagrange: the inst_rows values of a column against the first inst_rows Lagrange points, plus W
+            BZH_TRY(pv.commit_prefix(g_lagrange, hv.data(), inst_rows, B * ni, g0_u_w + 16, inst_xy));
+        } else {
+            uint32_t* inst = pv.dalloc(B * ni * n);
+            uint32_t* inst_polys = pv.dalloc(B * ni * n);
+            if (!inst || !inst_polys) return BZH_E_OOM;
+            BZH_TRY(pv.zero(inst, B * ni * n));
+            if (inst_rows) {
+                uint32_t* tmp = pv.dalloc(hv.size());
+                if (!tmp) return BZH_E_OOM;
+                BZH_TRY(pv.upload(tmp, hv.data(), hv.size()));
+                BZH_TRY(pv.copy2d(inst, n, tmp, inst_rows, inst_rows, B * ni));
+            }
+            BZH_TRY(pv.to_coeff(inst_polys, inst, B * ni));
+            BZH_TRY(pv.commit(srs, inst_polys, B * ni, inst_xy));
         }
-        BZH_TRY(pv.to_coeff(inst_polys, inst, B * ni));
-        blinds.assign(B * ni, fe_one<SF>());
-        BZH_TRY(pv.commit(inst_polys, n, B * ni, blinds, inst_xy));
     }
     mark("instance commitments");
     if (np) {
@@ -534,8 +591,8 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
         mark("vp:read-back");
     }
     // host pass, one thread per proof
-    const size_t ncommit = (size_t)pk->na + 3 * pk->nl + pk->nsets + 1 + pk->npieces + 1 + pk->nf + pk->perm_columns.size() + ni;
-    const size_t nl_cap = ncommit + 2 * (size_t)pk->k + 1 + 3 + 4;
+    const size_t ncommit = (size_t)key.na + 3 * key.nl + key.nsets + 1 + key.npieces + 1 + key.nf + key.perm_columns.size() + ni;
+    const size_t nl_cap = ncommit + 2 * (size_t)key.k + 1 + 3 + 4;
     std::vector<ProofView<C>> views(B);
     {
         const size_t nthreads = std::min<size_t>({B, (size_t)host_thread_budget(), (size_t)32});
@@ -546,7 +603,7 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
                 const auto t0 = std::chrono::steady_clock::now();
                 for (size_t b = t; b < B; b += nthreads) {
                     PrePoints pre{vp_offs.data(), np, np ? &pre_xy[b * np * 8] : nullptr, np ? &pre_st[b * np] : nullptr};
-                    verify_host<C>(*pk, &inst_xy[b * std::max(ni, 1) * 8], proofs + b * proof_stride, proof_lens[b], nl_cap, views[b],
+                    verify_host<C>(key, &inst_xy[b * std::max(ni, 1) * 8], proofs + b * proof_stride, proof_lens[b], nl_cap, views[b],
                                    np ? &pre : nullptr, trace ? &times[t] : nullptr);
                 }
                 if (trace) times[t].total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -567,7 +624,7 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
         if (views[b].ok) live.push_back(b);
     }
     if (live.empty()) return BZH_OK;
-    const size_t Bl = live.size(), kk = pk->k;
+    const size_t Bl = live.size(), kk = key.k;
     std::vector<uint64_t> lc_pts(Bl * nl_cap * 8), lc_scal(Bl * nl_cap * 4), cu(Bl * (kk + 1) * 4);
     for (size_t j = 0; j < Bl; j++) {
         ProofView<C>& v = views[live[j]];
@@ -577,7 +634,7 @@ static int verify_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t
         memcpy(&cu[j * (kk + 1) * 4], v.cu.data(), (kk + 1) * 32);
     }
     std::vector<int> ok(Bl, 0);
-    BZH_TRY(ipa_check_batch(ctx, pk->srs, Bl, nl_cap, lc_pts.data(), lc_scal.data(), cu.data(), ok.data()));
+    BZH_TRY(ipa_check_batch(ctx, srs, Bl, nl_cap, lc_pts.data(), lc_scal.data(), cu.data(), ok.data()));
     for (size_t j = 0; j < Bl; j++) results[live[j]] = ok[j];
     mark("ipa check");
     return BZH_OK;

@@ -153,6 +153,27 @@ int main(int argc, char** argv) {
            "\"quotient\": \"%s\", \"vk_digest\": \"%s\", \"fnv1a\": \"%016llx\"}\n", batch, best, batch / best * 1e3, lens[0], accepted,
            flavour == BZH_QUOTIENT_BUILTIN ? "builtin kernel" : (flavour == BZH_QUOTIENT_MODULE ? "module" : "interpreted"),
            vk_placeholder ? "placeholder (BZH_EXAMPLE_VK_REPR not given)" : "caller's", (unsigned long long)h);
+    // a verifier without the proving key (verify_shot runs keygen_vk only, src/wasm/circuit_wasm.rs:180-194): keygen_vk, write the
+    // key, read it back -- host only -- and verify the batch through it, instance columns committed on g_lagrange
+    {
+        bzh_vk *vk = nullptr, *vk_back = nullptr;
+        CHECK(bzh_vk_create(ctx, g, blob.data(), blob.size(), &vk));
+        size_t vk_len = 0;
+        CHECK(bzh_vk_write(vk, nullptr, 0, &vk_len));
+        std::vector<uint8_t> vk_bytes(vk_len);
+        CHECK(bzh_vk_write(vk, vk_bytes.data(), vk_len, &vk_len));
+        CHECK(bzh_vk_read(vk_bytes.data(), vk_len, &vk_back));
+        std::vector<int> ok_vk(batch, 0);
+        CHECK(bzh_verify_batch_vk(ctx, vk_back, g, g_lagrange, batch, instances.data(), 4, proofs.data(), max_proof, lens.data(), g0_u_w,
+                                  ok_vk.data()));
+        size_t accepted_vk = 0, key_bytes = 1;
+        for (int v : ok_vk) accepted_vk += v != 0;
+        CHECK(bzh_vk_device_bytes(vk_back, &key_bytes, nullptr));
+        printf("{\"vk_bytes\": %zu, \"vk_device_bytes\": %zu, \"verified_through_vk\": %zu, \"same_as_pk\": %s}\n", vk_len, key_bytes,
+               accepted_vk, ok_vk == ok ? "true" : "false");
+        bzh_vk_free(vk_back);
+        bzh_vk_free(vk);
+    }
     // what the reference's wasm frontend returns per proof (src/wasm/circuit_wasm.rs:27-31,164-170): {commitment, proof}
     {
         const size_t stride = bzh_record_stride(max_proof);

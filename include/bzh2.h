@@ -405,6 +405,52 @@ int bzh_prove_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advi
                     size_t instance_rows, const uint8_t* rng, size_t rng_stride, uint8_t* proofs, size_t proof_stride,
                     size_t* proof_lens);
 
+/* ---- the verifying key (halo2_proofs plonk::{keygen_vk, VerifyingKey}; the reference's verify_board / verify_shot run keygen_vk
+ * only, src/wasm/circuit_wasm.rs:97-111,180-194; benches/board.rs:80-86 verifies through pk.get_vk()) ---------------------------
+ * What verify_proof reads of a key and nothing else: curve, k, the verifying-key digest, the constraint system (gates, lookups,
+ * query lists, permutation columns -- no fixed assignment), the commitments to the fixed and permutation polynomials, and the
+ * multiopen structure derived from those.  A bzh_vk is host memory only, immutable and tied to no device: it owns no device
+ * allocation (the per-call workspace of a verification lives with the (key, ctx) pair inside the library, as for bzh_pk), and
+ * several host threads may verify on ONE key concurrently, each through its own ctx.
+ *   bzh_vk_create        keygen_vk: parses the blob, builds the permutation polynomials, commits the fixed and permutation columns
+ *                        (blind 1) against `srs` (n + 2 points, as for bzh_pk_create), keeps the commitments and releases every
+ *                        column before it returns.  No quotient program, no cosets, no hoisted or fe29 columns are made.
+ *   bzh_vk_from_pk       pk.get_vk(): the same bytes as bzh_vk_create on the pk's blob and SRS (fills the pk's lazy commitments
+ *                        if they have not been computed yet).
+ *   bzh_vk_write / read  VerifyingKey::write / read in THIS LIBRARY'S OWN FORMAT "BZV1" (layout at the top of
+ *                        csrc/verifying_key.hpp; not upstream's, which stores the commitments only and re-derives the constraint
+ *                        system from the Circuit type).  out == NULL: size query; a cap below *len is BZH_E_ARG and nothing is
+ *                        written.  bzh_vk_read is host only -- no ctx, no device, no keygen -- and validates everything the
+ *                        verifier will index with: truncated / corrupt / wrong-magic input is BZH_E_ARG, a coordinate >= p or a
+ *                        point off the curve BZH_E_RANGE.
+ *   bzh_vk_info          any out pointer may be NULL.
+ *   bzh_vk_device_bytes / bzh_pk_device_bytes
+ *                        the library's own bookkeeping of device memory held under a key: *key_bytes = allocations that live as
+ *                        long as the key (always 0 for a bzh_vk; columns, cosets, hoisted and fe29 columns for a bzh_pk),
+ *                        *workspace_bytes = the per-(key, ctx) workspaces calls have grown so far.  Either may be NULL.
+ *   bzh_vk_free          BZH_E_ARG, leaving the key as it was, while a bzh_verify_batch_vk on it is still running.
+ *   bzh_verify_batch_vk  bzh_verify_batch with the key and the SRS apart.  srs: (g | u | w) with its window table; g_lagrange:
+ *                        (g_lagrange | u | w) or NULL; the other arguments and results[] exactly as bzh_verify_batch; g0_u_w is
+ *                        checked against `srs`.  With g_lagrange the instance columns are committed as upstream's commit_lagrange
+ *                        does -- their instance_rows values against the first instance_rows points of g_lagrange, plus W -- and
+ *                        nothing proportional to n is allocated for them; with NULL they go through an inverse NTT and an n-term
+ *                        MSM against srs, as in bzh_verify_batch.  The same points, hence the same results[], either way.
+ *                        A proof of another circuit or another k is results[b] = 0, not an error. */
+typedef struct bzh_vk bzh_vk;
+int bzh_vk_create(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* circuit, size_t circuit_len, bzh_vk** out);
+int bzh_vk_from_pk(bzh_ctx* ctx, bzh_pk* pk, bzh_vk** out);
+int bzh_vk_write(const bzh_vk* vk, uint8_t* out, size_t cap, size_t* len);
+int bzh_vk_read(const uint8_t* bytes, size_t len, bzh_vk** out);
+int bzh_vk_info(const bzh_vk* vk, int* curve, unsigned* k, uint32_t* num_instance, uint32_t* num_fixed_commitments,
+                uint32_t* num_permutation_commitments, size_t* max_proof_bytes);
+int bzh_vk_vk_repr(const bzh_vk* vk, uint8_t* out_repr32, int* is_placeholder);
+int bzh_vk_device_bytes(const bzh_vk* vk, size_t* key_bytes, size_t* workspace_bytes);
+int bzh_pk_device_bytes(const bzh_pk* pk, size_t* key_bytes, size_t* workspace_bytes);
+int bzh_vk_free(bzh_vk* vk);
+int bzh_verify_batch_vk(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch,
+                        const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
+                        const size_t* proof_lens, const uint64_t* g0_u_w, int* results);
+
 /* create_proof with the randomness drawn inside the library, as the reference does from OsRng (benches/shot.rs:68): proof b's
  * stream is ChaCha20 keyed by seeds[b] (32 bytes; 64-bit block counter from 0, zero nonce), block i being the i-th 64-byte draw
  * (ff::Field::random), expanded on the device -- no rng_bytes_per_proof (2 MB at k = 14) to generate and upload per proof.
