@@ -327,6 +327,29 @@ inline bool h_batch_invert(Fe<P>* v, size_t n, bool skip_zeros = false) {
 }
 
 // ---------------------------------------------------------------------------
+// out[0 .. np) <- the coefficients, lowest first, of the polynomial of degree < np through (points[j], evals[j]), j < np, by
+// Lagrange's formula.  inv_den[j] = 1 / prod_(m != j) (points[j] - points[m]): the caller inverts them (h_batch_invert, for many
+// interpolations at once).
+// ---------------------------------------------------------------------------
+template <class P>
+inline void h_interpolate(const Fe<P>* points, const Fe<P>* evals, const Fe<P>* inv_den, size_t np, Fe<P>* out) {
+    for (size_t i = 0; i < np; i++) out[i] = fe_zero<P>();
+    for (size_t j = 0; j < np; j++) {
+        std::vector<Fe<P>> num{fe_one<P>()};   // prod_(m != j) (X - points[m])
+        for (size_t m = 0; m < np; m++) {
+            if (m == j) continue;
+            std::vector<Fe<P>> nx(num.size() + 1);
+            nx[0] = fe_neg(fe_mul(points[m], num[0]));
+            for (size_t i = 1; i < num.size(); i++) nx[i] = fe_sub(num[i - 1], fe_mul(points[m], num[i]));
+            nx[num.size()] = num.back();
+            num.swap(nx);
+        }
+        const Fe<P> cf = fe_mul(evals[j], inv_den[j]);
+        for (size_t i = 0; i < np; i++) out[i] = fe_add(out[i], fe_mul(cf, num[i]));
+    }
+}
+
+// ---------------------------------------------------------------------------
 // points
 // ---------------------------------------------------------------------------
 // n Jacobian points (X, Y, Z: 12 limbs each, in in_form) -> affine x || y (8 limbs each, in out_form) with one inversion;

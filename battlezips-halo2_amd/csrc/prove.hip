@@ -51,6 +51,7 @@ extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __at
 #include "quotient_program.hpp"  // the compiler (host only)
 #include "proving_key.hpp"       // closes them around the global struct bzh_pk, reopens; keygen
 #include "verifying_key.hpp"     // likewise around bzh_vk; its byte format and host-only entry points
+#include "device_columns.hpp"     // columns on the device, their commitments: shared by prover, verifier and keygen_vk
 #include "prover.hpp"
 #include "verifier.hpp"
 

@@ -405,57 +405,25 @@ static bool verify_host(const KeyShape& pk, const uint64_t* inst_xy, const uint8
 }
 
 
-// The device side of the verifier and of keygen_vk: columns of n Montgomery elements out of an arena, and their commitments
-// with blind 1 against a table the caller names -- the key itself is host data.
+// The device side of the verifier and of keygen_vk: the shared column helpers (device_columns.hpp), with commitments of blind 1
+// against a table the caller names -- the key itself is host data.
 template <class C>
-struct ColumnCommitter {
-    using SF = typename CurveInfo<C>::SF;
-    using PB = typename C::Base;
-    bzh_ctx* ctx;
-    const KeyShape& key;
-    Arena& arena;
-    hipStream_t st;
-    const size_t n;
-    ColumnCommitter(bzh_ctx* c, const KeyShape& ks, Arena& ar) : ctx(c), key(ks), arena(ar), st(c->stream), n(ks.n) {}
+struct ColumnCommitter : DeviceColumns<C> {
+    using DC = DeviceColumns<C>;
+    using SF = typename DC::SF;
+    using PB = typename DC::PB;
+    using DC::arena;
+    using DC::ctx;
+    using DC::dalloc;
+    using DC::n;
+    using DC::read_points;
+    using DC::upload;
+    using DC::DeviceColumns;
 
-    uint32_t* dalloc(size_t elems) { return (uint32_t*)arena.alloc(elems * 32); }
-    int zero(uint32_t* p, size_t elems) {
-        BZH_HIP_TRY(ctx, hipMemsetAsync(p, 0, elems * 32, st));
-        return BZH_OK;
-    }
-    int copy2d(uint32_t* dst, size_t dpitch, const uint32_t* src, size_t spitch, size_t width, size_t rows) {
-        if (!rows || !width) return BZH_OK;
-        BZH_HIP_TRY(ctx, hipMemcpy2DAsync(dst, dpitch * 32, src, spitch * 32, width * 32, rows, hipMemcpyDeviceToDevice, st));
-        return BZH_OK;
-    }
-    int upload(uint32_t* dst, const Fe<SF>* src, size_t elems) { return h2d_small(ctx, dst, src, elems * 32); }
-    int to_coeff(uint32_t* dst, const uint32_t* src, size_t count) {
-        if (!count) return BZH_OK;
-        BZH_HIP_TRY(ctx, hipMemcpyAsync(dst, src, count * n * 32, hipMemcpyDeviceToDevice, st));
-        return ntt_run(ctx, key.field, dst, key.k, count, key.omega, nullptr, 1, BZH_FORM_MONTGOMERY);
-    }
     // Params::commit with blind 1 for `count` polynomials of n coefficients (contiguous) against srs = (g | u | w): affine
-    // canonical points out.  The scalar rows are (coefficients | 0 | 1), as the prover lays them out.
+    // canonical points out
     int commit(const bzh_bases* srs, const uint32_t* polys, size_t count, std::vector<uint64_t>& xy) {
-        xy.assign(count * 8, 0);
-        if (!count) return BZH_OK;
-        ArenaScope scope(arena);
-        const size_t cols = n + 2;
-        uint32_t* sc = dalloc(count * cols);
-        uint32_t* bl = dalloc(count);
-        uint32_t* d_out = dalloc(count * 3);
-        if (!sc || !bl || !d_out) return BZH_E_OOM;
-        const std::vector<Fe<SF>> ones(count, fe_one<SF>());
-        BZH_TRY(upload(bl, ones.data(), count));
-        BZH_TRY(zero(sc, count * cols));
-        BZH_TRY(copy2d(sc, cols, polys, n, n, count));
-        BZH_TRY(copy2d(sc + (n + 1) * 8, cols, bl, 1, 1, count));
-        BZH_TRY(msm_run(ctx, srs, sc, cols, count, BZH_FORM_MONTGOMERY, d_out));
-        std::vector<uint64_t> jac(count * 12);
-        BZH_TRY(d2h_async(ctx, jac.data(), d_out, count * 96));
-        BZH_TRY(d2h_finish(ctx));
-        h_jac_to_affine<PB>(jac.data(), count, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, xy.data());
-        return BZH_OK;
+        return DC::commit(srs, polys, n, count, std::vector<Fe<SF>>(count, fe_one<SF>()), xy);
     }
     // Params::commit_lagrange with blind 1 for `count` columns of which only the first `len` rows are non-zero: `vals` holds
     // count x len values (host, Montgomery), committed against the first len points of g_lagrange by ONE prefix MSM; W (w_xy,
@@ -471,10 +439,7 @@ struct ColumnCommitter {
             if (!sc || !d_out) return BZH_E_OOM;
             BZH_TRY(upload(sc, vals, count * len));
             BZH_TRY(msm_run(ctx, g_lagrange, sc, len, count, BZH_FORM_MONTGOMERY, d_out));
-            std::vector<uint64_t> jac(count * 12);
-            BZH_TRY(d2h_async(ctx, jac.data(), d_out, count * 96));
-            BZH_TRY(d2h_finish(ctx));
-            h_jac_to_affine<PB>(jac.data(), count, BZH_FORM_MONTGOMERY, BZH_FORM_MONTGOMERY, aff.data());
+            BZH_TRY(read_points(d_out, count, BZH_FORM_MONTGOMERY, aff.data()));
         }
         Affine<PB> w;
         w.x = fe_from_u64<PB>(w_xy, BZH_FORM_CANONICAL);

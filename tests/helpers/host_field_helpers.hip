@@ -1,11 +1,12 @@
 // Test program (not product code): the host helpers of csrc/host_field.hpp -- square root, point decompression, roots of
-// unity, batch inversion, Jacobian -> affine -- driven by a command file, one command per line, one answer line each.
+// unity, batch inversion, interpolation, Jacobian -> affine -- driven by a command file, one command per line, one answer line each.
 // tests/test_host_field_cpu.py writes the commands and compares the answers with oracle/pasta.py.  All values are 64 hex
 // digits, big-endian, canonical unless a form says otherwise.
 //   sqrt F a                         -> "ok r" | "none"
 //   decompress C bytes32             -> "ok x y" | "reject"          (bytes32: the 32 encoded bytes as they lie in memory)
 //   omega F log_n                    -> "w"
 //   binv F skip_zeros n v_0 .. v_n-1 -> "ok 1/v_0 .." | "fail"
+//   interp F np x_0 .. x_np-1 y_0 .. y_np-1 -> "ok c_0 .. c_np-1" (coefficients, lowest first) | "fail" (two points coincide)
 //   jac C in_form out_form n X Y Z.. -> "x y .."                      (limbs in the given forms, 0 canonical, 1 Montgomery)
 #include <cstdio>
 #include <fstream>
@@ -91,6 +92,26 @@ int main(int argc, char** argv) {
                     for (size_t i = 0; i < n; i++)
                         if (!fe_eq(v[i], before[i])) out = "fail-but-wrote";
                 }
+                return BZH_OK;
+            });
+        } else if (cmd == "interp") {
+            rc = with_field(id, [&](auto p) {
+                using P = decltype(p);
+                size_t np = 0;
+                in >> np;
+                std::vector<Fe<P>> x(np), y(np), den(np, fe_one<P>()), c(np + 1, fe_one<P>());   // c[np]: a guard past the output
+                for (auto& e : x) e = read_fe<P>(in);
+                for (auto& e : y) e = read_fe<P>(in);
+                for (size_t j = 0; j < np; j++)
+                    for (size_t m = 0; m < np; m++)
+                        if (m != j) den[j] = fe_mul(den[j], fe_sub(x[j], x[m]));
+                if (!h_batch_invert(den.data(), np)) {
+                    out = "fail";
+                    return BZH_OK;
+                }
+                h_interpolate(x.data(), y.data(), den.data(), np, c.data());
+                out = fe_eq(c[np], fe_one<P>()) ? "ok" : "wrote-past-the-end";
+                for (size_t i = 0; i < np; i++) out += " " + show(c[i]);
                 return BZH_OK;
             });
         } else if (cmd == "jac") {

@@ -3,7 +3,7 @@ algebra): csrc/field.cuh gives the host pass a 64-bit-limb Montgomery product.  
 against the library's own header and compares it with the 32-bit CIOS on all four fields (host code only: no GPU needed).  tests/helpers/host_field_edges.hip runs
 the host fe_add / fe_sub / fe_neg and both host products over the adversarial operand table of tests/helpers/field_edges.py.
 tests/helpers/host_field_helpers.hip drives the helpers of csrc/host_field.hpp (square root, point decompression, roots of unity,
-batch inversion, Jacobian -> affine), which the library otherwise reaches only around GPU work, against oracle/pasta.py."""
+batch inversion, interpolation, Jacobian -> affine), which the library otherwise reaches only around GPU work, against oracle/pasta.py."""
 import os
 import shutil
 import subprocess
@@ -166,6 +166,52 @@ def test_host_batch_inversion_with_zeros(helper_program, fid):
             assert g == ["fail"], g[:1]
         else:
             assert g[0] == "ok" and [int(x, 16) for x in g[1:]] == [F.inv(x) for x in v], "field %d skip %d n %d" % (fid, skip, len(v))
+
+
+def _interpolate(F, xs, ys):
+    """coefficients, lowest first, of the polynomial of degree < len(xs) through the points: Lagrange's formula in exact integers"""
+    p = F.p
+    out = [0] * len(xs)
+    for j, (xj, yj) in enumerate(zip(xs, ys)):
+        num, den = [1], 1
+        for mm, xm in enumerate(xs):
+            if mm != j:
+                num = [((num[i - 1] if i else 0) - xm * (num[i] if i < len(num) else 0)) % p for i in range(len(num) + 1)]
+                den = den * (xj - xm) % p
+        cf = yj * F.inv(den) % p
+        out = [(o + cf * c) % p for o, c in zip(out, num)]
+    return out
+
+
+@pytest.mark.parametrize("fid", [0, 1])
+def test_host_interpolation_against_exact_integers(helper_program, fid):
+    """h_interpolate (the multiopen remainders) through 1, 2, 3 and 4 points of Fp and Fq: points at 0, 1 and p - 1, evaluations
+    of 0 (all of them, and one among others), edge and random operands, coefficient by coefficient against Lagrange's formula
+    in Python integers; the result takes the given values at the given points, and two equal points make the inversion fail"""
+    import random
+
+    from helpers import field_edges as E
+    O = _oracle()
+    F = O.FIELD_BY_ID[fid]
+    p = F.p
+    rng = random.Random(400 + fid)
+    edges = E.edge_values(p)
+    cases = []
+    for np_ in (1, 2, 3, 4):
+        special = [0, 1, p - 1, 2][:np_]
+        cases.append((special, [rng.randrange(p) for _ in range(np_)]))
+        cases.append((special[::-1], [0] * np_))
+        cases.append(([p - 1, rng.randrange(2, p - 1), 0, 1][:np_], [rng.randrange(p), 0, p - 1, 1][:np_]))
+        cases.append(([rng.randrange(p) for _ in range(np_)], [rng.randrange(p) for _ in range(np_)]))
+        cases.append((rng.sample(edges, np_), rng.sample(edges, np_)))
+    assert all(len(set(xs)) == len(xs) for xs, _ in cases)
+    got = helper_program(["interp %d %d %s" % (fid, len(xs), " ".join(_hx(v) for v in xs + ys)) for xs, ys in cases])
+    for (xs, ys), g in zip(cases, got):
+        want = _interpolate(F, xs, ys)
+        assert [sum(c * pow(x, i, p) for i, c in enumerate(want)) % p for x in xs] == ys   # (the reference itself)
+        assert g[0] == "ok" and [int(c, 16) for c in g[1:]] == want, "field %d, %d points %s" % (fid, len(xs), [hex(x) for x in xs])
+    twice = helper_program(["interp %d 3 %s" % (fid, " ".join(_hx(v) for v in [5, 7, 5, 1, 2, 3]))])
+    assert twice == [["fail"]]
 
 
 def _decompress(O, curve, raw):
