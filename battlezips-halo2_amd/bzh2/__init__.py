@@ -748,6 +748,34 @@ def _ctx_kate_division_batch(self, field: int, coeffs, xs, form: int = FORM_CANO
 Context.kate_division_batch = _ctx_kate_division_batch
 
 
+EXPORTS += ["bzh_batch_invert_plan", "bzh_kate_division_plan"]
+
+
+def batch_invert_plan(count: int) -> int:
+    """threads of the launch bzh_batch_invert makes for `count` elements: thread t owns the elements t, t + nthreads, ...
+    (bzh_batch_invert_plan)."""
+    L = load()
+    L.bzh_batch_invert_plan.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    nthreads = ctypes.c_size_t()
+    rc = L.bzh_batch_invert_plan(count, ctypes.byref(nthreads))
+    if rc != OK:
+        raise BzhError(rc, "bzh_batch_invert_plan")
+    return nthreads.value
+
+
+def kate_division_plan(n: int, batch: int = 1):
+    """(threads, L, S) of the launch bzh_kate_division_batch makes for `batch` polynomials of n coefficients: S workgroups of
+    `threads` threads per polynomial, L quotient coefficients per thread (bzh_kate_division_plan)."""
+    L = load()
+    szp = ctypes.POINTER(ctypes.c_size_t)
+    L.bzh_kate_division_plan.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), szp, szp]
+    threads, seg, spans = ctypes.c_uint(), ctypes.c_size_t(), ctypes.c_size_t()
+    rc = L.bzh_kate_division_plan(n, batch, ctypes.byref(threads), ctypes.byref(seg), ctypes.byref(spans))
+    if rc != OK:
+        raise BzhError(rc, "bzh_kate_division_plan")
+    return threads.value, seg.value, spans.value
+
+
 EXPORTS += ["bzh_permute_expression_pair_batch"]
 
 

@@ -226,10 +226,8 @@ static int batch_invert_t(bzh_ctx* ctx, uint32_t* d, size_t count) {
     void* tmp = nullptr;
     int rc = ws_ensure(ctx, 0, count * 32, &tmp);
     if (rc) return rc;
-    // chains of ~16 elements, at least one wave, at most ~64k threads
-    size_t nthreads = (count + 15) / 16;
-    if (nthreads < 64) nthreads = count < 64 ? count : 64;
-    if (nthreads > 65536) nthreads = 65536;
+    size_t nthreads;
+    if ((rc = bzh_batch_invert_plan(count, &nthreads))) return rc;
     ScopedTimer t(ctx, BZH_T_POLY);
     hipLaunchKernelGGL((k_batch_invert<P>), dim3((unsigned)((nthreads + kVecThreads - 1) / kVecThreads)), dim3(kVecThreads), 0,
                        ctx->stream, d, (uint32_t*)tmp, count, nthreads);
@@ -360,23 +358,12 @@ __global__ void __launch_bounds__(kKateMaxThreads) k_kate_rows(const uint32_t* _
 template <class P>
 static int kate_t(bzh_ctx* ctx, const uint32_t* d_c, size_t n, size_t batch, const uint32_t* d_xs, uint32_t* d_q) {
     if (n < 2 || !batch) return BZH_OK;
-    if (batch > 65535) return BZH_E_ARG;
-    const size_t m = n - 1;
-    // 256-thread workgroups (64 for tiny inputs), about 256 workgroups per launch: S = 256 / batch spans per polynomial,
-    // at least 4 coefficients per thread and at most 32 spans.  Per coefficient the kernel spends 2 multiplications on the
-    // recurrence and (3 log2(threads) + log2(L) + S) / L on the stitching, so short chains are for small batches only.
-    unsigned threads = 64;
-    while (threads < 256u && (size_t)threads * 4 < m) threads <<= 1;
-    size_t S = (256 + batch - 1) / batch;
-    if (S > 32) S = 32;
-    size_t L = (m + (size_t)threads * S - 1) / ((size_t)threads * S);
-    if (L < 4) L = 4;
-    S = (m + (size_t)threads * L - 1) / ((size_t)threads * L);
+    unsigned threads;
+    size_t L, S;
+    int rc = bzh_kate_division_plan(n, batch, &threads, &L, &S);  // refuses batch > 65535 (the grid's y extent)
+    if (rc) return rc;
     void* tot = nullptr;
-    if (S > 1) {
-        int rc = ws_ensure(ctx, 2, (S - 1) * batch * 32, &tot);
-        if (rc) return rc;
-    }
+    if (S > 1 && (rc = ws_ensure(ctx, 2, (S - 1) * batch * 32, &tot))) return rc;
     ScopedTimer t(ctx, BZH_T_POLY);
     if (S > 1)
         hipLaunchKernelGGL((k_kate_span_totals<P>), dim3((unsigned)(S - 1), (unsigned)batch), dim3(kVecThreads), 0, ctx->stream, d_c, n, d_xs,
@@ -431,3 +418,37 @@ int poly_vec_mul(bzh_ctx* ctx, int field, uint32_t* a, const uint32_t* b, size_t
 }
 
 }  // namespace bzh
+
+// ---------------------------------------------------------------------------
+// the launch shapes, as host functions of the C ABI: the drivers above call them, and a test can ask which regime a size
+// lands in
+// ---------------------------------------------------------------------------
+// threads of the k_batch_invert launch: chains of ~16 elements, at least one wave, at most ~64k threads
+extern "C" int bzh_batch_invert_plan(size_t count, size_t* nthreads) {
+    if (!nthreads) return BZH_E_ARG;
+    size_t t = (count + 15) / 16;
+    if (t < 64) t = count < 64 ? count : 64;
+    if (t > 65536) t = 65536;
+    *nthreads = t;  // count == 0: no thread, the driver launches nothing
+    return BZH_OK;
+}
+
+// k_kate_rows runs on a grid of (S, batch) workgroups of `threads` threads, L coefficients each.
+// 256-thread workgroups (64 for tiny inputs), about 256 workgroups per launch: S = 256 / batch spans per polynomial,
+// at least 4 coefficients per thread and at most 32 spans.  Per coefficient the kernel spends 2 multiplications on the
+// recurrence and (3 log2(threads) + log2(L) + S) / L on the stitching, so short chains are for small batches only.
+extern "C" int bzh_kate_division_plan(size_t n, size_t batch, unsigned* threads_out, size_t* L_out, size_t* S_out) {
+    if (!threads_out || !L_out || !S_out || n < 2 || !batch || batch > 65535) return BZH_E_ARG;
+    const size_t m = n - 1;
+    unsigned threads = 64;
+    while (threads < 256u && (size_t)threads * 4 < m) threads <<= 1;
+    size_t S = (256 + batch - 1) / batch;
+    if (S > 32) S = 32;
+    size_t L = (m + (size_t)threads * S - 1) / ((size_t)threads * S);
+    if (L < 4) L = 4;
+    S = (m + (size_t)threads * L - 1) / ((size_t)threads * L);
+    *threads_out = threads;
+    *L_out = L;
+    *S_out = S;
+    return BZH_OK;
+}

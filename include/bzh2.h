@@ -623,6 +623,16 @@ int bzh_batch_normalize(bzh_ctx* ctx, int curve, const uint64_t* xyz, size_t n, 
                         uint8_t* status);
 int bzh_affine_compress_batch(bzh_ctx* ctx, int curve, const uint64_t* xy, size_t n, int form, int mem, uint8_t* out32);
 int bzh_batch_normalize_plan(size_t n, size_t* lanes, size_t* chain);
+/* host only, no ctx: the launch shapes of bzh_batch_invert and bzh_kate_division(_batch), from the functions the drivers call.
+ *   bzh_batch_invert_plan    thread t of *nthreads owns the chain of elements t, t + nthreads, ... below count (Montgomery's
+ *                            trick over it, one inversion per thread); count == 0 gives 0: nothing is launched.
+ *   bzh_kate_division_plan   every polynomial of n coefficients is cut into *S spans, one workgroup of *threads threads each,
+ *                            thread t of a span walking *L consecutive quotient coefficients (the last span and its last
+ *                            threads may have fewer, or none).  BZH_E_ARG for what is not launched or refused: n < 2,
+ *                            batch == 0, batch > 65535.
+ * BZH_E_ARG on a NULL output. */
+int bzh_batch_invert_plan(size_t count, size_t* nthreads);
+int bzh_kate_division_plan(size_t n, size_t batch, unsigned* threads, size_t* L, size_t* S);
 /* root of unity of order 2^log_n used by halo2's EvaluationDomain for this field
  * (ROOT_OF_UNITY^(2^(S-log_n))); out: 4 limbs in `form`. */
 int bzh_field_omega(int field, unsigned log_n, int form, uint64_t* out);
