@@ -159,7 +159,11 @@ class NativeProvingKey:
         L.bzh_pk_quotient_stats.argtypes = [_VP] + [ctypes.POINTER(ctypes.c_uint32)] * 4
         v = [ctypes.c_uint32() for _ in range(4)]
         self.ctx._check(L.bzh_pk_quotient_stats(self.handle, *[ctypes.byref(x) for x in v]), "bzh_pk_quotient_stats")
-        return {"ops": v[0].value, "multiplications_per_row": v[1].value, "lds_slots": v[2].value, "hoisted_columns": v[3].value}
+        L.bzh_pk_quotient_loads.argtypes = [_VP] + [ctypes.POINTER(ctypes.c_uint32)] * 2
+        w = [ctypes.c_uint32() for _ in range(2)]
+        self.ctx._check(L.bzh_pk_quotient_loads(self.handle, *[ctypes.byref(x) for x in w]), "bzh_pk_quotient_loads")
+        return {"ops": v[0].value, "multiplications_per_row": v[1].value, "lds_slots": v[2].value, "hoisted_columns": v[3].value,
+                "loads_per_row": w[0].value, "leaf_slots": w[1].value}
 
     # ---- the quotient evaluator as compiled code -------------------------------------------------------------
     def quotient_source(self) -> str:

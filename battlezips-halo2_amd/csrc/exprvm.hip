@@ -172,14 +172,16 @@ struct ExprOp2 {
 };
 static_assert(sizeof(ExprOp2) == 16, "ExprOp2 layout");
 
-static constexpr int kVm2Threads = 128;
+// rows per workgroup: 128, or 64 for a program whose slot file would not fit 64 KB of LDS at 128 (more than 16 slots: the
+// quotient programs with column leaves in slots, csrc/quotient_program.hpp)
+static constexpr int kVm2Threads = 128, kVm2ThreadsSmall = 64;
 
-template <class P>
-__global__ void __launch_bounds__(kVm2Threads) k_expr_vm2(const ExprOp2* __restrict__ prog, int nops, const uint32_t* const* __restrict__ cols,
+template <class P, int kRows>
+__global__ void __launch_bounds__(kRows) k_expr_vm2(const ExprOp2* __restrict__ prog, int nops, const uint32_t* const* __restrict__ cols,
                                                            const size_t* __restrict__ strides, const uint32_t* __restrict__ consts,
                                                            size_t const_stride, size_t size, uint32_t* __restrict__ out) {
     extern __shared__ uint4 vm2_lds[];
-    const size_t r = blockIdx.x * (size_t)kVm2Threads + threadIdx.x, v = blockIdx.y;
+    const size_t r = blockIdx.x * (size_t)kRows + threadIdx.x, v = blockIdx.y;
     if (r >= size) return;   // size is a multiple of the block size for every domain the prover uses; no barriers below
     const size_t mask = size - 1;
     const uint32_t* cv = consts + v * const_stride * 8;
@@ -192,13 +194,13 @@ __global__ void __launch_bounds__(kVm2Threads) k_expr_vm2(const ExprOp2* __restr
         }
         if (kind == BZH_EXPR_CONST) return fe_load<P>(cv + (size_t)idx * 8);
         Fe<P> x;   // LDS slot
-        const uint4 lo = vm2_lds[((size_t)idx * 2) * kVm2Threads + t], hi = vm2_lds[((size_t)idx * 2 + 1) * kVm2Threads + t];
+        const uint4 lo = vm2_lds[((size_t)idx * 2) * kRows + t], hi = vm2_lds[((size_t)idx * 2 + 1) * kRows + t];
         x.l[0] = lo.x, x.l[1] = lo.y, x.l[2] = lo.z, x.l[3] = lo.w, x.l[4] = hi.x, x.l[5] = hi.y, x.l[6] = hi.z, x.l[7] = hi.w;
         return x;
     };
     auto store = [&](int idx, const Fe<P>& x) {
-        vm2_lds[((size_t)idx * 2) * kVm2Threads + t] = make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]);
-        vm2_lds[((size_t)idx * 2 + 1) * kVm2Threads + t] = make_uint4(x.l[4], x.l[5], x.l[6], x.l[7]);
+        vm2_lds[((size_t)idx * 2) * kRows + t] = make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]);
+        vm2_lds[((size_t)idx * 2 + 1) * kRows + t] = make_uint4(x.l[4], x.l[5], x.l[6], x.l[7]);
     };
 #define VM2_ARITH(OP, A, B) ((OP) == 0 ? fe_add(A, B) : ((OP) == 1 ? fe_sub(A, B) : ((OP) == 2 ? fe_mul(A, B) : fe_sub(B, A))))
 #define VM2_SS(OP, P0, RA, RB) case (0 << 4) | ((OP) << 2) | (P0): RA = VM2_ARITH(OP, RA, RB); break;
@@ -238,13 +240,18 @@ __global__ void __launch_bounds__(kVm2Threads) k_expr_vm2(const ExprOp2* __restr
 int expr_eval2(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint32_t* const* d_cols, const size_t* d_strides,
                const uint32_t* d_consts, size_t const_stride, size_t size, size_t batch, int nlds, uint32_t* d_out) {
     if (size % kVm2Threads) return BZH_E_ARG;
-    const size_t lds = (size_t)std::max(nlds, 1) * 2 * kVm2Threads * sizeof(uint4);
+    const size_t per_row = (size_t)std::max(nlds, 1) * 2 * sizeof(uint4);
+    const int threads = per_row * kVm2Threads <= 64 * 1024 ? kVm2Threads : kVm2ThreadsSmall;
+    const size_t lds = per_row * (size_t)threads;
     if (lds > 64 * 1024) return BZH_E_RANGE;
     ScopedTimer t(ctx, BZH_T_QUOTIENT);
-    const dim3 grid((unsigned)(size / kVm2Threads), (unsigned)batch), block(kVm2Threads);
+    const dim3 grid((unsigned)(size / (size_t)threads), (unsigned)batch), block((unsigned)threads);
     const ExprOp2* p = (const ExprOp2*)d_prog;
     BZH_TRY(with_pasta_field(field, [&](auto f) {
-        hipLaunchKernelGGL((k_expr_vm2<decltype(f)>), grid, block, lds, ctx->stream, p, nops, d_cols, d_strides, d_consts, const_stride, size, d_out);
+        if (threads == kVm2Threads)
+            hipLaunchKernelGGL((k_expr_vm2<decltype(f), kVm2Threads>), grid, block, lds, ctx->stream, p, nops, d_cols, d_strides, d_consts, const_stride, size, d_out);
+        else
+            hipLaunchKernelGGL((k_expr_vm2<decltype(f), kVm2ThreadsSmall>), grid, block, lds, ctx->stream, p, nops, d_cols, d_strides, d_consts, const_stride, size, d_out);
         return BZH_OK;
     }));
     BZH_HIP_TRY(ctx, hipGetLastError());

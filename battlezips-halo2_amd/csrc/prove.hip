@@ -245,6 +245,13 @@ int bzh_pk_quotient_stats(bzh_pk* pk, uint32_t* ops, uint32_t* multiplications, 
     return BZH_OK;
 }
 
+int bzh_pk_quotient_loads(bzh_pk* pk, uint32_t* loads_per_row, uint32_t* leaf_slots) {
+    if (!pk) return BZH_E_ARG;
+    if (loads_per_row) *loads_per_row = pk->q_ok ? (uint32_t)bzh::program2_loads(pk->qprog) : 0;
+    if (leaf_slots) *leaf_slots = pk->q_ok ? (uint32_t)pk->qprog.leaf_slots : 0;
+    return BZH_OK;
+}
+
 static int copy_text(const std::string& src, char* buf, size_t cap, size_t* len) {
     *len = src.size();
     if (buf && cap) {
@@ -274,6 +281,41 @@ int bzh_quotient_source_for_circuit(int curve, const uint8_t* circuit, size_t ci
     if (program_hash) *program_hash = pk.q_hash;
     // two flavours of the same program: saturated limbs (namespace bzh_q_<hash>) and unsaturated 9 x 29-bit limbs (bzh_q29_<hash>)
     return copy_text(bzh::program2_source(pk.qprog, pk.field, true) + "\n" + bzh::program2_source29(pk.qprog, pk.field), buf, cap, len);
+}
+
+int bzh_quotient_program_for_circuit(int curve, const uint8_t* circuit, size_t circuit_len, void* ops, size_t ops_cap, size_t* nops,
+                                     void* consts, size_t consts_cap, size_t* nconsts, uint32_t* stats8) {
+    if (!circuit || !nops || !nconsts) return BZH_E_ARG;
+    bzh_pk pk;
+    BZH_TRY(bzh::with_pasta_curve(curve, [&](auto c) {
+        using C = decltype(c);
+        bzh::ParsedKey<typename bzh::CurveInfo<C>::SF> po;
+        return bzh::pk_parse_t<C>(circuit, circuit_len, pk, po);
+    }));
+    if (!pk.q_ok) return BZH_E_RANGE;
+    const bzh::Program2& pg = pk.qprog;
+    *nops = pg.ops.size();
+    *nconsts = pg.consts.size();
+    if (stats8) {
+        uint32_t nm = 0;
+        for (auto& o : pg.ops) nm += ((o.code >> 4) < 3 && ((o.code >> 2) & 3) == bzh::V2_MUL);
+        const uint32_t st[8] = {(uint32_t)pg.ops.size(), nm, (uint32_t)pg.nlds, (uint32_t)bzh::program2_loads(pg), (uint32_t)pg.leaf_slots,
+                                (uint32_t)pg.leaf_base, (uint32_t)pk.hoist_cols, 0};
+        memcpy(stats8, st, sizeof(st));
+    }
+    if (ops) {
+        if (ops_cap < pg.ops.size() * sizeof(bzh::ExprOp2)) return BZH_E_ARG;
+        memcpy(ops, pg.ops.data(), pg.ops.size() * sizeof(bzh::ExprOp2));
+    }
+    if (consts) {
+        if (consts_cap < pg.consts.size() * 40) return BZH_E_ARG;
+        for (size_t i = 0; i < pg.consts.size(); i++) {
+            uint32_t w[10] = {(uint32_t)pg.consts[i].sym, 0};
+            memcpy(w + 2, pg.consts[i].val, 32);
+            memcpy((uint8_t*)consts + 40 * i, w, 40);
+        }
+    }
+    return BZH_OK;
 }
 
 int bzh_quotient_degree_histogram(int curve, const uint8_t* circuit, size_t circuit_len, uint32_t* polys, uint32_t* muls) {

@@ -217,6 +217,14 @@ enum { V2_ADD = 0, V2_SUB = 1, V2_MUL = 2, V2_RSUB = 3 };
 enum { V2_SS = 0, V2_SL = 1, V2_LL = 2, V2_UN = 3, V2_NEG = 0, V2_LOAD = 1, V2_STORE = 2 };
 // LDS slots: 0 ACC, 1 IN, then the shared-subexpression slots, spill slots last (allocated only if a program uses them)
 static constexpr int kV2Regs = 4, kV2LdsAcc = 0, kV2LdsInner = 1, kV2LdsCse0 = 2, kV2LdsCseMax = 8, kV2LdsSpills = 2, kV2LdsGlobalMax = 6;
+// ... and the column-leaf slots after the cross-group ones (Compiler2::select_leaves)
+// The default is ONE number for every circuit: 3 is what the builtin kernels of both of the reference's circuits have registers
+// for (9 VGPRs per slot, 162 of the 168 that three waves per SIMD allow).  A foreign circuit gets the same 3:
+// it has no builtin kernel, its slots are the interpreter's LDS or whatever its own compiled module makes of them.
+static constexpr int kV2LdsLeafMax = 8, kV2LdsLeafDefault = 3;
+// BZH_VM2_LEAF = 0...8: how many of them a program may use (0: no leaf is kept; like BZH_VM2_CSE / BZH_VM2_GLOBAL another value is
+// another program, which the interpreter runs).  Pinned bit for bit by tests/test_gpu_quotient_leaf_slots.py.
+static constexpr char kV2LeafEnv[] = "BZH_VM2_LEAF";
 enum { SY_YPOW0 = 4096 /* + m: y^m */ };
 
 struct Program2 {
@@ -224,7 +232,18 @@ struct Program2 {
     std::vector<ConstEnt> consts;
     bool ok = true;
     int nlds = 2;
+    int leaf_base = 0, leaf_slots = 0;   // the slots that hold column leaves: [leaf_base, leaf_base + leaf_slots)
 };
+// column loads per row: the operands of kind BZH_EXPR_COLUMN the program reads
+static size_t program2_loads(const Program2& pg) {
+    size_t n = 0;
+    for (const ExprOp2& o : pg.ops) {
+        const int form = o.code >> 4, op = (o.code >> 2) & 3;
+        n += (form == V2_LL || (form == V2_UN && op == V2_LOAD)) && o.a_kind == BZH_EXPR_COLUMN;
+        n += (form == V2_SL || form == V2_LL) && o.b_kind == BZH_EXPR_COLUMN;
+    }
+    return n;
+}
 
 // FNV-1a over the instruction words: ties a compiled quotient module to the program it was generated from
 static uint64_t program2_hash(const Program2& pg, int field) {
@@ -679,10 +698,23 @@ struct Compiler2 {
     };
     int global_slots = 6;   // Board 541 -> 475 products, Shot 398 -> 356 (2: 495 / 376; perfect sharing: 447 / 327); 138 -> 146 VGPRs
     std::map<int, GlobalEnt> gsel;
+    // COLUMN LEAVES kept across (and inside) gate groups.  A (column, rotation) leaf is an operand of the instruction that uses it,
+    // so the program loaded it again at every use: Board 564 column loads per row for 130 distinct leaves, the eight rotation-0
+    // advice leaves most of them.  Up to `leaf_slots` slots hold one leaf each over a range of groups: filled by LOAD + STORE when
+    // the first group of the range opens, a slot operand until the last one closes -- no new operation, the products unchanged.
+    // A leaf may reside several times (the ranges are chosen, not first-to-last use: select_leaves).  Each slot is 9 VGPRs in
+    // the unsaturated builtin kernel: 3 keep it at three waves per SIMD without scratch (162 of 168 VGPRs; Board 564 -> 340, Shot 421 -> 258 loads).
+    struct LeafEnt {
+        int col, rot, slot, first, last;
+    };
+    int leaf_slots = kV2LdsLeafDefault, cur_group = -1;
+    std::vector<LeafEnt> lsel;
     explicit Compiler2(const EPool& p) : pool(p), label(p.n.size(), -1) {
         if (const char* e = getenv("BZH_VM2_CSE")) cse_slots = std::max(0, std::min(kV2LdsCseMax, atoi(e)));
         if (const char* e = getenv("BZH_VM2_GLOBAL")) global_slots = std::max(0, std::min(kV2LdsGlobalMax, atoi(e)));
+        if (const char* e = getenv(kV2LeafEnv)) leaf_slots = std::max(0, std::min(kV2LdsLeafMax, atoi(e)));
     }
+    int leaf_base() const { return kV2LdsCse0 + cse_slots + kV2LdsSpills + global_slots; }
     int nlds() const { return max_lds + 1; }
 
     struct Leaf {
@@ -703,16 +735,22 @@ struct Compiler2 {
         const ENode& e = pool.n[i];
         return e.tag == EX_CONST || e.tag == EX_SYMBOL || e.tag == EX_QUERY || cse.count(i) || hoisted.count(i);
     }
+    // a column leaf: the slot it resides in while the current group is inside one of its ranges, else the column itself
+    Leaf column_leaf(int col, int rot) const {
+        for (const LeafEnt& l : lsel)
+            if (l.col == col && l.rot == rot && l.first <= cur_group && cur_group <= l.last) return {BZH_EXPR_LDS, l.slot, 0};
+        return {BZH_EXPR_COLUMN, col, rot};
+    }
     Leaf leaf_of(int i) {
         auto ih = hoisted.find(i);
-        if (ih != hoisted.end()) return {BZH_EXPR_COLUMN, ih->second, 0};
+        if (ih != hoisted.end()) return column_leaf(ih->second, 0);
         auto it = cse.find(i);
         if (it != cse.end()) return {BZH_EXPR_LDS, it->second, 0};
         const ENode& e = pool.n[i];
         if (e.tag == EX_CONST) return {BZH_EXPR_CONST, const_index(-1, e.val), 0};
         if (e.tag == EX_SYMBOL) return {BZH_EXPR_CONST, const_index(e.col, nullptr), 0};
         if (e.rot < -32768 || e.rot > 32767) prog.ok = false;
-        return {BZH_EXPR_COLUMN, e.col, e.rot};
+        return column_leaf(e.col, e.rot);
     }
     int label_of(int i) {
         if (is_leaf(i)) return 0;
@@ -886,6 +924,72 @@ struct Compiler2 {
             max_lds = std::max(max_lds, base + best_slot);
         }
     }
+    // Choose the residences of column leaves from the program emitted WITHOUT them (`group_of[i]`: the group of instruction i):
+    // caching a leaf changes operand kinds only, so the loads counted there are exact.  A candidate is a leaf over a range of
+    // groups [first, last] that begins and ends at a use; its saving is the loads inside the range minus the one that fills
+    // the slot.  Greedy like select_globals: the best saving per group of residence that still finds a slot free over its range;
+    // re-evaluated after every choice, because a chosen range takes its loads away from the leaf's other candidates.
+    // Cost: every round takes at least two loads out of `uses`, so there are at most loads / 2 rounds (Board 65, Shot 51 at the
+    // default), each a scan of leaves x groups^2 / 2 ranges x slots: Board 130 leaves, a few milliseconds of host time per
+    // bzh_pk_create (not visible beside the two emissions).  It grows with the cube of the group count; a circuit with many hundreds of gates would want per-group
+    // free-slot masks kept between rounds.
+    void select_leaves(const std::vector<int>& group_of, int ngroups) {
+        lsel.clear();
+        if (leaf_slots <= 0 || ngroups <= 0) return;
+        std::map<std::pair<int, int>, std::vector<int>> uses;   // (column, rotation) -> loads per group
+        auto count = [&](int kind, int col, int rot, int g) {
+            if (kind != BZH_EXPR_COLUMN) return;
+            std::vector<int>& u = uses[{col, rot}];
+            if (u.empty()) u.assign((size_t)ngroups, 0);
+            u[(size_t)g]++;
+        };
+        for (size_t i = 0; i < prog.ops.size(); i++) {
+            const ExprOp2& o = prog.ops[i];
+            const int form = o.code >> 4, oo = (o.code >> 2) & 3;
+            if (form == V2_LL || (form == V2_UN && oo == V2_LOAD)) count(o.a_kind, o.a_idx, o.a_rot, group_of[i]);
+            if (form == V2_SL || form == V2_LL) count(o.b_kind, o.b_idx, o.b_rot, group_of[i]);
+        }
+        std::vector<std::vector<char>> busy((size_t)leaf_slots, std::vector<char>((size_t)ngroups, 0));
+        for (;;) {
+            double best_score = 0;
+            int best_saving = 0, best_slot = -1, best_first = 0, best_last = 0;
+            std::pair<int, int> best_leaf{0, 0};
+            for (auto& kv : uses) {
+                const std::vector<int>& u = kv.second;
+                for (int first = 0; first < ngroups; first++) {
+                    if (!u[(size_t)first]) continue;
+                    int loads = 0;
+                    unsigned free_ = (1u << leaf_slots) - 1;   // slots free over [first, last] so far
+                    for (int last = first; last < ngroups && free_; last++) {
+                        for (int sl = 0; sl < leaf_slots; sl++)
+                            if (busy[(size_t)sl][(size_t)last]) free_ &= ~(1u << sl);
+                        if (!free_) break;
+                        if (!u[(size_t)last]) continue;
+                        loads += u[(size_t)last];
+                        const int saving = loads - 1;
+                        const double score = (double)saving / (double)(last - first + 1);
+                        if (saving > 0 && (score > best_score || (score == best_score && saving > best_saving))) {
+                            best_score = score, best_saving = saving, best_leaf = kv.first, best_first = first, best_last = last;
+                            best_slot = __builtin_ctz(free_);
+                        }
+                    }
+                }
+            }
+            if (best_slot < 0) break;
+            lsel.push_back(LeafEnt{best_leaf.first, best_leaf.second, leaf_base() + best_slot, best_first, best_last});
+            std::vector<int>& u = uses[best_leaf];
+            for (int g = best_first; g <= best_last; g++) busy[(size_t)best_slot][(size_t)g] = 1, u[(size_t)g] = 0;
+        }
+    }
+    // fill the slots of the leaves whose residence begins with this group
+    void fill_leaves(int group) {
+        for (const LeafEnt& l : lsel) {
+            if (l.first != group) continue;
+            op(V2_UN, V2_LOAD, 0, Leaf{BZH_EXPR_COLUMN, l.col, l.rot});
+            op(V2_UN, V2_STORE, 0, Leaf{BZH_EXPR_LDS, l.slot, 0});
+            max_lds = std::max(max_lds, l.slot);
+        }
+    }
     std::set<int> gparked;
     void open_scope(const std::vector<int>& roots, int group = -1) {
         cse.clear();
@@ -966,58 +1070,80 @@ struct Compiler2 {
             gparked.clear();
             select_globals(group_roots);
         }
-        bool first_group = true;
-        int group_index = -1;
-        for (auto& g : groups) {
-            group_index++;
-            std::vector<int> roots = g.c;
-            if (g.s >= 0) roots.push_back(g.s);
-            open_scope(roots, group_index);
-            const size_t m = g.c.size();
-            if (m > 64) prog.ok = false;   // y^m symbols are provided up to 64
-            for (size_t j = 0; j < m; j++) {
-                depth = 0;
-                if (j == 0) {
-                    emit(g.c[0]);
-                } else if (label_of(g.c[j]) < kV2Regs) {
-                    op(V2_LL, V2_MUL, 0, inner, y);          // r0 = IN y
-                    depth = 1;
-                    emit(g.c[j]);                            // r1 = C_j
-                    op(V2_SS, V2_ADD, 0);
-                    depth = 1;
-                } else {
-                    emit(g.c[j]);                            // r0 = C_j (needs every register)
-                    op(V2_LL, V2_MUL, 1, inner, y);          // r1 = IN y
-                    op(V2_SS, V2_ADD, 0);
-                }
-                if (j + 1 < m) op(V2_UN, V2_STORE, 0, inner);
-            }
-            // r0 = sum_j C_j y^(m-1-j); times the shared factor
-            if (g.s >= 0) {
-                if (is_leaf(g.s)) {
-                    op(V2_SL, V2_MUL, 0, Leaf{0, 0, 0}, leaf_of(g.s));
-                } else if (label_of(g.s) < kV2Regs) {
-                    depth = 1;
-                    emit(g.s);
-                    op(V2_SS, V2_MUL, 0);
-                } else {
-                    op(V2_UN, V2_STORE, 0, inner);
+        // (the accumulator's Horner form ACC <- ACC y^m + S inner fixes the order of the groups: the power of y a constraint gets is
+        // the number of constraints after it, so the groups run in protocol order and the leaf ranges are chosen for that order)
+        std::vector<int> group_of;
+        auto emit_groups = [&]() {
+            prog.ops.clear();
+            group_of.clear();
+            gparked.clear();
+            spill_used = 0;
+            bool first_group = true;
+            int group_index = -1;
+            for (auto& g : groups) {
+                group_index++;
+                cur_group = group_index;
+                std::vector<int> roots = g.c;
+                if (g.s >= 0) roots.push_back(g.s);
+                open_scope(roots, group_index);
+                fill_leaves(group_index);
+                const size_t m = g.c.size();
+                if (m > 64) prog.ok = false;   // y^m symbols are provided up to 64
+                for (size_t j = 0; j < m; j++) {
                     depth = 0;
-                    emit(g.s);
-                    op(V2_SL, V2_MUL, 0, Leaf{0, 0, 0}, inner);
+                    if (j == 0) {
+                        emit(g.c[0]);
+                    } else if (label_of(g.c[j]) < kV2Regs) {
+                        op(V2_LL, V2_MUL, 0, inner, y);          // r0 = IN y
+                        depth = 1;
+                        emit(g.c[j]);                            // r1 = C_j
+                        op(V2_SS, V2_ADD, 0);
+                        depth = 1;
+                    } else {
+                        emit(g.c[j]);                            // r0 = C_j (needs every register)
+                        op(V2_LL, V2_MUL, 1, inner, y);          // r1 = IN y
+                        op(V2_SS, V2_ADD, 0);
+                    }
+                    if (j + 1 < m) op(V2_UN, V2_STORE, 0, inner);
                 }
+                // r0 = sum_j C_j y^(m-1-j); times the shared factor
+                if (g.s >= 0) {
+                    if (is_leaf(g.s)) {
+                        op(V2_SL, V2_MUL, 0, Leaf{0, 0, 0}, leaf_of(g.s));
+                    } else if (label_of(g.s) < kV2Regs) {
+                        depth = 1;
+                        emit(g.s);
+                        op(V2_SS, V2_MUL, 0);
+                    } else {
+                        op(V2_UN, V2_STORE, 0, inner);
+                        depth = 0;
+                        emit(g.s);
+                        op(V2_SL, V2_MUL, 0, Leaf{0, 0, 0}, inner);
+                    }
+                }
+                if (!first_group) {                              // ACC = ACC y^m + r0
+                    const Leaf ym{BZH_EXPR_CONST, const_index(m == 1 ? SY_Y : SY_YPOW0 + (int)m, nullptr), 0};
+                    op(V2_LL, V2_MUL, 1, acc, ym);
+                    op(V2_SS, V2_ADD, 0);
+                }
+                op(V2_UN, V2_STORE, 0, acc);
+                first_group = false;
+                group_of.resize(prog.ops.size(), group_index);
             }
-            if (!first_group) {                              // ACC = ACC y^m + r0
-                const Leaf ym{BZH_EXPR_CONST, const_index(m == 1 ? SY_Y : SY_YPOW0 + (int)m, nullptr), 0};
-                op(V2_LL, V2_MUL, 1, acc, ym);
-                op(V2_SS, V2_ADD, 0);
-            }
-            op(V2_UN, V2_STORE, 0, acc);
-            first_group = false;
+            cse.clear();
+            want.clear();
+            cur_group = -1;
+            op(V2_SL, V2_MUL, 0, Leaf{0, 0, 0}, leaf_of(tinv_node));
+            group_of.resize(prog.ops.size(), group_index);
+        };
+        emit_groups();
+        if (leaf_slots > 0 && prog.ok) {   // the same program again with the chosen leaves in slots (0: the first emission is the program)
+            select_leaves(group_of, (int)groups.size());
+            if (!lsel.empty()) emit_groups();
         }
-        cse.clear();
-        want.clear();
-        op(V2_SL, V2_MUL, 0, Leaf{0, 0, 0}, leaf_of(tinv_node));
+        std::set<int> used;
+        for (const LeafEnt& l : lsel) used.insert(l.slot);
+        prog.leaf_base = leaf_base(), prog.leaf_slots = (int)used.size();
     }
 };
 

@@ -341,6 +341,9 @@ int bzh_pk_set_lagrange(bzh_pk* pk, const bzh_bases* g_lagrange);
 /* the quotient's evaluator program (compiled on the host at bzh_pk_create): instructions, field multiplications per
  * extended-domain row, LDS slots, proof-independent subexpressions hoisted into key-owned coset columns */
 int bzh_pk_quotient_stats(bzh_pk* pk, uint32_t* ops, uint32_t* multiplications, uint32_t* lds_slots, uint32_t* hoisted_columns);
+/* ... and its memory side: column operands loaded per extended-domain row, and how many of the slots hold column leaves
+ * (a (column, rotation) value loaded once and read from its slot over a range of gate groups; BZH_VM2_LEAF, default 3) */
+int bzh_pk_quotient_loads(bzh_pk* pk, uint32_t* loads_per_row, uint32_t* leaf_slots);
 /* The quotient evaluator as compiled code.  The program depends on the circuit only (not on k, the SRS or a witness), so for
  * the reference's two circuits (ShotCircuit, BoardCircuit) the kernels are generated when the library is BUILT
  * (csrc/gen_quotient.cpp -> quotient_builtin.hip, linked into libbzh2.so) and picked up by bzh_pk_create through the program's
@@ -378,6 +381,14 @@ int bzh_pk_verify_selected(bzh_pk* pk, int* where);
  * build-time generator calls; BZH_E_RANGE if the circuit does not fit the evaluator (such circuits use the VM v1 fold). */
 int bzh_quotient_source_for_circuit(int curve, const uint8_t* circuit, size_t circuit_len, char* buf, size_t cap, size_t* len,
                                     uint64_t* program_hash);
+/* Host only: the quotient program itself, as the interpreter runs it and the kernels are generated from it.  ops: 16-byte
+ * instructions {u8 code = form << 4 | operation << 2 | register, u8 a_kind, u8 b_kind, u8 0, i32 a_idx, i32 b_idx, i16 a_rot,
+ * i16 b_rot} (forms, operations and operand kinds: csrc/exprvm.hip); consts: 40-byte entries {i32 symbol (< 0: a literal), u32 0,
+ * u32 value[8] (the literal, Montgomery form)}.  *nops / *nconsts are the counts; a buffer is filled when it is non-NULL and
+ * its capacity in bytes suffices (BZH_E_ARG otherwise).  stats8 (may be NULL): instructions, multiplications per row, slots,
+ * column loads per row, slots holding column leaves, the first of those slots, hoisted columns, 0. */
+int bzh_quotient_program_for_circuit(int curve, const uint8_t* circuit, size_t circuit_len, void* ops, size_t ops_cap, size_t* nops,
+                                     void* consts, size_t consts_cap, size_t* nconsts, uint32_t* stats8);
 /* Host only: the terms of a circuit's quotient numerator (gate constraints with their compressed selectors, permutation and
  * lookup argument terms, in protocol order) by polynomial degree -- polys[d] terms of degree d (in units of n - 1, d < 16) and
  * muls[d] field multiplications in their expression trees.  A term of degree d vanishes on the 2^k-row domain by itself, so its
