@@ -283,15 +283,15 @@ inline EccPoint pedersen_synthesize(const PedersenConfig& c, Layouter& layouter,
 // native pedersen_commit (src/utils/pedersen.rs:17-28) from the same window tables: [m]V + [t]R, affine
 inline Aff pedersen_commit_native(const BoardFixedBases& bases, const Fp& message, const Fq& trapdoor) {
     const auto mc = message.canon();
-    if (!Fq::lt_mod(mc.data())) throw GameError("pedersen_commit: message repr is not a canonical scalar");   // from_repr(..).unwrap()
+    if (!Fq::is_canonical(mc.data())) throw GameError("pedersen_commit: message repr is not a canonical scalar");   // from_repr(..).unwrap()
     const auto tc = trapdoor.canon();
     const std::vector<unsigned> mw = decompose_word_3bit(mc.data(), ECC_NUM_WINDOWS), tw = decompose_word_3bit(tc.data(), ECC_NUM_WINDOWS);
-    Jac acc = jac_identity();
+    Xyzz acc = bzh::xyzz_identity<bzh::FpParams>();
     for (int w = 0; w < ECC_NUM_WINDOWS; w++) {
-        acc = jac_add_mixed(acc, bases.v.points[w][mw[w]]);
-        acc = jac_add_mixed(acc, bases.r.points[w][tw[w]]);
+        bzh::xyzz_madd(acc, bases.v.points[w][mw[w]]);
+        bzh::xyzz_madd(acc, bases.r.points[w][tw[w]]);
     }
-    return to_affine(acc);
+    return bzh::xyzz_to_affine(acc);
 }
 
 // ---- board (src/chips/board.rs, src/circuits/board.rs) -----------------------------------------------------------

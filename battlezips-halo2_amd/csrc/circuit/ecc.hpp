@@ -35,28 +35,26 @@ struct FixedBase {
 };
 
 inline void fixed_base_window_points(const Aff& base, int num_windows, std::vector<std::array<Aff, ECC_H>>& out) {
-    std::vector<Jac> all;
-    Jac pw = to_jac(base);               // [8^w]B
-    Jac sum_lower = jac_identity();      // sum_{j<w} [8^j]B
+    std::vector<Xyzz> all;
+    Xyzz pw = bzh::xyzz_from_affine(base);          // [8^w]B
+    Xyzz sum_lower = bzh::xyzz_identity<bzh::FpParams>();   // sum_{j<w} [8^j]B
     for (int w = 0; w < num_windows; w++) {
+        Xyzz m;
         if (w < num_windows - 1) {
-            Jac m = jac_double(pw);      // [2 8^w]B
-            for (int k = 0; k < ECC_H; k++) {
-                all.push_back(m);
-                m = jac_add(m, pw);
-            }
-            sum_lower = jac_add(sum_lower, pw);
+            m = bzh::xyzz_dbl(pw);                  // [2 8^w]B
+            bzh::xyzz_add(sum_lower, pw);
         } else {
-            const Jac off = jac_neg(jac_double(sum_lower));   // -[sum 2 8^j]B
-            Jac m = off;                                       // k = 0
-            for (int k = 0; k < ECC_H; k++) {
-                all.push_back(m);
-                m = jac_add(m, pw);
-            }
+            m = bzh::xyzz_dbl(sum_lower);           // k = 0: -[sum 2 8^j]B
+            m.y = bzh::fe_neg(m.y);
         }
-        pw = jac_double(jac_double(jac_double(pw)));
+        for (int k = 0; k < ECC_H; k++) {
+            all.push_back(m);
+            bzh::xyzz_add(m, pw);
+        }
+        pw = bzh::xyzz_dbl(bzh::xyzz_dbl(bzh::xyzz_dbl(pw)));
     }
-    const std::vector<Aff> aff = batch_normalize(all);
+    std::vector<Aff> aff(all.size());
+    bzh::h_xyzz_to_affine(all.data(), all.size(), aff.data());
     out.resize(num_windows);
     for (int w = 0; w < num_windows; w++) {
         for (int k = 0; k < ECC_H; k++) out[w][k] = aff[(size_t)w * ECC_H + k];
@@ -628,7 +626,7 @@ inline std::pair<EccPoint, EccPoint> mul_fixed_assign_region_inner(const MulFixe
     auto process_window = [&](int w) {
         const unsigned k = windows[w];
         const Aff& m = base.points[w][k];
-        if (m.x.is_zero()) throw SynthesisError("fixed-base mul: window point with x = 0");
+        if (bzh::fe_is_zero(m.x)) throw SynthesisError("fixed-base mul: window point with x = 0");
         EccPoint pt;
         pt.x = region.assign_advice(c.add.x_p, offset + w, m.x);
         pt.y = region.assign_advice(c.add.y_p, offset + w, m.y);
@@ -636,11 +634,15 @@ inline std::pair<EccPoint, EccPoint> mul_fixed_assign_region_inner(const MulFixe
         return pt;
     };
     // The running sums acc_w = sum_{j <= w} m_j are what the incomplete-addition rows witness (no slope cell): they are
-    // accumulated in Jacobian coordinates and normalised with ONE field inversion, instead of one inversion per row.
-    std::vector<Jac> sums(NW - 1);
-    sums[0] = to_jac(base.points[0][windows[0]]);
-    for (int w = 1; w < NW - 1; w++) sums[w] = jac_add_mixed(sums[w - 1], base.points[w][windows[w]]);
-    const std::vector<Aff> acc_aff = region.shape_pass ? std::vector<Aff>(NW - 1, Aff{Fp::zero(), Fp::zero()}) : batch_normalize(sums);
+    // accumulated in XYZZ coordinates and normalised with ONE field inversion, instead of one inversion per row.
+    std::vector<Xyzz> sums(NW - 1);
+    sums[0] = bzh::xyzz_from_affine(base.points[0][windows[0]]);
+    for (int w = 1; w < NW - 1; w++) {
+        sums[w] = sums[w - 1];
+        bzh::xyzz_madd(sums[w], base.points[w][windows[w]]);
+    }
+    std::vector<Aff> acc_aff(NW - 1, Aff{Fp::zero(), Fp::zero()});
+    if (!region.shape_pass) bzh::h_xyzz_to_affine(sums.data(), sums.size(), acc_aff.data());
     EccPoint acc = process_window(0);                       // initialize_accumulator
     for (int w = 1; w < NW - 1; w++) {                      // add_incomplete over the lower windows
         const EccPoint mul_b = process_window(w);

@@ -42,7 +42,7 @@ struct BinaryValue {
             w[i / 64] &= ~((uint64_t)1 << (i % 64));
         }
     }
-    u128 lower_u128() const { return (u128)w[0] | ((u128)w[1] << 64); }
+    std::array<uint64_t, 2> lower_u128() const { return {w[0], w[1]}; }
     // to_fp: Fp::from_repr(..).unwrap() -- a non-canonical value is an error upstream
     Fp to_fp() const {
         Fp v;

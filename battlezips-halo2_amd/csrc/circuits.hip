@@ -31,9 +31,9 @@ static const uint64_t* const GEN_V = bzh::PEDERSEN_GEN_V;
 static const uint64_t* const GEN_R = bzh::PEDERSEN_GEN_R;
 
 static Aff aff_from_limbs(const uint64_t* l) {
-    Aff a;
-    if (!Fp::from_limbs(l, &a.x) || !Fp::from_limbs(l + 4, &a.y)) throw std::logic_error("generator constant");
-    return a;
+    Fp x, y;
+    if (!Fp::from_limbs(l, &x) || !Fp::from_limbs(l + 4, &y)) throw std::logic_error("generator constant");
+    return Aff{x, y};
 }
 
 // ---- fixed-base tables: derived once per process (Z search), cached on disk next to the library -------------------
@@ -61,8 +61,8 @@ static bool load_zu(const std::string& path, const Aff& gen, FixedBase& fb) {
     fclose(f);
     if (!ok) return false;
     uint64_t g[8];
-    gen.x.to_limbs(g);
-    gen.y.to_limbs(g + 4);
+    Fp(gen.x).to_limbs(g);
+    Fp(gen.y).to_limbs(g + 4);
     if (memcmp(g, buf.data(), 64) != 0) return false;
     fb.z.assign(buf.begin() + 8, buf.begin() + 8 + NW);
     fb.u.resize(NW);
@@ -81,8 +81,8 @@ static void save_zu(const std::string& dir, const std::string& path, const Aff& 
     FILE* f = fopen(tmp.c_str(), "wb");
     if (!f) return;
     std::vector<uint64_t> buf(8);
-    gen.x.to_limbs(buf.data());
-    gen.y.to_limbs(buf.data() + 4);
+    Fp(gen.x).to_limbs(buf.data());
+    Fp(gen.y).to_limbs(buf.data() + 4);
     buf.insert(buf.end(), fb.z.begin(), fb.z.end());
     for (auto& row : fb.u) {
         for (auto& v : row) {
@@ -528,11 +528,7 @@ int bzh_vk_digest(const char* pinned_debug, size_t len, uint8_t* out_repr) {
     h.update((const uint8_t*)pinned_debug, len);
     uint8_t d[64];
     h.finalize(d);
-    uint64_t w[8];
-    memcpy(w, d, 64);
-    // from_bytes_wide: the 512-bit little-endian integer mod p = lo + hi * 2^256
-    const Fp lo = Fp::from_raw_reduce({w[0], w[1], w[2], w[3]}), hi = Fp::from_raw_reduce({w[4], w[5], w[6], w[7]});
-    const Fp v = lo + Fp::mul(hi, Fp::r2());   // r2() read as a Montgomery value is R = 2^256
+    const Fp v = bzh::h_from_u512<bzh::FpParams>(d);   // from_bytes_wide: the 512-bit little-endian integer mod p
     v.to_repr(out_repr);
     return BZH_OK;
 }
@@ -572,7 +568,7 @@ static int synthesize_any(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, cons
             for (size_t r = 0; r < stride; r++) {
                 uint64_t* dst = advice + (pc * n + r) * 4;
                 if (form == BZH_FORM_MONTGOMERY) {
-                    memcpy(dst, compact[pc * stride + r].l, 32);
+                    memcpy(dst, compact[pc * stride + r].fe.l, 32);
                 } else {
                     compact[pc * stride + r].to_limbs(dst);
                 }
@@ -586,7 +582,7 @@ static int synthesize_any(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, cons
     const size_t bytes = batch * na * stride * 32;
     int rc = bzh::h2d_stage(ctx, bytes, &slot);
     if (rc) return rc;
-    rc = synthesize_compact(*c, batch, bi, (Fp*)slot, stride, instances, threads, &err);
+    rc = synthesize_compact(*c, batch, bi, (Fp*)slot, stride, instances, threads, &err);   // pinned staging: circuit/hostfield.hpp asserts Fp's size and alignment
     if (rc) {
         g_circuit_error = err;
         ctx->last_error = err;
@@ -660,8 +656,8 @@ int bzh_pedersen_commit_host(const uint64_t* message, const uint64_t* trapdoor, 
         Fq t;
         if (!Fp::from_limbs(message, &m) || !Fq::from_limbs(trapdoor, &t)) return BZH_E_RANGE;
         const Aff a = pedersen_commit_native(fixed_bases(), m, t);
-        a.x.to_limbs(out_xy);
-        a.y.to_limbs(out_xy + 4);
+        Fp(a.x).to_limbs(out_xy);
+        Fp(a.y).to_limbs(out_xy + 4);
         return BZH_OK;
     } catch (const std::exception& e) {
         g_circuit_error = e.what();

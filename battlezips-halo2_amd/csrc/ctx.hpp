@@ -340,7 +340,5 @@ int decompress_run(bzh_ctx* ctx, int curve, const uint32_t* d_in, size_t n, int 
 // memory (16-byte aligned); enqueues only, the caller holds ctx->mu.  ev: null, or three events recorded before k_hash_to_field,
 // between the two kernels and after k_map_to_curve.
 int h2c_generators_run(bzh_ctx* ctx, uint32_t first, size_t count, uint32_t* d_out_xy, uint8_t* d_status, hipEvent_t* ev = nullptr);
-// params.hip: the iso-curve and isogeny constants of hash_to_curve (Pallas / Vesta), canonical limbs: A, B, Z, x0, t, u, 1/9, 1/27
-int h2c_iso_constants(int curve, uint64_t out[8][4]);
 
 }  // namespace bzh

@@ -86,41 +86,6 @@ static void h2f_plan(const std::string& dst, size_t msg_len, H2fPlan* pl) {
     pl->len0 = (uint32_t)(128 + r0);
     pl->len1 = (uint32_t)r1;
 }
-template <class C>
-static const char* curve_name() {
-    return C::id == BZH_CURVE_PALLAS ? "pallas" : "vesta";
-}
-template <class C>
-static std::string h2c_dst(const char* prefix) {
-    return std::string(prefix) + "-" + curve_name<C>() + "_XMD:BLAKE2b_SSWU_RO_";
-}
-
-// the map's constants out of the host's Iso<F> (csrc/params.hip, after its self-check), made once per curve
-template <class C>
-struct H2cHost {
-    H2cConsts<typename C::Base> K;
-    bool ok = false;
-    H2cHost() {
-        using P = typename C::Base;
-        uint64_t raw[8][4];
-        if (h2c_iso_constants(C::id, raw) != BZH_OK) return;
-        Fe<P> v[8];
-        for (int i = 0; i < 8; i++) v[i] = fe_from_u64<P>(raw[i], BZH_FORM_CANONICAL);
-        K.a = v[0], K.b = v[1], K.z = v[2], K.x0 = v[3], K.t = v[4], K.u = v[5], K.s2 = v[6], K.s3 = v[7];
-        const Fe<P> ai = fe_inv(K.a);
-        K.mba = fe_mul(fe_neg(K.b), ai);
-        K.bza = fe_mul(K.b, fe_mul(fe_inv(K.z), ai));
-        // Z and g are non-squares, so Z g has a root; it turns fe_sqrt_ct's r for a non-square gx1 (r^2 = gx1 / g) into sqrt(Z gx1)
-        const Fe<P> zg = fe_mul(K.z, fe_sqrt_gpow<P>(h_sqrt_table<P>(), 0));
-        ok = h_sqrt(zg, K.c) && fe_eq(fe_sqr(K.c), zg);
-    }
-};
-template <class C>
-static const H2cHost<C>& h2c_host() {
-    static const H2cHost<C> v;
-    return v;
-}
-
 // the ctx's device copy of g^(2^i), i <= S, of one field (shared with csrc/sqrt_decompress.hip through ctx->sqrt_tbl)
 template <class P>
 static int sqrt_table(bzh_ctx* ctx, const uint32_t** out) {

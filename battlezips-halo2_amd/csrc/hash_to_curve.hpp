@@ -2,8 +2,11 @@
 // csrc/hash_to_curve.hip's kernels run one lane per message is what its host path (ctx == NULL) runs in a loop.
 //   h2c_hash_to_field  expand_message_xmd over BLAKE2b-512 (len_in_bytes = 128, no personalisation) -> u0, u1 (Montgomery)
 //   h2c_map            iso_map(swu(u0) + swu(u1)) -> affine point (Montgomery) and a BZH_POINT_* status
-// csrc/params.hip's hash_to_curve_t (on bzc::Fp, one message at a time) is the same function and stays the comparator.
+// csrc/params.hip's hash_to_curve_t (bzh_hash_to_curve, bzh_params_generators: one message of any length at a time) streams its
+// own expand_message_xmd and then runs h2f_os2ip and h2c_map from here with the same constants (h2c_host): there is one map.
 #pragma once
+#include <string>
+
 #include "host_field.hpp"
 
 namespace bzh {
@@ -260,6 +263,41 @@ BZH_HD uint8_t h2c_map(const Fe<P>& u0, const Fe<P>& u1, const H2cConsts<P>& K, 
     ox = fe_csel(inf, zero, fe_mul(K.s2, X));
     oy = fe_csel(inf, zero, fe_mul(K.s3, Y));
     return inf ? BZH_POINT_IDENTITY : BZH_POINT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// host side: the domain separation tag and the map's constants, made once per curve
+// ---------------------------------------------------------------------------
+template <class C>
+inline std::string h2c_dst(const char* prefix) {
+    return std::string(prefix) + "-" + (C::id == BZH_CURVE_PALLAS ? "pallas" : "vesta") + "_XMD:BLAKE2b_SSWU_RO_";
+}
+// the iso-curve and isogeny constants, canonical limbs: A, B, Z, x0, t, u, 1/9, 1/27.  csrc/params.hip derives them and checks
+// them (Iso<F>); BZH_E_HIP if that self-check fails
+int h2c_iso_constants(int curve, uint64_t out[8][4]);
+template <class C>
+struct H2cHost {
+    H2cConsts<typename C::Base> K;
+    bool ok = false;
+    H2cHost() {
+        using P = typename C::Base;
+        uint64_t raw[8][4];
+        if (h2c_iso_constants(C::id, raw) != BZH_OK) return;
+        Fe<P> v[8];
+        for (int i = 0; i < 8; i++) v[i] = fe_from_u64<P>(raw[i], BZH_FORM_CANONICAL);
+        K.a = v[0], K.b = v[1], K.z = v[2], K.x0 = v[3], K.t = v[4], K.u = v[5], K.s2 = v[6], K.s3 = v[7];
+        const Fe<P> ai = fe_inv(K.a);
+        K.mba = fe_mul(fe_neg(K.b), ai);
+        K.bza = fe_mul(K.b, fe_mul(fe_inv(K.z), ai));
+        // Z and g are non-squares, so Z g has a root; it turns fe_sqrt_ct's r for a non-square gx1 (r^2 = gx1 / g) into sqrt(Z gx1)
+        const Fe<P> zg = fe_mul(K.z, fe_sqrt_gpow<P>(h_sqrt_table<P>(), 0));
+        ok = h_sqrt(zg, K.c) && fe_eq(fe_sqr(K.c), zg);
+    }
+};
+template <class C>
+inline const H2cHost<C>& h2c_host() {
+    static const H2cHost<C> v;
+    return v;
 }
 
 }  // namespace bzh

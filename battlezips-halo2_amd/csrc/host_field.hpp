@@ -1,9 +1,11 @@
 // Host-side field and curve helpers of the library (portable Fe<P> arithmetic, csrc/field.cuh's host product) and the
 // dispatch from a runtime field / curve id (include/bzh2.h) to the parameter pack: the one home of the per-field constants,
-// limb marshalling, roots of unity, the square root, batch inversion, Jacobian -> affine and point (de)compression.
+// limb marshalling, roots of unity, the square root, the Jacobi symbol, batch inversion, interpolation, Jacobian / XYZZ -> affine
+// and point (de)compression.  The circuit front end's value types (csrc/circuit/hostfield.hpp) forward to it.
 // Host only; Montgomery form unless noted.
 #pragma once
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "../../include/bzh2.h"
@@ -175,8 +177,9 @@ inline Fe<P> h_omega(unsigned log_n) {
 // ---------------------------------------------------------------------------
 // square root, host and device (csrc/sqrt_decompress.hip runs the same function, one lane per element)
 //
-// The root is the one pasta_curves 0.4.1's `sqrt` returns (circuit/hostfield.hpp states the choice): with p - 1 = 2^S T,
-// g = gen^T and t in [0, 2^S) such that u^T g^t = 1 -- t is even exactly when u is a square -- it is u^((T+1)/2) g^(t/2).
+// The root is the one pasta_curves 0.4.1's table-based `sqrt` (Sarkar) returns: with p - 1 = 2^S T, g = gen^T and t in [0, 2^S)
+// such that u^T g^t = 1 -- t is even exactly when u is a square -- it is u^((T+1)/2) g^(t/2).  This fixes WHICH of the two roots
+// the circuit's fixed-base `u` tables hold; the sampled U rows of tests/golden/fixed_bases.json pin it.
 //   * v = u^((T-1)/2) by 3-bit fixed windows over the compile-time exponent p >> (S + 1); then w = v u = u^((T+1)/2) and
 //     x = w v = u^T, so no inversion is needed.
 //   * t bit by bit from the bottom, in two halves (Pohlig-Hellman): x^(2^HI) has order dividing 2^LO and gives the low LO bits
@@ -302,6 +305,52 @@ inline bool h_sqrt(const Fe<P>& a, Fe<P>& out) {
     out = r;
     return true;
 }
+// Jacobi symbol (a / p) of a CANONICAL a (plain limbs below p, not Montgomery) by the binary algorithm: +1 a non-zero square,
+// -1 a non-square, 0 zero.  Shifts and subtractions only, where a square root costs ~600 products: the circuit's fixed-base
+// tables ask it per table entry (the search for z, and the check of a cached table).
+template <class P>
+inline int h_jacobi(const Fe<P>& canonical) {
+    uint64_t a[4], n[4];
+    Fe<P> p;
+    for (int i = 0; i < 8; i++) p.l[i] = P::mod(i);
+    fe_to_u64<P>(a, canonical);
+    fe_to_u64<P>(n, p);
+    auto is_zero = [](const uint64_t* x) { return (x[0] | x[1] | x[2] | x[3]) == 0; };
+    auto shr = [](uint64_t* x, unsigned s) {
+        for (; s >= 64; s -= 64) x[0] = x[1], x[1] = x[2], x[2] = x[3], x[3] = 0;
+        if (s) {
+            for (int i = 0; i < 3; i++) x[i] = (x[i] >> s) | (x[i + 1] << (64 - s));
+            x[3] >>= s;
+        }
+    };
+    auto ctz = [](const uint64_t* x) {
+        unsigned s = 0;
+        for (int i = 0; i < 4 && !x[i]; i++) s += 64;
+        return s < 256 ? s + (unsigned)__builtin_ctzll(x[s / 64]) : s;
+    };
+    auto less = [](const uint64_t* x, const uint64_t* y) {
+        for (int i = 3; i >= 0; i--)
+            if (x[i] != y[i]) return x[i] < y[i];
+        return false;
+    };
+    int t = 1;
+    while (!is_zero(a)) {
+        const unsigned z = ctz(a);   // (2 / n) = -1 exactly for n = 3, 5 mod 8
+        shr(a, z);
+        if ((z & 1) && ((n[0] & 7) == 3 || (n[0] & 7) == 5)) t = -t;
+        if (less(a, n)) {            // reciprocity: the sign flips when both are 3 mod 4
+            for (int i = 0; i < 4; i++) std::swap(a[i], n[i]);
+            if ((a[0] & 3) == 3 && (n[0] & 3) == 3) t = -t;
+        }
+        uint64_t br = 0;             // a -= n (both odd: a becomes even)
+        for (int i = 0; i < 4; i++) {
+            const uint64_t d = a[i] - n[i] - br;
+            br = a[i] < n[i] || (a[i] == n[i] && br);
+            a[i] = d;
+        }
+    }
+    return (n[0] == 1 && !(n[1] | n[2] | n[3])) ? t : 0;
+}
 
 // ---------------------------------------------------------------------------
 // v[i] <- 1 / v[i], i < n, with ONE field inversion (Montgomery's trick; an inversion is ~12 us on the host).  A zero has no
@@ -367,6 +416,18 @@ inline void h_jac_to_affine(const uint64_t* xyz, size_t n, int in_form, int out_
         const Fe<P> zi2 = fe_sqr(zi[i]), zi3 = fe_mul(zi2, zi[i]);
         fe_to_u64<P>(xy + 8 * i, fe_mul(fe_from_u64<P>(xyz + 12 * i, in_form), zi2), out_form);
         fe_to_u64<P>(xy + 8 * i + 4, fe_mul(fe_from_u64<P>(xyz + 12 * i + 4, in_form), zi3), out_form);
+    }
+}
+// n XYZZ points -> affine with one inversion: i = 1 / (ZZ ZZZ) gives 1 / ZZ = i ZZZ and 1 / ZZZ = i ZZ; the identity (ZZ = 0)
+// maps to (0, 0)
+template <class P>
+inline void h_xyzz_to_affine(const Xyzz<P>* v, size_t n, Affine<P>* out) {
+    std::vector<Fe<P>> zi(n);
+    for (size_t i = 0; i < n; i++) zi[i] = fe_mul(v[i].zz, v[i].zzz);
+    h_batch_invert(zi.data(), n, true);
+    for (size_t i = 0; i < n; i++) {
+        out[i].x = fe_mul(v[i].x, fe_mul(zi[i], v[i].zzz));
+        out[i].y = fe_mul(v[i].y, fe_mul(zi[i], v[i].zz));
     }
 }
 // pasta_curves to_bytes: x little-endian, bit 255 = parity of y; the identity (0, 0) = zeros

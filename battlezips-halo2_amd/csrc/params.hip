@@ -29,9 +29,11 @@
 #include "circuit/hostfield.hpp"
 #include "ctx.hpp"
 #include "curve.cuh"
+#include "hash_to_curve.hpp"
 
 namespace {
 
+using namespace bzh;
 using bzc::Fp;
 using bzc::Fq;
 
@@ -43,13 +45,11 @@ template <class F>
 struct IsoParams;
 template <>
 struct IsoParams<Fp> {   // Pallas (base field Fp)
-    static constexpr const char* curve_id = "pallas";
     static constexpr uint64_t A[4] = {0x92bb4b0b657a014bull, 0xb74134581a27a59full, 0x49be2d7258370742ull, 0x18354a2eb0ea8c9cull};
     static constexpr uint64_t X0[4] = {0x6a57031b4ba19471ull, 0x4301a71d1ff0c7cdull, 0x52cfc0198fdb5ac3ull, 0x115468c111fb3180ull};
 };
 template <>
 struct IsoParams<Fq> {   // Vesta (base field Fq)
-    static constexpr const char* curve_id = "vesta";
     static constexpr uint64_t A[4] = {0xc515ad7242eaa6b1ull, 0x9673928c7d01b212ull, 0x81639c4d96f78773ull, 0x267f9b2ee592271aull};
     static constexpr uint64_t X0[4] = {0xea8f4dd1286f2e8cull, 0xbf4c98bd6fef5204ull, 0x75d5c33ad251d4a6ull, 0x1ae90dbd54bf6d15ull};
 };
@@ -83,88 +83,21 @@ static const Iso<F>& iso() {
     return v;
 }
 
-template <class F>
-struct Pt {
-    F x, y;
-    bool inf = false;
-};
-template <class F>
-static Pt<F> iso_add(const Pt<F>& p, const Pt<F>& q) {   // on y^2 = x^3 + a x + b
-    if (p.inf) return q;
-    if (q.inf) return p;
-    F lambda;
-    if (p.x == q.x) {
-        if (p.y != q.y || p.y.is_zero()) return Pt<F>{F::zero(), F::zero(), true};
-        lambda = (F::from_u64(3) * p.x.sqr() + iso<F>().a) * p.y.dbl().inv();
-    } else {
-        lambda = (q.y - p.y) * (q.x - p.x).inv();
-    }
-    Pt<F> r;
-    r.x = lambda.sqr() - p.x - q.x;
-    r.y = lambda * (p.x - r.x) - p.y;
-    return r;
-}
-// simplified SWU (RFC 9380 6.6.2, AB != 0) onto the iso-curve
-template <class F>
-static Pt<F> map_to_curve_simple_swu(const F& uu) {
-    const Iso<F>& I = iso<F>();
-    const F zu2 = I.z * uu.sqr();
-    const F ta = zu2.sqr() + zu2;
-    F x1;
-    if (ta.is_zero()) x1 = I.b * (I.z * I.a).inv();
-    else x1 = (-I.b) * I.a.inv() * (F::one() + ta.inv());
-    const F gx1 = x1.sqr() * x1 + I.a * x1 + I.b;
-    Pt<F> r;
-    F y;
-    if (gx1.sqrt(&y)) {
-        r.x = x1;
-    } else {
-        r.x = zu2 * x1;
-        const F gx2 = r.x.sqr() * r.x + I.a * r.x + I.b;
-        if (!gx2.sqrt(&y)) y = F::zero();   // cannot happen: one of gx1, gx2 is a square
-    }
-    if (uu.is_odd() != y.is_odd()) y = -y;   // sgn0(u) == sgn0(y)
-    r.y = y;
-    return r;
-}
-// the normalised 3-isogeny (Velu, then (X, Y) -> (X / 9, Y / 27)) from the iso-curve to y^2 = x^3 + 5
-template <class F>
-static Pt<F> iso_map(const Pt<F>& p) {
-    if (p.inf) return p;
-    const Iso<F>& I = iso<F>();
-    const F d = p.x - I.x0;
-    if (d.is_zero()) return Pt<F>{F::zero(), F::zero(), true};
-    const F di = d.inv(), di2 = di.sqr();
-    const F X = p.x + I.t * di + I.u * di2;
-    const F Y = p.y * (F::one() - I.t * di2 - I.u.dbl() * di2 * di);
-    return Pt<F>{I.s2 * X, I.s3 * Y, false};
-}
-template <class F>
-static F field_from_be64(const uint8_t* b) {   // OS2IP of 64 big-endian bytes, mod p
-    uint64_t lo[4], hi[4];
-    for (int i = 0; i < 4; i++) {
-        uint64_t l = 0, h = 0;
-        for (int j = 0; j < 8; j++) {
-            l |= (uint64_t)b[63 - (8 * i + j)] << (8 * j);
-            h |= (uint64_t)b[31 - (8 * i + j)] << (8 * j);
-        }
-        lo[i] = l, hi[i] = h;
-    }
-    // any 256-bit x: mul(x, R^2) = x R mod p (Montgomery form of x mod p)
-    const F lom = F::mul(F{{lo[0], lo[1], lo[2], lo[3]}}, F::r2());
-    const F him = F::mul(F::mul(F{{hi[0], hi[1], hi[2], hi[3]}}, F::r2()), F::r2());   // (hi 2^256) R
-    return lom + him;
-}
-// CurveExt::hash_to_curve(domain_prefix)(message), affine; false only for the (never observed) identity result
-template <class F>
-static bool hash_to_curve_t(const std::string& domain_prefix, const uint8_t* msg, size_t len, F* ox, F* oy) {
-    const std::string dst = domain_prefix + "-" + IsoParams<F>::curve_id + "_XMD:BLAKE2b_SSWU_RO_";
+// CurveExt::hash_to_curve(domain_prefix)(message), affine Montgomery: expand_message_xmd streamed over bzh::Blake2b -- a message
+// and a prefix of any length, which the batch plan (H2fPlan, csrc/hash_to_curve.hpp) does not take --, then the two stages the
+// batch and device paths run: h2f_os2ip and h2c_map with h2c_host's constants.  The caller has checked h2c_host<C>().ok.
+// false only for the (never observed) identity result.
+template <class C>
+static bool hash_to_curve_t(const std::string& domain_prefix, const uint8_t* msg, size_t len, Fe<typename C::Base>* ox, Fe<typename C::Base>* oy) {
+    using P = typename C::Base;
+    const std::string dst = h2c_dst<C>(domain_prefix.c_str());
     std::vector<uint8_t> dst_prime(dst.begin(), dst.end());
     dst_prime.push_back((uint8_t)dst.size());
     const uint8_t nopersonal[16] = {0};
-    uint8_t b0[64], b1[64], b2[64];
+    uint8_t b0[64];
+    uint64_t b1[8], b2[8];   // the digests as their eight little-endian words
     {
-        bzh::Blake2b h;
+        Blake2b h;
         h.init(64, nopersonal);
         const uint8_t zpad[128] = {0};
         h.update(zpad, 128);
@@ -175,36 +108,39 @@ static bool hash_to_curve_t(const std::string& domain_prefix, const uint8_t* msg
         h.finalize(b0);
     }
     {
-        bzh::Blake2b h;
+        Blake2b h;
         h.init(64, nopersonal);
         h.update(b0, 64);
         const uint8_t one = 1;
         h.update(&one, 1);
         h.update(dst_prime.data(), dst_prime.size());
-        h.finalize(b1);
+        h.finalize((uint8_t*)b1);
     }
     {
-        bzh::Blake2b h;
+        Blake2b h;
         h.init(64, nopersonal);
         uint8_t x[64];
-        for (int i = 0; i < 64; i++) x[i] = b0[i] ^ b1[i];
+        for (int i = 0; i < 64; i++) x[i] = b0[i] ^ ((const uint8_t*)b1)[i];
         h.update(x, 64);
         const uint8_t two = 2;
         h.update(&two, 1);
         h.update(dst_prime.data(), dst_prime.size());
-        h.finalize(b2);
+        h.finalize((uint8_t*)b2);
     }
-    const F u0 = field_from_be64<F>(b1), u1 = field_from_be64<F>(b2);
-    const Pt<F> r = iso_map(iso_add(map_to_curve_simple_swu(u0), map_to_curve_simple_swu(u1)));
-    if (r.inf) return false;
-    *ox = r.x;
-    *oy = r.y;
-    return true;
+    return h2c_map(h2f_os2ip<P>(b1), h2f_os2ip<P>(b2), h2c_host<C>().K, h_sqrt_table<P>(), *ox, *oy) == BZH_POINT_OK;
+}
+// the same, canonical x || y: BZH_E_RANGE for the identity
+template <class C>
+static int hash_to_curve_canonical(const std::string& domain_prefix, const uint8_t* msg, size_t len, uint64_t* out_xy) {
+    using P = typename C::Base;
+    Fe<P> x, y;
+    if (!hash_to_curve_t<C>(domain_prefix, msg, len, &x, &y)) return BZH_E_RANGE;
+    fe_to_u64<P>(out_xy, x, BZH_FORM_CANONICAL);
+    fe_to_u64<P>(out_xy + 4, y, BZH_FORM_CANONICAL);
+    return BZH_OK;
 }
 
 // ---- group FFT (device) ------------------------------------------------------------------------------------------
-using namespace bzh;
-
 template <class C>
 __device__ Xyzz<typename C::Base> point_scalar_mul(const Xyzz<typename C::Base>& p, const uint32_t* k /* 8 canonical limbs */) {
     using P = typename C::Base;
@@ -434,27 +370,17 @@ extern "C" {
 
 int bzh_hash_to_curve(int curve, const char* domain_prefix, const uint8_t* msg, size_t len, uint64_t* out_xy) {
     if (!domain_prefix || (!msg && len) || !out_xy) return BZH_E_ARG;
-    if (curve == BZH_CURVE_PALLAS) {
-        if (!iso<Fp>().ok) return BZH_E_HIP;
-        Fp x, y;
-        if (!hash_to_curve_t<Fp>(domain_prefix, msg, len, &x, &y)) return BZH_E_RANGE;
-        x.to_limbs(out_xy), y.to_limbs(out_xy + 4);
-        return BZH_OK;
-    }
-    if (curve == BZH_CURVE_VESTA) {
-        if (!iso<Fq>().ok) return BZH_E_HIP;
-        Fq x, y;
-        if (!hash_to_curve_t<Fq>(domain_prefix, msg, len, &x, &y)) return BZH_E_RANGE;
-        x.to_limbs(out_xy), y.to_limbs(out_xy + 4);
-        return BZH_OK;
-    }
-    return BZH_E_ARG;
+    return with_pasta_curve(curve, [&](auto c) -> int {
+        using C = decltype(c);
+        if (!h2c_host<C>().ok) return BZH_E_HIP;
+        return hash_to_curve_canonical<C>(domain_prefix, msg, len, out_xy);
+    });
 }
 
 // g, w, u of Params::new(k) on the host (no device): g_xy = n x 8 canonical limbs
 int bzh_params_generators(unsigned k, uint64_t* g_xy, uint64_t* w_xy, uint64_t* u_xy, unsigned threads) {
     if (k > 24 || (!g_xy && !w_xy && !u_xy)) return BZH_E_ARG;
-    if (!iso<Fq>().ok) return BZH_E_HIP;
+    if (!h2c_host<VestaCurve>().ok) return BZH_E_HIP;
     const size_t n = (size_t)1 << k;
     const std::string domain = "Halo2-Parameters";
     std::atomic<int> bad{0};
@@ -468,12 +394,7 @@ int bzh_params_generators(unsigned k, uint64_t* g_xy, uint64_t* w_xy, uint64_t* 
                 if (lo >= n) return;
                 for (size_t i = lo; i < std::min(n, lo + 256); i++) {
                     const uint8_t msg[5] = {0, (uint8_t)i, (uint8_t)(i >> 8), (uint8_t)(i >> 16), (uint8_t)(i >> 24)};
-                    Fq x, y;
-                    if (!hash_to_curve_t<Fq>(domain, msg, 5, &x, &y)) {
-                        bad = 1;
-                        continue;
-                    }
-                    x.to_limbs(g_xy + 8 * i), y.to_limbs(g_xy + 8 * i + 4);
+                    if (hash_to_curve_canonical<VestaCurve>(domain, msg, 5, g_xy + 8 * i)) bad = 1;
                 }
             }
         };
@@ -486,9 +407,7 @@ int bzh_params_generators(unsigned k, uint64_t* g_xy, uint64_t* w_xy, uint64_t* 
         uint64_t* out = which == 1 ? w_xy : u_xy;
         if (!out) continue;
         const uint8_t msg[1] = {(uint8_t)which};
-        Fq x, y;
-        if (!hash_to_curve_t<Fq>(domain, msg, 1, &x, &y)) return BZH_E_RANGE;
-        x.to_limbs(out), y.to_limbs(out + 4);
+        BZH_TRY(hash_to_curve_canonical<VestaCurve>(domain, msg, 1, out));
     }
     return bad ? BZH_E_RANGE : BZH_OK;
 }

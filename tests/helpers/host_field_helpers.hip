@@ -1,5 +1,5 @@
 // Test program (not product code): the host helpers of csrc/host_field.hpp -- square root, point decompression, roots of
-// unity, batch inversion, interpolation, Jacobian -> affine -- driven by a command file, one command per line, one answer line each.
+// unity, the Jacobi symbol, batch inversion, interpolation, Jacobian / XYZZ -> affine -- driven by a command file, one command per line, one answer line each.
 // tests/test_host_field_cpu.py writes the commands and compares the answers with oracle/pasta.py.  All values are 64 hex
 // digits, big-endian, canonical unless a form says otherwise.
 //   sqrt F a                         -> "ok r" | "none"
@@ -8,6 +8,8 @@
 //   binv F skip_zeros n v_0 .. v_n-1 -> "ok 1/v_0 .." | "fail"
 //   interp F np x_0 .. x_np-1 y_0 .. y_np-1 -> "ok c_0 .. c_np-1" (coefficients, lowest first) | "fail" (two points coincide)
 //   jac C in_form out_form n X Y Z.. -> "x y .."                      (limbs in the given forms, 0 canonical, 1 Montgomery)
+//   jacobi F a                       -> "1" | "-1" | "0"
+//   xyzz C n X Y ZZ ZZZ ..           -> "x y .."                      (h_xyzz_to_affine)
 #include <cstdio>
 #include <fstream>
 #include <iostream>
@@ -127,6 +129,26 @@ int main(int argc, char** argv) {
                 }
                 h_jac_to_affine<typename decltype(c)::Base>(xyz.data(), n, in_form, out_form, xy.data());
                 for (size_t i = 0; i < 2 * n; i++) out += (i ? " " : "") + hex(&xy[4 * i]);
+                return BZH_OK;
+            });
+        } else if (cmd == "jacobi") {
+            rc = with_field(id, [&](auto p) {
+                using P = decltype(p);
+                out = std::to_string(h_jacobi(fe_from_mont(read_fe<P>(in))));
+                return BZH_OK;
+            });
+        } else if (cmd == "xyzz") {
+            rc = with_curve(id, [&](auto c) {
+                using P = typename decltype(c)::Base;
+                size_t n = 0;
+                in >> n;
+                std::vector<Xyzz<P>> v(n);
+                for (auto& e : v) e.x = read_fe<P>(in), e.y = read_fe<P>(in), e.zz = read_fe<P>(in), e.zzz = read_fe<P>(in);
+                std::vector<Affine<P>> a(n + 1);
+                a[n].x = a[n].y = fe_one<P>();   // a guard past the output
+                h_xyzz_to_affine(v.data(), n, a.data());
+                if (!fe_eq(a[n].x, fe_one<P>()) || !fe_eq(a[n].y, fe_one<P>())) out = "wrote-past-the-end ";
+                for (size_t i = 0; i < n; i++) out += (i ? " " : "") + show(a[i].x) + " " + show(a[i].y);
                 return BZH_OK;
             });
         }

@@ -1,7 +1,8 @@
 """Batched hash-to-curve on the host (ctx == NULL): bzh_hash_to_curve_batch and bzh_map_to_curve_batch run the functions of
 csrc/hash_to_curve.hpp that the device kernels run one lane per message.  Checked against the oracle (oracle/pasta.py), against
-the one-message host function bzh_hash_to_curve (another field library, csrc/circuit/hostfield.hpp) and the reference's two
-`generator` known answers, at the BLAKE2b block boundaries of expand_message_xmd and on the operands of every select of the map."""
+the one-message host function bzh_hash_to_curve (its own streaming expand_message_xmd for messages and prefixes of any length,
+then the same map) and the reference's two `generator` known answers, at the BLAKE2b block boundaries of expand_message_xmd and
+on the operands of every select of the map."""
 import ctypes
 import json
 import os
@@ -69,6 +70,26 @@ def test_host_path_at_the_prefix_lengths_around_one_block(cid):
             xy, _ = Pm.hash_to_curve_batch(None, cid, prefix, msgs, form)
             assert xy.tobytes() == K.points_array(want, p, form).tobytes(), (cid, plen, form)
     assert blocks == {1, 2}       # the second and third hash take one block and two
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_one_message_function_at_lengths_the_batch_plan_cannot_take(cid):
+    """bzh_hash_to_curve under a 200-byte domain prefix at message lengths 0, 1, 127, 128, 129 and 300 against the oracle: the
+    streaming expand_message_xmd keeps the lengths past the batch plan's 128 bytes; up to 128 bytes the batch gives the same point"""
+    import bzh2
+    import pasta as O
+    from bzh2 import params as Pm
+    prefix = ("battlezips:" + "long-domain-prefix/" * 10)[:200]
+    assert len(prefix) == 200
+    for length in (0, 1, 127, 128, 129, 300):
+        msg = K.messages(length, 2, seed=length)[1]
+        assert len(msg) == length
+        want = K.hashed(cid, prefix, msg)
+        assert O.CURVE_BY_ID[cid].is_on_curve(want)
+        assert Pm.hash_to_curve(cid, prefix, msg) == want, (cid, length)
+        if length <= 128:
+            xy, st = Pm.hash_to_curve_batch(None, cid, prefix, [msg])
+            assert st.tolist() == [bzh2.POINT_OK] and _ints(xy[0]) == want, (cid, length)
 
 
 def test_the_references_generators_come_out_as_one_batch_of_two():

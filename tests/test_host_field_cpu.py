@@ -2,8 +2,8 @@
 algebra): csrc/field.cuh gives the host pass a 64-bit-limb Montgomery product.  tests/helpers/host_field_check.hip compiles
 against the library's own header and compares it with the 32-bit CIOS on all four fields (host code only: no GPU needed).  tests/helpers/host_field_edges.hip runs
 the host fe_add / fe_sub / fe_neg and both host products over the adversarial operand table of tests/helpers/field_edges.py.
-tests/helpers/host_field_helpers.hip drives the helpers of csrc/host_field.hpp (square root, point decompression, roots of unity,
-batch inversion, interpolation, Jacobian -> affine), which the library otherwise reaches only around GPU work, against oracle/pasta.py."""
+tests/helpers/host_field_helpers.hip drives the helpers of csrc/host_field.hpp (square root, Jacobi symbol, point decompression,
+roots of unity, batch inversion, interpolation, Jacobian / XYZZ -> affine), which the library otherwise reaches only around GPU work, against oracle/pasta.py."""
 import os
 import shutil
 import subprocess
@@ -300,3 +300,79 @@ def test_host_jacobian_to_affine_with_identities(helper_program, cid):
         assert [int(x, 16) for x in g] == [w * R % p if fo else w for w in want], "curve %d forms %d -> %d, %d points" % (cid, fi, fo, len(b))
     # the non-identity points of the first batch come back as the oracle's own affine points
     assert [int(x, 16) for x in got[0]] == [c for pt in pts for c in pt]
+
+
+@pytest.mark.parametrize("fid", [0, 1])
+def test_host_jacobi_symbol_against_eulers_criterion(helper_program, fid):
+    """h_jacobi (the circuit's fixed-base tables ask it per entry) on 0, 1, p - 1, the edge operands, and the generator of the
+    2-Sylow subgroup (never a square) and its square: +1, -1 or 0 exactly as a^((p-1)/2) says"""
+    from helpers import field_edges as E
+    O = _oracle()
+    F = O.FIELD_BY_ID[fid]
+    p = F.p
+    root = F.omega(F.S)
+    assert pow(root, 1 << (F.S - 1), p) == p - 1        # order exactly 2^S
+    vals = [0, 1, p - 1, root, root * root % p] + E.edge_values(p)
+    want = [{0: 0, 1: 1, p - 1: -1}[pow(a, (p - 1) // 2, p)] for a in vals]
+    assert want[:5] == [0, 1, 1, -1, 1] and want.count(-1) >= 64 and want.count(1) >= 64
+    got = helper_program(["jacobi %d %s" % (fid, _hx(a)) for a in vals])
+    assert [int(g[0]) for g in got] == want, [hex(a) for a, w, g in zip(vals, want, got) if int(g[0]) != w][:4]
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_host_xyzz_to_affine_with_one_shared_inversion(helper_program, cid):
+    """h_xyzz_to_affine over a vector holding the identity (ZZ = 0 with arbitrary X, Y), a point, its negative and the doubled
+    point, each scaled by another z (X = x z^2, Y = y z^3, ZZ = z^2, ZZZ = z^3), z from the edge operands and p - 1; the identity
+    first, in the middle, last and alone, and the empty vector"""
+    import random
+
+    from helpers import field_edges as E
+    O = _oracle()
+    cv = O.CURVE_BY_ID[cid]
+    p = cv.p
+    rng = random.Random(500 + cid)
+    zs = [z for z in E.edge_values(p) if z] + [p - 1]
+    pt = cv.random_point(rng)
+    assert cv.is_on_curve(cv.add(pt, pt)) and cv.add(pt, cv.neg(pt)) is None
+    quad = [None, pt, cv.neg(pt), cv.add(pt, pt)]
+
+    def xyzz(q, z):
+        if q is None:
+            return (rng.randrange(p), rng.randrange(p), 0, 0)
+        return (q[0] * z * z % p, q[1] * z ** 3 % p, z * z % p, z ** 3 % p)
+    batches = [quad, quad[1:] + [None], [pt, None, None, cv.neg(pt)], [None], [cv.add(pt, pt)], []]
+    batches += [[quad[(i + j) % 4] for j in range(4)] for i in range(8)]
+    cases = [[(q, zs[(7 * bi + 3 * i) % len(zs)] if bi else zs[-1 - i]) for i, q in enumerate(b)] for bi, b in enumerate(batches)]
+    got = helper_program(["xyzz %d %d %s" % (cid, len(b), " ".join(_hx(c) for q, z in b for c in xyzz(q, z))) for b in cases])
+    for b, g in zip(cases, got):
+        assert [int(x, 16) for x in g] == [c for q, _ in b for c in (q or (0, 0))], "curve %d, %d points" % (cid, len(b))
+
+
+def test_circuit_value_types_accept_exactly_the_canonical_encodings():
+    """The circuit front end's Fp / Fq (csrc/circuit/hostfield.hpp) read limbs through the library's is_canonical: from_repr
+    (bzh_circuit_set_vk_repr) and from_limbs (bzh_pedersen_commit_host: an Fp message, an Fq trapdoor) take 0 and p - 1 and refuse
+    p, p + 1 and 2^256 - 1 with BZH_E_RANGE.  The accepted commitments are the oracle's: [0]V + [0]R is the identity (0, 0), which
+    the window sums reach by adding a point to its negative."""
+    import bzh2
+    from bzh2 import BzhError, circuits as Cm
+    O = _oracle()
+    p, q = O.FP.p, O.FQ.p
+    assert p < q
+    lay = Cm.CircuitLayout(Cm.SHOT, 11)
+    try:
+        for good in (0, p - 1):
+            lay.set_vk_repr(good)
+            assert lay.vk_repr() == (good, False)
+        for bad in (p, p + 1, (1 << 256) - 1):
+            with pytest.raises(BzhError) as e:
+                lay.set_vk_repr(bad)
+            assert e.value.status == bzh2.E_RANGE
+        assert lay.vk_repr() == (p - 1, False)
+    finally:
+        lay.close()
+    for m, t in ((0, 0), (p - 1, q - 1), (0, q - 1), (p - 1, 0)):
+        assert Cm.pedersen_commit_host(m, t) == (O.pedersen_commit(m, t) or (0, 0)), (hex(m), hex(t))
+    for m, t in [(bad, 1) for bad in (p, p + 1, (1 << 256) - 1)] + [(1, bad) for bad in (q, q + 1, (1 << 256) - 1)]:
+        with pytest.raises(BzhError) as e:
+            Cm.pedersen_commit_host(m, t)
+        assert e.value.status == bzh2.E_RANGE, (hex(m), hex(t))
