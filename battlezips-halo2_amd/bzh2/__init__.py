@@ -608,6 +608,139 @@ class Transcript:
             self.h = None
 
 
+# ---- batched transcripts (host-resident or on the device) ----------------------------------------
+EXPORTS += ["bzh_transcript_batch_new", "bzh_transcript_batch_free", "bzh_transcript_batch_common_points",
+            "bzh_transcript_batch_write_points", "bzh_transcript_batch_write_jacobian", "bzh_transcript_batch_common_scalars",
+            "bzh_transcript_batch_write_scalars", "bzh_transcript_batch_squeeze", "bzh_transcript_batch_proofs",
+            "bzh_transcript_batch_status", "bzh_transcript_batch_from_host", "bzh_transcript_batch_to_host"]
+
+
+def _bind_transcript_batch():
+    L = load()
+    vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+    L.bzh_transcript_batch_new.argtypes = [vp, ci, sz, sz, ctypes.POINTER(vp)]
+    L.bzh_transcript_batch_free.argtypes = [vp]
+    for f in ("common_points", "write_points", "write_jacobian", "common_scalars", "write_scalars"):
+        getattr(L, "bzh_transcript_batch_" + f).argtypes = [vp, vp, sz, sz, ci, ci]
+    L.bzh_transcript_batch_squeeze.argtypes = [vp, ci, ci, vp]
+    L.bzh_transcript_batch_proofs.argtypes = [vp, ci, vp, sz, ctypes.POINTER(sz)]
+    L.bzh_transcript_batch_status.argtypes = [vp, vp]
+    L.bzh_transcript_batch_from_host.argtypes = [vp, ctypes.POINTER(vp)]
+    L.bzh_transcript_batch_to_host.argtypes = [vp, ctypes.POINTER(vp)]
+    return L
+
+
+class TranscriptBatch:
+    """`batch` Blake2bWrite + Challenge255 transcripts in lockstep (bzh_transcript_batch_*): on ctx's device, or host-resident
+    (ctx None, the same step code on the host).  `curve` fixes the fields: coordinates in its base field, scalars and challenges
+    in its scalar field.  Every call gives every transcript the same number of items.
+    MEM_HOST: operands are uint64 arrays of shape (batch, n, limbs) -- 8 limbs for an affine point, 12 for a Jacobian point, 4
+    for a scalar --, in `form`; a canonical operand that is not below its modulus raises BzhError E_RANGE and absorbs nothing.
+    MEM_DEVICE: operands are device pointers (ints, 16-byte aligned) with `n` items per transcript, transcript b reading the
+    items b * stride + i (stride defaults to n); the call only enqueues on the ctx's stream."""
+    ITEM_LIMBS = {"common_points": 8, "write_points": 8, "write_jacobian": 12, "common_scalars": 4, "write_scalars": 4}
+
+    def __init__(self, curve: int, batch: int, proof_cap: int, ctx: "Context | None" = None):
+        L = _bind_transcript_batch()
+        self.ctx, self.curve, self.batch, self.proof_cap = ctx, curve, batch, proof_cap
+        self.h = ctypes.c_void_p()
+        rc = L.bzh_transcript_batch_new(ctx.handle if ctx is not None else None, curve, batch, proof_cap, ctypes.byref(self.h))
+        if rc != OK:
+            self.h = None
+            raise BzhError(rc, "bzh_transcript_batch_new", self._detail())
+
+    def _detail(self) -> str:
+        return load().bzh_last_error(self.ctx.handle).decode() if self.ctx is not None and self.ctx.handle is not None else ""
+
+    def _check(self, rc: int, where: str):
+        if rc != OK:
+            raise BzhError(rc, where, self._detail())
+
+    def _absorb(self, op: str, data, form: int, mem: int, n, stride):
+        fn = getattr(_bind_transcript_batch(), "bzh_transcript_batch_" + op)
+        if mem == MEM_DEVICE:
+            assert n is not None
+            ptr = ctypes.c_void_p(int(data))
+        else:
+            a = np.ascontiguousarray(data, dtype=np.uint64).reshape(self.batch, -1, self.ITEM_LIMBS[op])
+            n = a.shape[1]
+            ptr = _vp(a)
+        self._check(fn(self.h, ptr, n, n if stride is None else stride, form, mem), "bzh_transcript_batch_" + op)
+
+    def common_points(self, xy, *, form: int = FORM_CANONICAL, mem: int = MEM_HOST, n: int | None = None, stride: int | None = None):
+        self._absorb("common_points", xy, form, mem, n, stride)
+
+    def write_points(self, xy, *, form: int = FORM_CANONICAL, mem: int = MEM_HOST, n: int | None = None, stride: int | None = None):
+        self._absorb("write_points", xy, form, mem, n, stride)
+
+    def write_jacobian(self, xyz, *, form: int = FORM_CANONICAL, mem: int = MEM_HOST, n: int | None = None, stride: int | None = None):
+        self._absorb("write_jacobian", xyz, form, mem, n, stride)
+
+    def common_scalars(self, s, *, form: int = FORM_CANONICAL, mem: int = MEM_HOST, n: int | None = None, stride: int | None = None):
+        self._absorb("common_scalars", s, form, mem, n, stride)
+
+    def write_scalars(self, s, *, form: int = FORM_CANONICAL, mem: int = MEM_HOST, n: int | None = None, stride: int | None = None):
+        self._absorb("write_scalars", s, form, mem, n, stride)
+
+    def squeeze(self, *, form: int = FORM_CANONICAL, mem: int = MEM_HOST, out: int | None = None):
+        """one challenge per transcript: a (batch, 4) uint64 array in `form`, or, with MEM_DEVICE, into the device pointer `out`
+        (batch x 4 limbs; enqueues only, returns None)"""
+        L = _bind_transcript_batch()
+        if mem == MEM_DEVICE:
+            self._check(L.bzh_transcript_batch_squeeze(self.h, form, mem, ctypes.c_void_p(out) if out else None), "bzh_transcript_batch_squeeze")
+            return None
+        a = np.zeros((self.batch, 4), dtype=np.uint64)
+        self._check(L.bzh_transcript_batch_squeeze(self.h, form, mem, _vp(a)), "bzh_transcript_batch_squeeze")
+        return a
+
+    def proof_len(self) -> int:
+        n = ctypes.c_size_t()
+        self._check(_bind_transcript_batch().bzh_transcript_batch_proofs(self.h, MEM_HOST, None, 0, ctypes.byref(n)), "bzh_transcript_batch_proofs")
+        return n.value
+
+    def proofs(self, *, mem: int = MEM_HOST, out: int | None = None, out_stride: int | None = None):
+        """the proof bytes written so far: a list of `batch` byte strings, or, with MEM_DEVICE, into rows of out_stride bytes at
+        the device pointer `out` (enqueues only; returns the length of each)"""
+        L = _bind_transcript_batch()
+        n = self.proof_len()
+        if mem == MEM_DEVICE:
+            self._check(L.bzh_transcript_batch_proofs(self.h, mem, ctypes.c_void_p(out) if out else None, n if out_stride is None else out_stride,
+                                                      None), "bzh_transcript_batch_proofs")
+            return n
+        a = np.zeros((self.batch, max(n, 1)), dtype=np.uint8)
+        self._check(L.bzh_transcript_batch_proofs(self.h, mem, _vp(a), a.shape[1], None), "bzh_transcript_batch_proofs")
+        return [a[b, :n].tobytes() for b in range(self.batch)]
+
+    def status(self) -> np.ndarray:
+        """(batch,) uint8: the largest POINT_* status each transcript has seen; waits for the stream"""
+        st = np.zeros(self.batch, dtype=np.uint8)
+        self._check(_bind_transcript_batch().bzh_transcript_batch_status(self.h, _vp(st)), "bzh_transcript_batch_status")
+        return st
+
+    def _handles(self, transcripts):
+        assert len(transcripts) == self.batch
+        return (ctypes.c_void_p * self.batch)(*[t.h for t in transcripts])
+
+    def from_host(self, transcripts):
+        """take over the state and proof bytes of `batch` Transcript objects (bzh_transcript_batch_from_host)"""
+        self._check(_bind_transcript_batch().bzh_transcript_batch_from_host(self.h, self._handles(transcripts)), "bzh_transcript_batch_from_host")
+
+    def to_host(self, transcripts):
+        """overwrite the state and proof bytes of `batch` Transcript objects (bzh_transcript_batch_to_host)"""
+        self._check(_bind_transcript_batch().bzh_transcript_batch_to_host(self.h, self._handles(transcripts)), "bzh_transcript_batch_to_host")
+
+    def close(self):
+        if self.h is not None:
+            load().bzh_transcript_batch_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 # ---- IPA opening --------------------------------------------------------------------------------
 EXPORTS += ["bzh_ipa_open", "bzh_ipa_open_batch", "bzh_ipa_verify"]
 EXPORTS += ["bzh_pk_create", "bzh_pk_free", "bzh_pk_set_lagrange", "bzh_pk_quotient_stats", "bzh_pk_quotient_source", "bzh_pk_set_quotient_module", "bzh_pk_info", "bzh_prove_batch", "bzh_prove_batch_seeded", "bzh_rng_expand", "bzh_verify_batch",

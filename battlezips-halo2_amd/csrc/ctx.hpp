@@ -336,6 +336,9 @@ bool point_decompress(int curve, const uint8_t* in, uint64_t* xy_canonical);
 // BZH_POINT_* byte each; zeros unless BZH_POINT_OK.
 int batch_sqrt_run(bzh_ctx* ctx, int field, uint32_t* d_data, size_t count, int form, uint8_t* d_status);
 int decompress_run(bzh_ctx* ctx, int curve, const uint32_t* d_in, size_t n, int form, uint32_t* d_out_xy, uint8_t* d_status);
+// normalize_compress.hip (device pointers, 16-byte aligned; enqueues only): bzh_batch_normalize's launch.  d_out_xy, d_out32 and
+// d_status may each be null, d_out_xy and d_out32 not both.
+int normalize_run(bzh_ctx* ctx, int curve, const void* d_xyz, size_t n, int form, void* d_out_xy, void* d_out32, uint8_t* d_status);
 // hash_to_curve.hip: Params::new's g[first .. first + count) as Montgomery affine points and one BZH_POINT_* byte each, into device
 // memory (16-byte aligned); enqueues only, the caller holds ctx->mu.  ev: null, or three events recorded before k_hash_to_field,
 // between the two kernels and after k_map_to_curve.

@@ -45,8 +45,10 @@ static bool valid_mem(int m) { return m == BZH_MEM_HOST || m == BZH_MEM_DEVICE; 
 static bool valid_curve(int c) { return c >= BZH_CURVE_VESTA && c <= BZH_CURVE_BN254; }
 constexpr size_t kMaxCount = (size_t)1 << 28;   // the byte offsets and the grid stay far inside their types
 
-// device pointers, 16-byte aligned; enqueues only
-static int normalize_run(bzh_ctx* ctx, int curve, const void* d_xyz, size_t n, int form, void* d_out_xy, void* d_out32, uint8_t* d_status) {
+}  // namespace
+
+// device pointers, 16-byte aligned; enqueues only (declared in ctx.hpp: csrc/transcript_batch.hip's write_jacobian runs it too)
+int normalize_run(bzh_ctx* ctx, int curve, const void* d_xyz, size_t n, int form, void* d_out_xy, void* d_out32, uint8_t* d_status) {
     NormIo io{d_xyz, d_out_xy, d_out32, d_status, n, 0, 0, form == BZH_FORM_CANONICAL ? 1 : 0};
     normalize_plan(n, &io.lanes, &io.chain);
     return with_curve(curve, [&](auto c) -> int {
@@ -58,6 +60,8 @@ static int normalize_run(bzh_ctx* ctx, int curve, const void* d_xyz, size_t n, i
         return BZH_OK;
     });
 }
+namespace {
+
 static int compress_run(bzh_ctx* ctx, int curve, const uint32_t* d_xy, size_t n, int form, uint32_t* d_out32) {
     return with_curve(curve, [&](auto c) -> int {
         {

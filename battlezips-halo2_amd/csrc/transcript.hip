@@ -11,17 +11,11 @@
 #include <new>
 #include <vector>
 
-#include "blake2b.hpp"
 #include "host_field.hpp"
+#include "transcript.hpp"
 #include "../../include/bzh2.h"
 
 using bzh::Blake2b;
-
-struct bzh_transcript {
-    Blake2b state;
-    int field;
-    std::vector<uint8_t> proof;
-};
 
 extern "C" {
 

@@ -634,6 +634,47 @@ int bzh_batch_normalize(bzh_ctx* ctx, int curve, const uint64_t* xyz, size_t n, 
                         uint8_t* status);
 int bzh_affine_compress_batch(bzh_ctx* ctx, int curve, const uint64_t* xy, size_t n, int form, int mem, uint8_t* out32);
 int bzh_batch_normalize_plan(size_t n, size_t* lanes, size_t* chain);
+/* ---- Batched Fiat-Shamir transcripts on the device (csrc/transcript_batch.hip): `batch` transcripts of
+ * transcript::{Blake2bWrite, Challenge255} in lockstep, resident in HBM -- the step the points of bzh_msm are normalised for.
+ * They absorb from device memory and squeeze into device memory, one launch per step for the whole batch:
+ *     bzh_msm (BZH_MEM_DEVICE output)  ->  bzh_transcript_batch_write_jacobian  ->  bzh_transcript_batch_squeeze
+ * with no read-back in between.  Not used by bzh_prove_batch, bzh_ipa_open(_batch) or the verifier.
+ * Conventions: those of bzh_batch_normalize.  `mem` applies to every data pointer of a call; device buffers are 16-byte aligned;
+ * with BZH_MEM_DEVICE a call only enqueues on the ctx's stream; count == 0 returns BZH_OK.  `curve` (Vesta, Pallas, BN254 G1)
+ * fixes both fields: coordinates are in the base field, scalars and challenges in the scalar field.  Every call gives every
+ * transcript the same number of items: transcript b reads the items b * stride + i, i < count, stride >= count (in items).
+ *   _new             ctx == NULL makes a host-resident batch: it takes BZH_MEM_HOST only and runs the same step code on the host.
+ *                    proof_cap: the most proof bytes one transcript may hold.  Free the batch before its ctx.
+ *   _common_points   absorb affine points x || y (8 limbs, `form`) as 0x01 || x || y;  _write_points also appends to_bytes
+ *   _write_jacobian  the same for Jacobian points X || Y || Z (12 limbs): bzh_batch_normalize's launch into the batch's own
+ *                    scratch, then _write_points.  Device operands are normalised as the whole span they lie in, gaps included.
+ *   _common_scalars  absorb scalars (4 limbs, `form`) as 0x02 || repr;  _write_scalars also appends the repr
+ *   _squeeze         absorb 0x00; out: batch x 4 limbs, the digest of a copy of the state as a 512-bit integer mod the scalar field
+ *   _proofs          *len (may be NULL) = the proof bytes per transcript; out (may be NULL): batch rows of out_stride >= *len bytes
+ *   _status          host, batch bytes, waits for the stream: per transcript the largest bzh_point_status seen (sticky) --
+ *                    BZH_POINT_IDENTITY: a point (0, 0) was absorbed (hashed as 64 zero bytes, as bzh_transcript_common_point
+ *                    does; upstream refuses it); BZH_POINT_INVALID: a canonical device operand was not below its modulus
+ *                    (hashed as zeros).  Host operands not below the modulus are checked first: BZH_E_RANGE, nothing absorbed.
+ *   _from_host       load the state and proof bytes of `batch` bzh_transcript objects (statuses restart at BZH_POINT_OK);
+ *                    BZH_E_ARG if their absorbed or proof lengths differ from each other, their challenge field is not the
+ *                    curve's scalar field, or a proof is longer than proof_cap.   _to_host  overwrites the objects' state and
+ *                    proof bytes: together they let a caller cross between the two kinds in the middle of a proof.
+ * BZH_E_RANGE: a write past proof_cap (nothing is absorbed).  BZH_E_ARG: a NULL batch or pointer, unknown curve, form or mem,
+ * stride < count, batch == 0, BZH_MEM_DEVICE on a host-resident batch or with a misaligned buffer.  Every argument error
+ * leaves the batch as it was. */
+typedef struct bzh_transcript_batch bzh_transcript_batch;
+int bzh_transcript_batch_new(bzh_ctx* ctx, int curve, size_t batch, size_t proof_cap, bzh_transcript_batch** out);
+int bzh_transcript_batch_free(bzh_transcript_batch* tb);
+int bzh_transcript_batch_common_points(bzh_transcript_batch* tb, const uint64_t* xy, size_t count, size_t stride, int form, int mem);
+int bzh_transcript_batch_write_points(bzh_transcript_batch* tb, const uint64_t* xy, size_t count, size_t stride, int form, int mem);
+int bzh_transcript_batch_write_jacobian(bzh_transcript_batch* tb, const uint64_t* xyz, size_t count, size_t stride, int form, int mem);
+int bzh_transcript_batch_common_scalars(bzh_transcript_batch* tb, const uint64_t* s, size_t count, size_t stride, int form, int mem);
+int bzh_transcript_batch_write_scalars(bzh_transcript_batch* tb, const uint64_t* s, size_t count, size_t stride, int form, int mem);
+int bzh_transcript_batch_squeeze(bzh_transcript_batch* tb, int form, int mem, uint64_t* out);
+int bzh_transcript_batch_proofs(bzh_transcript_batch* tb, int mem, uint8_t* out, size_t out_stride, size_t* len);
+int bzh_transcript_batch_status(bzh_transcript_batch* tb, uint8_t* out);
+int bzh_transcript_batch_from_host(bzh_transcript_batch* tb, const bzh_transcript* const* hosts);
+int bzh_transcript_batch_to_host(bzh_transcript_batch* tb, bzh_transcript* const* hosts);
 /* host only, no ctx: the launch shapes of bzh_batch_invert and bzh_kate_division(_batch), from the functions the drivers call.
  *   bzh_batch_invert_plan    thread t of *nthreads owns the chain of elements t, t + nthreads, ... below count (Montgomery's
  *                            trick over it, one inversion per thread); count == 0 gives 0: nothing is launched.
