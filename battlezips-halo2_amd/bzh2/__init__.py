@@ -747,6 +747,7 @@ EXPORTS += ["bzh_pk_create", "bzh_pk_free", "bzh_pk_set_lagrange", "bzh_pk_quoti
             "bzh_vk_digest", "bzh_pk_vk_repr"]
 EXPORTS += ["bzh_vk_create", "bzh_vk_from_pk", "bzh_vk_write", "bzh_vk_read", "bzh_vk_info", "bzh_vk_vk_repr", "bzh_vk_device_bytes",
             "bzh_pk_device_bytes", "bzh_vk_free", "bzh_verify_batch_vk"]
+EXPORTS += ["bzh_pk_verify_pass_select", "bzh_pk_verify_pass_selected", "bzh_verify_batch_vk_with"]
 # Params::new (bzh2/params.py)
 EXPORTS += ["bzh_hash_to_curve", "bzh_params_generators", "bzh_group_ifft", "bzh_params_create", "bzh_params_free", "bzh_params_bases",
             "bzh_params_points"]

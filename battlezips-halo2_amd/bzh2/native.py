@@ -43,6 +43,10 @@ def _bind():
     L.bzh_vk_free.argtypes = [_VP]
     L.bzh_verify_batch_vk.argtypes = [_VP, _VP, _VP, _VP, ctypes.c_size_t, _VP, ctypes.c_size_t, _VP, ctypes.c_size_t,
                                       ctypes.POINTER(ctypes.c_size_t), _VP, ctypes.POINTER(ctypes.c_int)]
+    L.bzh_verify_batch_vk_with.argtypes = [_VP, _VP, _VP, _VP, ctypes.c_int, ctypes.c_size_t, _VP, ctypes.c_size_t, _VP, ctypes.c_size_t,
+                                           ctypes.POINTER(ctypes.c_size_t), _VP, ctypes.POINTER(ctypes.c_int)]
+    L.bzh_pk_verify_pass_select.argtypes = [_VP, ctypes.c_int]
+    L.bzh_pk_verify_pass_selected.argtypes = [_VP, ctypes.POINTER(ctypes.c_int)]
     L._bzh_native_bound = True
     return L
 
@@ -60,6 +64,7 @@ def rng_expand(seed: bytes, first_draw: int, draws: int) -> bytes:
 QUOTIENT_INTERPRETER, QUOTIENT_BUILTIN, QUOTIENT_MODULE = 0, 1, 2
 LOOKUP_HOST, LOOKUP_DEVICE = 0, 1
 VERIFY_POINTS_HOST, VERIFY_POINTS_DEVICE = 0, 1
+VERIFY_PASS_HOST, VERIFY_PASS_DEVICE = 0, 1
 
 _QUOTIENT_CODE = {}   # source hash -> code object (several keys of one circuit in a process share one compilation)
 
@@ -224,6 +229,16 @@ class NativeProvingKey:
         L = _bind()
         L.bzh_pk_verify_select.argtypes = [_VP, ctypes.c_int]
         self.ctx._check(L.bzh_pk_verify_select(self.handle, where), "bzh_pk_verify_select")
+
+    # ---- where bzh_verify_batch runs the per-proof pass ------------------------------------------------------
+    def verify_pass_selected(self) -> int:
+        """VERIFY_PASS_HOST (host threads, one proof each) or VERIFY_PASS_DEVICE (the key's scalar program, one lane per proof)"""
+        w = ctypes.c_int()
+        self.ctx._check(_bind().bzh_pk_verify_pass_selected(self.handle, ctypes.byref(w)), "bzh_pk_verify_pass_selected")
+        return w.value
+
+    def verify_pass_select(self, where: int):
+        self.ctx._check(_bind().bzh_pk_verify_pass_select(self.handle, where), "bzh_pk_verify_pass_select")
 
     def compile_quotient(self, cache_dir: str | None = None) -> bool:
         """Make the key run its quotient program as compiled code.  The reference's circuits have a kernel inside libbzh2.so
@@ -400,10 +415,11 @@ class NativeVerifyingKey:
         _check(_bind().bzh_vk_device_bytes(self.handle, ctypes.byref(kb), ctypes.byref(wb)), "bzh_vk_device_bytes")
         return kb.value, wb.value
 
-    def verify_batch(self, ctx: Context, params, instances, proofs, lagrange: bool = True, g0_u_w=None) -> list:
+    def verify_batch(self, ctx: Context, params, instances, proofs, lagrange: bool = True, g0_u_w=None, pass_where: int | None = None) -> list:
         """plonk::verify_proof(&params, &vk, ..) for each (instances[b], proofs[b]); returns a list of bools.  params: a
         bzh2.params.Params -- with lagrange its g_lagrange table commits the instance columns -- or a Bases table (g | u | w)
-        together with g0_u_w (3 x 8 canonical limbs)."""
+        together with g0_u_w (3 x 8 canonical limbs).  pass_where: VERIFY_PASS_HOST / VERIFY_PASS_DEVICE through
+        bzh_verify_batch_vk_with; None: bzh_verify_batch_vk."""
         L = _bind()
         bases = getattr(params, "bases", params)
         lag = getattr(params, "bases_lagrange", None) if lagrange else None
@@ -416,8 +432,13 @@ class NativeVerifyingKey:
         for b, pr in enumerate(proofs):
             buf[b, :len(pr)] = np.frombuffer(pr, dtype=np.uint8)
         res = (ctypes.c_int * B)()
-        rc = L.bzh_verify_batch_vk(ctx.handle, self.handle, bases.handle, lag.handle if lag is not None else None, B, _VP(inst.ctypes.data),
-                                   rows, _VP(buf.ctypes.data), stride, lens, _VP(g0.ctypes.data), res)
+        lagh = lag.handle if lag is not None else None
+        if pass_where is None:
+            rc = L.bzh_verify_batch_vk(ctx.handle, self.handle, bases.handle, lagh, B, _VP(inst.ctypes.data), rows, _VP(buf.ctypes.data), stride,
+                                       lens, _VP(g0.ctypes.data), res)
+        else:
+            rc = L.bzh_verify_batch_vk_with(ctx.handle, self.handle, bases.handle, lagh, pass_where, B, _VP(inst.ctypes.data), rows,
+                                            _VP(buf.ctypes.data), stride, lens, _VP(g0.ctypes.data), res)
         ctx._check(rc, "bzh_verify_batch_vk")
         return [bool(v) for v in res]
 

@@ -330,6 +330,10 @@ int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_
                const uint8_t* proof, size_t proof_len, bzh_transcript* tr, const uint64_t* g0_u_w_xy);
 int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
                     const uint64_t* cu, int* ok);
+// the same check with its operands already on the device (the verifier's device pass): d_pts batch x nl affine canonical points
+// (taken to Montgomery form in place), d_scal canonical, d_cu batch x (k + 1) Montgomery; 16-byte aligned
+int ipa_check_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
+                           const uint32_t* d_cu, int* ok);
 bool point_decompress(int curve, const uint8_t* in, uint64_t* xy_canonical);
 // sqrt_decompress.hip (device pointers, 16-byte aligned; elements and points in `form`).  batch_sqrt_run: in place, d_status[i] = 1
 // for a square (root written), 0 otherwise (element untouched).  decompress_run: n x 32 bytes -> n affine points x || y and one
@@ -343,5 +347,35 @@ int normalize_run(bzh_ctx* ctx, int curve, const void* d_xyz, size_t n, int form
 // memory (16-byte aligned); enqueues only, the caller holds ctx->mu.  ev: null, or three events recorded before k_hash_to_field,
 // between the two kernels and after k_map_to_curve.
 int h2c_generators_run(bzh_ctx* ctx, uint32_t first, size_t count, uint32_t* d_out_xy, uint8_t* d_status, hipEvent_t* ev = nullptr);
+// transcript_batch.hip: a device-resident bzh_transcript_batch for a caller that holds ctx->mu; device operands, enqueue only.
+// kind 0: common points (d_pre: a BZH_POINT_* byte per point at [b * stride + i], or null), kind 2: common scalars; item i of
+// transcript b lies at d_base + (b * stride + i) items -- stride 0 gives every transcript the same items.  tb_squeeze_locked writes
+// batch x 32 bytes.  tb_free_locked waits for the stream.
+int tb_new_locked(bzh_ctx* ctx, int curve, size_t batch, bzh_transcript_batch** out);
+void tb_free_locked(bzh_transcript_batch* tb);
+int tb_absorb_locked(bzh_transcript_batch* tb, int kind, const void* d_base, size_t count, size_t stride, int form, const uint8_t* d_pre);
+int tb_squeeze_locked(bzh_transcript_batch* tb, int form, uint32_t* d_out);
+const uint8_t* tb_status_device(const bzh_transcript_batch* tb);
+// verify_pass.hip: the kernels of the verifier's device pass (BZH_VERIFY_PASS_DEVICE); device pointers, enqueue only
+struct VerifyPassArgs {
+    size_t batch = 0, pstride = 0;           // proofs: batch rows of pstride bytes (a multiple of 32)
+    const uint8_t* d_proofs = nullptr;
+    // the key's program in device memory (verify_program.hpp)
+    const uint32_t *d_ops = nullptr, *d_consts = nullptr, *d_ev_offsets = nullptr, *d_out_slots = nullptr, *d_pt_src = nullptr, *d_vp_offsets = nullptr;
+    uint32_t nops = 0, nslots = 0, nch = 0, nev = 0, nl_cap = 0, ncu = 0, np = 0, ni = 0;
+    const uint32_t* d_ch = nullptr;          // nch x batch challenges, Montgomery
+    uint32_t* d_slots = nullptr;             // nslots x 8 x batch words
+    uint32_t *d_lc_scal = nullptr, *d_cu = nullptr, *d_flags = nullptr;   // batch x nl_cap canonical, batch x ncu Montgomery, batch words
+    // the points: decompressed proof points (batch x np) with their status bytes, the key's fixed | permutation commitments, the
+    // instance commitments (batch x ni), G_0 U W; all affine canonical
+    const uint32_t *d_proof_xy = nullptr, *d_key_xy = nullptr, *d_inst_xy = nullptr, *d_srs_xy = nullptr;
+    uint32_t nfixed = 0;
+    const uint8_t *d_point_status = nullptr, *d_tb_status = nullptr, *d_pre_reject = nullptr;
+    uint32_t* d_lc_pts = nullptr;            // batch x nl_cap points
+    uint8_t* d_reject = nullptr;             // batch bytes
+};
+int vp_gather_points(bzh_ctx* ctx, const VerifyPassArgs& a, uint32_t* d_out32);
+int vp_scalars_run(bzh_ctx* ctx, int curve, const VerifyPassArgs& a);
+int vp_assemble_run(bzh_ctx* ctx, const VerifyPassArgs& a);
 
 }  // namespace bzh

@@ -612,39 +612,23 @@ __global__ void __launch_bounds__(kSmallMsmThreads) k_ipa_small_msm(const uint32
     }
 }
 
-// For every opening b:  sum_i lc_scal[b][i] * lc_pts[b][i]  ==  <c_b * s(u_b), G>  ?   (the IPA verification equation with
-// everything but the n-term G'_0 moved to the left: L_j, R_j, S, the opened commitment expanded into the proof's own
-// commitments, G_0, U, W).  lc_pts: batch x nl affine canonical points ((0,0) = identity padding), lc_scal: canonical.
+// The launches and the comparison, operands in device memory: d_s batch x (n + 2) scratch, d_cu Montgomery, d_pts canonical (taken
+// to Montgomery form in place), d_scal canonical, d_out 2 x batch Jacobian sums.
 template <class C>
-static int ipa_check_batch_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts,
-                             const uint64_t* lc_scal, const uint64_t* cu /* batch x (k+1) canonical: c, u_j */, int* ok) {
+static int ipa_check_run_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_s, const uint32_t* d_cu, uint32_t* d_pts,
+                           const uint32_t* d_scal, uint32_t* d_out, int* ok) {
     using SF = typename CurveInfo<C>::SF;
     using PB = typename C::Base;
     const size_t n = bases->n - 2, B = batch;
     unsigned k = 0;
     while (((size_t)1 << k) < n) k++;
-    if (((size_t)1 << k) != n || !B || !nl) return BZH_E_ARG;
     hipStream_t st = ctx->stream;
-    const size_t na = B * nl;  // every opening's own nl points and scalars, side by side
-    const size_t words = B * (n + 2) * 8 + B * (k + 1) * 8 + na * 16 + na * 8 + 2 * B * 24 + 256;
-    void* arena = nullptr;
-    BZH_TRY(ws_ensure(ctx, 4, words * 4, &arena));
-    uint32_t* d_s = (uint32_t*)arena;
-    uint32_t* d_cu = d_s + B * (n + 2) * 8;
-    uint32_t* d_pts = d_cu + B * (k + 1) * 8;
-    uint32_t* d_scal = d_pts + na * 16;
-    uint32_t* d_out = d_scal + na * 8;
     // right side
-    std::vector<Fe<SF>> cum(B * (k + 1));
-    for (size_t i = 0; i < cum.size(); i++) cum[i] = fe_to_mont(fe_from_u64<SF>(cu + 4 * i));
-    BZH_TRY(h2d_small(ctx, d_cu, cum.data(), cum.size() * 32));
     hipLaunchKernelGGL((k_ipa_verify_s<SF>), dim3((unsigned)((n + 2 + 255) / 256), (unsigned)B), dim3(256), 0, st, d_cu, n, k, d_s);
     BZH_HIP_TRY(ctx, hipGetLastError());
     BZH_TRY(msm_run(ctx, bases, d_s, n + 2, B, BZH_FORM_MONTGOMERY, d_out));
     // left side: B independent nl-term sums
-    BZH_TRY(h2d_small(ctx, d_pts, lc_pts, na * 64));
-    BZH_TRY(bases_to_montgomery(ctx, C::id, d_pts, na));
-    BZH_TRY(h2d_small(ctx, d_scal, lc_scal, na * 32));
+    BZH_TRY(bases_to_montgomery(ctx, C::id, d_pts, B * nl));
     hipLaunchKernelGGL((k_ipa_small_msm<C>), dim3((unsigned)B), dim3(kSmallMsmThreads), 0, st, d_pts, d_scal, nl, d_out + B * 24);
     BZH_HIP_TRY(ctx, hipGetLastError());
     std::vector<uint64_t> jac(2 * B * 12), lhs(B * 8), rhs(B * 8);
@@ -656,9 +640,51 @@ static int ipa_check_batch_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch,
     return BZH_OK;
 }
 
+// For every opening b:  sum_i lc_scal[b][i] * lc_pts[b][i]  ==  <c_b * s(u_b), G>  ?   (the IPA verification equation with
+// everything but the n-term G'_0 moved to the left: L_j, R_j, S, the opened commitment expanded into the proof's own
+// commitments, G_0, U, W).  lc_pts: batch x nl affine canonical points ((0,0) = identity padding), lc_scal: canonical.
+// Upload, then ipa_check_run_t.
+template <class C>
+static int ipa_check_batch_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts,
+                             const uint64_t* lc_scal, const uint64_t* cu /* batch x (k+1) canonical: c, u_j */, int* ok) {
+    using SF = typename CurveInfo<C>::SF;
+    const size_t n = bases->n - 2, B = batch;
+    unsigned k = 0;
+    while (((size_t)1 << k) < n) k++;
+    if (((size_t)1 << k) != n || !B || !nl) return BZH_E_ARG;
+    const size_t na = B * nl;  // every opening's own nl points and scalars, side by side
+    const size_t words = B * (n + 2) * 8 + B * (k + 1) * 8 + na * 16 + na * 8 + 2 * B * 24 + 256;
+    void* arena = nullptr;
+    BZH_TRY(ws_ensure(ctx, 4, words * 4, &arena));
+    uint32_t* d_s = (uint32_t*)arena;
+    uint32_t* d_cu = d_s + B * (n + 2) * 8;
+    uint32_t* d_pts = d_cu + B * (k + 1) * 8;
+    uint32_t* d_scal = d_pts + na * 16;
+    uint32_t* d_out = d_scal + na * 8;
+    std::vector<Fe<SF>> cum(B * (k + 1));
+    for (size_t i = 0; i < cum.size(); i++) cum[i] = fe_to_mont(fe_from_u64<SF>(cu + 4 * i));
+    BZH_TRY(h2d_small(ctx, d_cu, cum.data(), cum.size() * 32));
+    BZH_TRY(h2d_small(ctx, d_pts, lc_pts, na * 64));
+    BZH_TRY(h2d_small(ctx, d_scal, lc_scal, na * 32));
+    return ipa_check_run_t<C>(ctx, bases, B, nl, d_s, d_cu, d_pts, d_scal, d_out, ok);
+}
+
 int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
                     const uint64_t* cu, int* ok) {
     return with_curve(bases->curve, [&](auto c) { return ipa_check_batch_t<decltype(c)>(ctx, bases, batch, nl, lc_pts, lc_scal, cu, ok); });
+}
+
+int ipa_check_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
+                           const uint32_t* d_cu, int* ok) {
+    const size_t n = bases->n - 2, B = batch;
+    unsigned k = 0;
+    while (((size_t)1 << k) < n) k++;
+    if (((size_t)1 << k) != n || !B || !nl) return BZH_E_ARG;
+    void* arena = nullptr;   // workspace slot 4: the G'_0 scalars and the two sums per opening
+    BZH_TRY(ws_ensure(ctx, 4, (B * (n + 2) * 8 + 2 * B * 24 + 256) * 4, &arena));
+    uint32_t* d_s = (uint32_t*)arena;
+    uint32_t* d_out = d_s + B * (n + 2) * 8;
+    return with_curve(bases->curve, [&](auto c) { return ipa_check_run_t<decltype(c)>(ctx, bases, B, nl, d_s, d_cu, d_pts, d_scal, d_out, ok); });
 }
 
 // pasta_curves from_bytes for one compressed point (host): false = not on the curve / non-canonical

@@ -124,6 +124,10 @@ struct Reader {
     }
 };
 
+// the host pass as a tape (BZH_VERIFY_PASS_DEVICE): VerifyTape, its interpreter, and -- for this file -- its compiler
+#define BZH_VP_WITH_COMPILER 1
+#include "verify_program.hpp"
+
 // ---------------------------------------------------------------------------
 // the part of a key the verifier reads (verify_host, verify_batch_t): fixed by the constraint-system part of the circuit blob,
 // except for the two commitment lists, which keygen computes against an SRS
@@ -146,6 +150,7 @@ struct KeyShape {
     std::vector<std::vector<int>> rot_sets;
     std::vector<std::vector<uint64_t>> groups;
     std::vector<uint32_t> vp_offsets;   // byte offset of every point of a proof, in read order (verify_point_offsets)
+    VerifyTape vprog;                   // the host pass as a scalar program (verify_program.hpp): host memory, derived like the above
     // commitments to the fixed and permutation polynomials, blind 1: affine canonical x || y
     std::vector<uint64_t> fixed_commitments, sigma_commitments;
 
@@ -455,5 +460,6 @@ static int shape_parse_tail(Reader& r, KeyShape& pk, const ShapeHead& h) {
         }
     }
     pk.vp_offsets = verify_point_offsets(pk);
+    vp_compile<SF>(pk, pk.vprog);
     return BZH_OK;
 }

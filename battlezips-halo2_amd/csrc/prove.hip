@@ -376,6 +376,20 @@ int bzh_pk_verify_selected(bzh_pk* pk, int* where) {
     return BZH_OK;
 }
 
+int bzh_pk_verify_pass_select(bzh_pk* pk, int where) {
+    if (!pk || (where != BZH_VERIFY_PASS_HOST && where != BZH_VERIFY_PASS_DEVICE)) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(pk->mu);
+    pk->vpass_select = where;
+    return BZH_OK;
+}
+
+int bzh_pk_verify_pass_selected(bzh_pk* pk, int* where) {
+    if (!pk) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(pk->mu);
+    if (where) *where = pk->vpass_select;
+    return BZH_OK;
+}
+
 int bzh_pk_set_quotient_module(bzh_ctx* ctx, bzh_pk* pk, const void* code_object, size_t len) {
     if (!ctx || !pk || pk->device != ctx->device) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -454,12 +468,16 @@ int bzh_verify_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* ins
         return BZH_E_ARG;
     }
     const bool points_on_device = pk->vp_select == BZH_VERIFY_POINTS_DEVICE;
+    const bool pass_on_device = pk->vpass_select == BZH_VERIFY_PASS_DEVICE;
     lkp.unlock();
     bzh::Arena& arena = pk->arena_for(ctx, ctx->device);
     const int rc = bzh::with_pasta_curve(pk->curve, [&](auto c) {
         using C = decltype(c);
         arena.reset();
         BZH_TRY(bzh::pk_fill_vk<C>(ctx, pk));
+        if (pass_on_device)
+            return bzh::verify_batch_device_t<C>(ctx, *pk, pk->srs, nullptr, arena, batch, instances, instance_rows, proofs, proof_stride, proof_lens,
+                                                 g0_u_w, results);
         return bzh::verify_batch_t<C>(ctx, *pk, pk->srs, nullptr, arena, points_on_device, batch, instances, instance_rows, proofs, proof_stride,
                                       proof_lens, g0_u_w, results);
     });
@@ -504,6 +522,14 @@ int bzh_vk_from_pk(bzh_ctx* ctx, bzh_pk* pk, bzh_vk** out) {
 int bzh_verify_batch_vk(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch,
                         const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
                         const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
+    return bzh_verify_batch_vk_with(ctx, vk, srs, g_lagrange, BZH_VERIFY_PASS_HOST, batch, instances, instance_rows, proofs, proof_stride,
+                                    proof_lens, g0_u_w, results);
+}
+
+int bzh_verify_batch_vk_with(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, int pass_where,
+                             size_t batch, const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
+                             const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
+    if (pass_where != BZH_VERIFY_PASS_HOST && pass_where != BZH_VERIFY_PASS_DEVICE) return BZH_E_ARG;
     if (!ctx || !vk || !srs || !batch || batch > 4096 || !proofs || !proof_lens || !g0_u_w || !results) return BZH_E_ARG;
     const bzh::KeyShape& key = vk->shape;
     if (srs->device != ctx->device || srs->curve != key.curve || srs->n != key.n + 2) return BZH_E_ARG;
@@ -524,6 +550,9 @@ int bzh_verify_batch_vk(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, co
     }
     bzh::Arena& arena = vk->arena_for(ctx, ctx->device);
     const int rc = bzh::with_pasta_curve(key.curve, [&](auto c) {
+        if (pass_where == BZH_VERIFY_PASS_DEVICE)
+            return bzh::verify_batch_device_t<decltype(c)>(ctx, key, srs, g_lagrange, arena, batch, instances, instance_rows, proofs, proof_stride,
+                                                           proof_lens, g0_u_w, results);
         return bzh::verify_batch_t<decltype(c)>(ctx, key, srs, g_lagrange, arena, false, batch, instances, instance_rows, proofs, proof_stride,
                                                 proof_lens, g0_u_w, results);
     });

@@ -187,7 +187,76 @@ static int scratch_ensure(bzh_transcript_batch* tb, size_t bytes) {
     return BZH_OK;
 }
 
+// device memory of a fresh batch: h | buf | status | proofs (the caller holds ctx->mu)
+static int tb_device_init(bzh_transcript_batch* tb, const std::vector<uint64_t>& words) {
+    bzh_ctx* ctx = tb->ctx;
+    const size_t batch = tb->batch, st_off = 192 * batch, pr_off = st_off + round_up(batch, 256);
+    BZH_HIP_TRY(ctx, hipMalloc((void**)&tb->d_mem, pr_off + batch * tb->S.pstride + 256));
+    std::vector<uint8_t> img(pr_off, 0);
+    memcpy(img.data(), words.data(), 192 * batch);
+    BZH_TRY(h2d_small(ctx, tb->d_mem, img.data(), img.size()));
+    tb->S.h = (uint64_t*)tb->d_mem, tb->S.buf = (uint64_t*)tb->d_mem + 8 * batch;
+    tb->S.status = (uint8_t*)tb->d_mem + st_off, tb->S.proofs = (uint8_t*)tb->d_mem + pr_off;
+    return BZH_OK;
+}
+
 }  // namespace
+
+// ---------------------------------------------------------------------------
+// the same object for a caller inside the library that already holds ctx->mu (the verifier's device pass, csrc/verifier.hpp):
+// device operands only, enqueue only, no argument checks beyond the kind
+// ---------------------------------------------------------------------------
+int tb_new_locked(bzh_ctx* ctx, int curve, size_t batch, bzh_transcript_batch** out) {
+    if (!ctx || !out || !valid_curve(curve) || !batch || batch > kMaxBatch) return BZH_E_ARG;
+    bzh_transcript_batch* tb = new (std::nothrow) bzh_transcript_batch();
+    if (!tb) return BZH_E_OOM;
+    tb->ctx = ctx, tb->curve = curve, tb->batch = batch;
+    tb->S.batch = batch;
+    std::vector<uint64_t> words;
+    fresh_words(batch, words);
+    const int rc = tb_device_init(tb, words);
+    if (rc) {
+        if (tb->d_mem) (void)hipFree(tb->d_mem);
+        delete tb;
+        return rc;
+    }
+    *out = tb;
+    return BZH_OK;
+}
+void tb_free_locked(bzh_transcript_batch* tb) {
+    if (!tb) return;
+    (void)hipStreamSynchronize(tb->ctx->stream);
+    if (tb->d_mem) (void)hipFree(tb->d_mem);
+    if (tb->d_scratch) (void)hipFree(tb->d_scratch);
+    delete tb;
+}
+int tb_absorb_locked(bzh_transcript_batch* tb, int kind, const void* d_base, size_t count, size_t stride, int form, const uint8_t* d_pre) {
+    if (!count) return BZH_OK;
+    if (kind == 0)
+        BZH_TRY(absorb_launch<0>(tb, d_base, count, stride, form, d_pre));
+    else if (kind == 2)
+        BZH_TRY(absorb_launch<2>(tb, d_base, count, stride, form, nullptr));
+    else
+        return BZH_E_ARG;
+    advance(tb, count, (uint32_t)kKindLen[kind], false);
+    return BZH_OK;
+}
+int tb_squeeze_locked(bzh_transcript_batch* tb, int form, uint32_t* d_out) {
+    bzh_ctx* ctx = tb->ctx;
+    BZH_TRY(with_curve(tb->curve, [&](auto c) -> int {
+        {
+            ScopedTimer tm(ctx, BZH_T_POLY);
+            hipLaunchKernelGGL((k_tb_squeeze<decltype(c)>), dim3((unsigned)((tb->batch + 255) / 256)), dim3(256), 0, ctx->stream, tb->S, tb->t,
+                               tb->buflen, form == BZH_FORM_CANONICAL ? 1 : 0, d_out);
+        }
+        BZH_HIP_TRY(ctx, hipGetLastError());
+        return BZH_OK;
+    }));
+    advance(tb, 1, 1, false);
+    return BZH_OK;
+}
+const uint8_t* tb_status_device(const bzh_transcript_batch* tb) { return tb->S.status; }
+
 }  // namespace bzh
 
 using namespace bzh;
@@ -211,22 +280,16 @@ extern "C" int bzh_transcript_batch_new(bzh_ctx* ctx, int curve, size_t batch, s
         *out = tb;
         return BZH_OK;
     }
-    const size_t st_off = 192 * batch, pr_off = st_off + round_up(batch, 256);
-    int rc = [&]() -> int {
+    const int rc = [&]() -> int {
         std::lock_guard<std::mutex> lk(ctx->mu);
         BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        BZH_HIP_TRY(ctx, hipMalloc((void**)&tb->d_mem, pr_off + batch * pstride + 256));
-        std::vector<uint8_t> img(pr_off, 0);
-        memcpy(img.data(), words.data(), 192 * batch);
-        return h2d_small(ctx, tb->d_mem, img.data(), img.size());
+        return tb_device_init(tb, words);
     }();
     if (rc) {
         if (tb->d_mem) (void)hipFree(tb->d_mem);
         delete tb;
         return rc;
     }
-    tb->S.h = (uint64_t*)tb->d_mem, tb->S.buf = (uint64_t*)tb->d_mem + 8 * batch;
-    tb->S.status = (uint8_t*)tb->d_mem + st_off, tb->S.proofs = (uint8_t*)tb->d_mem + pr_off;
     *out = tb;
     return BZH_OK;
 }

@@ -6,404 +6,7 @@
 // Blake2b, ~56 point decompressions, a few hundred field operations; device work for the whole batch: the instance
 // commitments, one n-term MSM per proof against the SRS table and one small MSM over the proof's own points.
 // ---------------------------------------------------------------------------
-template <class C>
-struct ProofView {
-    using SF = typename CurveInfo<C>::SF;
-    // outputs of the host pass: left-side linear combination and the right side's (c, u_j)
-    std::vector<uint64_t> lc_pts, lc_scal, cu;
-    bool ok = false;
-};
-
-template <class SF>
-static Fe<SF> cx_eval(const KeyShape& pk, int i, const std::vector<Fe<SF>>& adv, const std::vector<Fe<SF>>& fix,
-                      const std::vector<Fe<SF>>& inst) {
-    const CNode& e = pk.cx[i];
-    auto find = [](const std::vector<std::pair<int, int>>& qs, int col, int rot) -> size_t {
-        for (size_t k = 0; k < qs.size(); k++)
-            if (qs[k].first == col && qs[k].second == rot) return k;
-        return (size_t)-1;
-    };
-    switch (e.tag) {
-        case CX_CONST: {
-            Fe<SF> v;
-            memcpy(v.l, e.val, 32);
-            return v;
-        }
-        case CX_ADVICE: return adv[find(pk.advice_queries, (int)e.col, e.rot)];
-        case CX_FIXED: return fix[find(pk.fixed_queries, (int)e.col, e.rot)];
-        case CX_INSTANCE: return inst[find(pk.instance_queries, (int)e.col, e.rot)];
-        case CX_NEG: return fe_neg(cx_eval<SF>(pk, e.a, adv, fix, inst));
-        case CX_SCALE: {
-            Fe<SF> v;
-            memcpy(v.l, e.val, 32);
-            return fe_mul(cx_eval<SF>(pk, e.a, adv, fix, inst), v);
-        }
-        case CX_ADD: return fe_add(cx_eval<SF>(pk, e.a, adv, fix, inst), cx_eval<SF>(pk, e.b, adv, fix, inst));
-        default: return fe_mul(cx_eval<SF>(pk, e.a, adv, fix, inst), cx_eval<SF>(pk, e.b, adv, fix, inst));
-    }
-}
-
-// the points of one proof decoded ahead of the host pass (BZH_VERIFY_POINTS_DEVICE): affine canonical, one BZH_POINT_* each
-struct PrePoints {
-    const uint32_t* offsets = nullptr;
-    size_t count = 0;
-    const uint64_t* xy = nullptr;
-    const uint8_t* status = nullptr;
-};
-// wall time a host pass spent decompressing points / in all (BZH_PROVE_TRACE only)
-struct HostPassTimes {
-    double decompress_ms = 0, total_ms = 0;
-};
-
-// host pass over one proof; inst_xy: this proof's instance commitments.  Returns false on any malformed input.
-template <class C>
-static bool verify_host(const KeyShape& pk, const uint64_t* inst_xy, const uint8_t* proof, size_t len, size_t nl_cap,
-                        ProofView<C>& out, const PrePoints* pre = nullptr, HostPassTimes* times = nullptr) {
-    using SF = typename CurveInfo<C>::SF;
-    const int na = pk.na, ni = pk.ni, nsets = pk.nsets, nl = pk.nl, npieces = pk.npieces;
-    const size_t n = pk.n, m = pk.perm_columns.size();
-    const unsigned k = pk.k;
-    bzh_transcript* T = nullptr;
-    if (bzh_transcript_new(pk.field, &T)) return false;
-    struct Guard {
-        bzh_transcript* t;
-        ~Guard() { bzh_transcript_free(t); }
-    } guard{T};
-    size_t off = 0;
-    bool bad = false;
-    std::vector<uint64_t> pts;     // every point read from the proof, affine canonical
-    pts.reserve(((size_t)na + 3 * nl + nsets + npieces + 3 + 2 * (size_t)k + 8) * 8);  // terms keep pointers into it: no regrowth
-    auto read_point = [&]() -> size_t {  // index into pts (units of 8 u64)
-        const size_t idx = pts.size() / 8;
-        pts.resize(pts.size() + 8, 0);
-        if (off + 32 > len) {
-            bad = true;
-            return idx;
-        }
-        bool ok;
-        if (pre && idx < pre->count && pre->offsets[idx] == off) {   // decoded on the device; INVALID and IDENTITY leave zeros
-            ok = pre->status[idx] == BZH_POINT_OK;
-            if (ok) memcpy(&pts[idx * 8], pre->xy + idx * 8, 64);
-        } else if (times) {
-            const auto t0 = std::chrono::steady_clock::now();
-            ok = point_decompress(C::id, proof + off, &pts[idx * 8]);
-            times->decompress_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        } else {
-            ok = point_decompress(C::id, proof + off, &pts[idx * 8]);
-        }
-        if (!ok) {
-            bad = true;
-            return idx;
-        }
-        // upstream's Blake2bRead::common_point fails on the identity ("cannot write points at infinity to the
-        // transcript"): a proof carrying an identity commitment is rejected, not absorbed as (0, 0)
-        {
-            uint64_t any = 0;
-            for (int i = 0; i < 8; i++) any |= pts[idx * 8 + i];
-            if (!any) {
-                bad = true;
-                return idx;
-            }
-        }
-        off += 32;
-        bzh_transcript_common_point(T, &pts[idx * 8]);
-        return idx;
-    };
-    auto read_scalar = [&]() -> Fe<SF> {
-        uint64_t l[4] = {0, 0, 0, 0};
-        if (off + 32 > len) {
-            bad = true;
-            return fe_zero<SF>();
-        }
-        memcpy(l, proof + off, 32);
-        off += 32;
-        const Fe<SF> v = fe_from_u64<SF>(l);
-        if (!is_canonical(v)) bad = true;
-        bzh_transcript_common_scalar(T, l);
-        return fe_to_mont(v);
-    };
-    auto squeeze = [&]() {
-        uint64_t ch[4];
-        bzh_transcript_squeeze_challenge(T, ch);
-        return fe_to_mont(fe_from_u64<SF>(ch));
-    };
-    bzh_transcript_common_scalar(T, pk.vk_repr);
-    for (int i = 0; i < ni; i++) bzh_transcript_common_point(T, inst_xy + 8 * i);
-    std::vector<size_t> adv_c(na);
-    for (int i = 0; i < na; i++) adv_c[i] = read_point();
-    const Fe<SF> theta = squeeze();
-    std::vector<size_t> lka(nl), lks(nl), lkz(nl), pz_c(nsets), h_c(npieces);
-    for (int i = 0; i < nl; i++) {
-        lka[i] = read_point();
-        lks[i] = read_point();
-    }
-    const Fe<SF> beta = squeeze(), gamma = squeeze();
-    for (int i = 0; i < nsets; i++) pz_c[i] = read_point();
-    for (int i = 0; i < nl; i++) lkz[i] = read_point();
-    const size_t rand_c = read_point();
-    const Fe<SF> y = squeeze();
-    for (int i = 0; i < npieces; i++) h_c[i] = read_point();
-    const Fe<SF> x = squeeze();
-    if (bad) return false;
-    const Fe<SF> one = fe_one<SF>();
-    const Fe<SF> xn = h_pow_u64(x, n);
-    std::vector<Fe<SF>> inst_ev(pk.instance_queries.size()), adv_ev(pk.advice_queries.size()), fix_ev(pk.fixed_queries.size());
-    for (auto& v : inst_ev) v = read_scalar();
-    for (auto& v : adv_ev) v = read_scalar();
-    for (auto& v : fix_ev) v = read_scalar();
-    const Fe<SF> rand_ev = read_scalar();
-    std::vector<Fe<SF>> sig_ev(m);
-    for (auto& v : sig_ev) v = read_scalar();
-    std::vector<Fe<SF>> pz0(nsets), pz1(nsets), pzl(nsets, fe_zero<SF>());
-    for (int i = 0; i < nsets; i++) {
-        pz0[i] = read_scalar();
-        pz1[i] = read_scalar();
-        if (i != nsets - 1) pzl[i] = read_scalar();
-    }
-    std::vector<Fe<SF>> lz0(nl), lz1(nl), la0(nl), lam1(nl), ls0(nl);
-    for (int i = 0; i < nl; i++) {
-        lz0[i] = read_scalar();
-        lz1[i] = read_scalar();
-        la0[i] = read_scalar();
-        lam1[i] = read_scalar();
-        ls0[i] = read_scalar();
-    }
-    if (bad) return false;
-    // Lagrange values at x: l_i(x) = (x^n - 1) w^i / (n (x - w^i))
-    Fe<SF> omega;
-    {
-        uint64_t t[4];
-        memcpy(t, pk.omega, 32);
-        omega = fe_from_u64<SF>(t);
-    }
-    Fe<SF> nfe = fe_zero<SF>();
-    {
-        uint64_t t[4] = {(uint64_t)n, 0, 0, 0};
-        nfe = fe_to_mont(fe_from_u64<SF>(t));
-    }
-    const Fe<SF> xn1 = fe_sub(xn, one);
-    if (fe_is_zero(xn1)) return false;
-    auto lag = [&](size_t row) {
-        const Fe<SF> wi = h_pow_u64(omega, row);
-        return fe_mul(fe_mul(xn1, wi), fe_inv(fe_mul(nfe, fe_sub(x, wi))));
-    };
-    const Fe<SF> l0 = lag(0), l_last = lag(pk.usable);
-    Fe<SF> l_blind = fe_zero<SF>();
-    for (size_t r = pk.usable + 1; r < n; r++) l_blind = fe_add(l_blind, lag(r));
-    const Fe<SF> active = fe_sub(one, fe_add(l_last, l_blind));
-    Fe<SF> delta;
-    memcpy(delta.l, pk.delta, 32);
-    // the quotient's terms in protocol order, folded with y
-    Fe<SF> hacc = fe_zero<SF>();
-    auto push = [&](const Fe<SF>& t) { hacc = fe_add(fe_mul(hacc, y), t); };
-    for (int g : pk.gates) push(cx_eval<SF>(pk, g, adv_ev, fix_ev, inst_ev));
-    auto col_at0 = [&](std::pair<int, int> col) -> Fe<SF> {
-        const auto& qs = col.first == CX_ADVICE ? pk.advice_queries : (col.first == CX_FIXED ? pk.fixed_queries : pk.instance_queries);
-        const auto& ev = col.first == CX_ADVICE ? adv_ev : (col.first == CX_FIXED ? fix_ev : inst_ev);
-        for (size_t q = 0; q < qs.size(); q++)
-            if (qs[q].first == col.second && qs[q].second == 0) return ev[q];
-        bad = true;
-        return fe_zero<SF>();
-    };
-    if (nsets) {
-        push(fe_mul(l0, fe_sub(one, pz0[0])));
-        const Fe<SF> zl = pz0[nsets - 1];
-        push(fe_mul(l_last, fe_sub(fe_sqr(zl), zl)));
-        for (int i = 1; i < nsets; i++) push(fe_mul(l0, fe_sub(pz0[i], pzl[i - 1])));
-        Fe<SF> cur_delta = fe_mul(beta, x);
-        for (int i = 0; i < nsets; i++) {
-            const size_t c0 = (size_t)i * pk.chunk_len, c1 = std::min(m, c0 + pk.chunk_len);
-            Fe<SF> left = pz1[i], right = pz0[i];
-            for (size_t gj = c0; gj < c1; gj++) {
-                const Fe<SF> v = col_at0(pk.perm_columns[gj]);
-                left = fe_mul(left, fe_add(fe_add(v, fe_mul(beta, sig_ev[gj])), gamma));
-                right = fe_mul(right, fe_add(fe_add(v, cur_delta), gamma));
-                cur_delta = fe_mul(cur_delta, delta);
-            }
-            push(fe_mul(active, fe_sub(left, right)));
-        }
-    }
-    for (int i = 0; i < nl; i++) {
-        auto comp = [&](const std::vector<int>& es) {
-            Fe<SF> acc = fe_zero<SF>();
-            for (int e : es) acc = fe_add(fe_mul(acc, theta), cx_eval<SF>(pk, e, adv_ev, fix_ev, inst_ev));
-            return acc;
-        };
-        push(fe_mul(l0, fe_sub(one, lz0[i])));
-        push(fe_mul(l_last, fe_sub(fe_sqr(lz0[i]), lz0[i])));
-        const Fe<SF> lhs = fe_mul(fe_mul(lz1[i], fe_add(la0[i], beta)), fe_add(ls0[i], gamma));
-        const Fe<SF> rhs = fe_mul(fe_mul(lz0[i], fe_add(comp(pk.lookups[i].first), beta)), fe_add(comp(pk.lookups[i].second), gamma));
-        push(fe_mul(active, fe_sub(lhs, rhs)));
-        push(fe_mul(l0, fe_sub(la0[i], ls0[i])));
-        push(fe_mul(fe_mul(active, fe_sub(la0[i], ls0[i])), fe_sub(la0[i], lam1[i])));
-    }
-    if (bad) return false;
-    const Fe<SF> expected_h = fe_mul(hacc, fe_inv(xn1));
-
-    // multiopen: evaluation of commitment `cid` at rotation r (a permutation product's third rotation is -(blinding + 1)),
-    // and its place in the linear combination
-    auto eval_of = [&](uint64_t cid, int r) -> Fe<SF> {
-        const int kind = (int)(cid >> 32);
-        const size_t i = (size_t)(cid & 0xffffffffu);
-        auto from = [&](const std::vector<std::pair<int, int>>& qs, const std::vector<Fe<SF>>& ev) {
-            for (size_t q = 0; q < qs.size(); q++)
-                if (qs[q].first == (int)i && qs[q].second == r) return ev[q];
-            bad = true;
-            return fe_zero<SF>();
-        };
-        switch (kind) {
-            case K_INST: return from(pk.instance_queries, inst_ev);
-            case K_ADV: return from(pk.advice_queries, adv_ev);
-            case K_FIX: return from(pk.fixed_queries, fix_ev);
-            case K_SIGMA: return sig_ev[i];
-            case K_PZ: return r == 0 ? pz0[i] : (r == 1 ? pz1[i] : pzl[i]);
-            case K_LZ: return r == 0 ? lz0[i] : lz1[i];
-            case K_LA: return r == 0 ? la0[i] : lam1[i];
-            case K_LS: return ls0[i];
-            default: return i == M_H0 ? expected_h : rand_ev;
-        }
-    };
-    const Fe<SF> x1 = squeeze(), x2 = squeeze();
-    const size_t nq = pk.rot_sets.size();
-    // left-side linear combination: (point, scalar) pairs; proof / key commitments are weighted later by x4 powers
-    struct Term {
-        const uint64_t* pt;
-        Fe<SF> s;
-    };
-    std::vector<std::vector<Term>> q_terms(nq);
-    std::vector<std::vector<Fe<SF>>> q_evalsets(nq);
-    std::vector<Fe<SF>> xn_pows(npieces);
-    {
-        Fe<SF> pw = one;
-        for (int i = 0; i < npieces; i++) {
-            xn_pows[i] = pw;
-            pw = fe_mul(pw, xn);
-        }
-    }
-    for (size_t si = 0; si < nq; si++) {
-        const auto& cids = pk.groups[si];
-        const auto& rots = pk.rot_sets[si];
-        std::vector<Fe<SF>> evs(rots.size(), fe_zero<SF>());
-        for (size_t j = 0; j < cids.size(); j++) {
-            for (auto& t : q_terms[si]) t.s = fe_mul(t.s, x1);  // cm = x1 * cm + C
-            const uint64_t cid = cids[j];
-            const int kind = (int)(cid >> 32);
-            const size_t i = (size_t)(cid & 0xffffffffu);
-            auto add_term = [&](const uint64_t* pt, const Fe<SF>& s) { q_terms[si].push_back({pt, s}); };
-            switch (kind) {
-                case K_INST: add_term(inst_xy + 8 * i, one); break;
-                case K_ADV: add_term(&pts[adv_c[i] * 8], one); break;
-                case K_FIX: add_term(&pk.fixed_commitments[8 * i], one); break;
-                case K_SIGMA: add_term(&pk.sigma_commitments[8 * i], one); break;
-                case K_PZ: add_term(&pts[pz_c[i] * 8], one); break;
-                case K_LZ: add_term(&pts[lkz[i] * 8], one); break;
-                case K_LA: add_term(&pts[lka[i] * 8], one); break;
-                case K_LS: add_term(&pts[lks[i] * 8], one); break;
-                default:
-                    if (i == M_H0) {
-                        for (int pi = 0; pi < npieces; pi++) add_term(&pts[h_c[pi] * 8], xn_pows[pi]);
-                    } else {
-                        add_term(&pts[rand_c * 8], one);
-                    }
-            }
-            for (size_t t = 0; t < rots.size(); t++) evs[t] = fe_add(fe_mul(evs[t], x1), eval_of(cid, rots[t]));
-        }
-        q_evalsets[si] = evs;
-    }
-    if (bad) return false;
-    const size_t f_commit = read_point();
-    const Fe<SF> x3 = squeeze();
-    std::vector<Fe<SF>> q_evals(nq);
-    for (auto& v : q_evals) v = read_scalar();
-    if (bad) return false;
-    Fe<SF> omega_inv = fe_inv(omega);
-    auto rot = [&](int r) { return fe_mul(x, r >= 0 ? h_pow_u64(omega, (uint64_t)r) : h_pow_u64(omega_inv, (uint64_t)(-(int64_t)r))); };
-    Fe<SF> f_eval = fe_zero<SF>();
-    for (size_t si = 0; si < nq; si++) {
-        const auto& rots = pk.rot_sets[si];
-        const size_t np = rots.size();
-        std::vector<Fe<SF>> ptv(np);
-        for (size_t t = 0; t < np; t++) ptv[t] = rot(rots[t]);
-        // r(x3) by Lagrange's formula on (points, evals)
-        Fe<SF> r_eval = fe_zero<SF>(), den = one;
-        for (size_t j = 0; j < np; j++) {
-            Fe<SF> num = one, dn = one;
-            for (size_t mm = 0; mm < np; mm++) {
-                if (mm == j) continue;
-                num = fe_mul(num, fe_sub(x3, ptv[mm]));
-                dn = fe_mul(dn, fe_sub(ptv[j], ptv[mm]));
-            }
-            if (fe_is_zero(dn)) return false;
-            r_eval = fe_add(r_eval, fe_mul(q_evalsets[si][j], fe_mul(num, fe_inv(dn))));
-            den = fe_mul(den, fe_sub(x3, ptv[j]));
-        }
-        if (fe_is_zero(den)) return false;
-        f_eval = fe_add(fe_mul(f_eval, x2), fe_mul(fe_sub(q_evals[si], r_eval), fe_inv(den)));
-    }
-    const Fe<SF> x4 = squeeze();
-    // final commitment = x4^nq f + sum_si x4^(nq-1-si) q_si, final value likewise
-    Fe<SF> final_v = f_eval;
-    for (size_t si = 0; si < nq; si++) final_v = fe_add(fe_mul(final_v, x4), q_evals[si]);
-    std::vector<Fe<SF>> x4p(nq + 1);
-    x4p[0] = one;
-    for (size_t i = 1; i <= nq; i++) x4p[i] = fe_mul(x4p[i - 1], x4);
-    std::vector<Term> lc;
-    lc.push_back({&pts[f_commit * 8], x4p[nq]});
-    for (size_t si = 0; si < nq; si++)
-        for (auto& t : q_terms[si]) lc.push_back({t.pt, fe_mul(t.s, x4p[nq - 1 - si])});
-    // the opening argument: S, xi, z, (L_j, R_j, u_j), c, f
-    const size_t S = read_point();
-    const Fe<SF> xi = squeeze(), z = squeeze();
-    std::vector<size_t> Ls(k), Rs(k);
-    std::vector<Fe<SF>> us(k);
-    for (unsigned j = 0; j < k; j++) {
-        Ls[j] = read_point();
-        Rs[j] = read_point();
-        us[j] = squeeze();
-        if (fe_is_zero(us[j])) bad = true;
-    }
-    if (bad || off + 64 != len) return false;
-    uint64_t cl[4], fl[4];
-    memcpy(cl, proof + off, 32);
-    memcpy(fl, proof + off + 32, 32);
-    const Fe<SF> cc = fe_from_u64<SF>(cl), ff = fe_from_u64<SF>(fl);
-    if (!is_canonical(cc) || !is_canonical(ff)) return false;
-    const Fe<SF> cm = fe_to_mont(cc), fm = fe_to_mont(ff);
-    std::vector<Fe<SF>> xp(k ? k : 1);
-    if (k) {
-        xp[0] = x3;
-        for (unsigned i = 1; i < k; i++) xp[i] = fe_sqr(xp[i - 1]);
-    }
-    Fe<SF> b0 = one;
-    for (unsigned j = 0; j < k; j++) b0 = fe_mul(b0, fe_add(one, fe_mul(us[j], xp[k - 1 - j])));
-    std::vector<Fe<SF>> uinv = us;
-    h_batch_invert(uinv.data(), k);  // (none of the u_j is zero: checked above)
-    for (unsigned j = 0; j < k; j++) {
-        lc.push_back({&pts[Ls[j] * 8], uinv[j]});
-        lc.push_back({&pts[Rs[j] * 8], us[j]});
-    }
-    lc.push_back({&pts[S * 8], xi});
-    // G_0, U, W are the first and the last two SRS points: supplied by the caller right after this table
-    out.lc_pts.assign(nl_cap * 8, 0);
-    out.lc_scal.assign(nl_cap * 4, 0);
-    if (lc.size() + 3 > nl_cap) return false;
-    size_t o = 0;
-    for (auto& t : lc) {
-        memcpy(&out.lc_pts[o * 8], t.pt, 64);
-        fe_to_u64<SF>(&out.lc_scal[o * 4], fe_from_mont(t.s));
-        o++;
-    }
-    // scalars of G_0 (-v), U (-c b0 z), W (-f): points filled in by the caller (slots nl_cap-3 .. nl_cap-1)
-    fe_to_u64<SF>(&out.lc_scal[(nl_cap - 3) * 4], fe_from_mont(fe_neg(final_v)));
-    fe_to_u64<SF>(&out.lc_scal[(nl_cap - 2) * 4], fe_from_mont(fe_neg(fe_mul(fe_mul(cm, b0), z))));
-    fe_to_u64<SF>(&out.lc_scal[(nl_cap - 1) * 4], fe_from_mont(fe_neg(fm)));
-    out.cu.assign((size_t)(k + 1) * 4, 0);
-    fe_to_u64<SF>(&out.cu[0], fe_from_mont(cm));
-    for (unsigned j = 0; j < k; j++) fe_to_u64<SF>(&out.cu[(j + 1) * 4], fe_from_mont(us[j]));
-    out.ok = true;
-    return true;
-}
-
+#include "verify_host.hpp"   // ProofView, PrePoints, HostPassTimes, verify_host: host code only
 
 // The device side of the verifier and of keygen_vk: the shared column helpers (device_columns.hpp), with commitments of blind 1
 // against a table the caller names -- the key itself is host data.
@@ -463,6 +66,38 @@ struct ColumnCommitter : DeviceColumns<C> {
     }
 };
 
+// the instance commitments of a batch, affine canonical, batch x max(ni, 1) points
+template <class C>
+static int instance_commitments(ColumnCommitter<C>& pv, const KeyShape& key, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t B,
+                                const uint64_t* instances, size_t inst_rows, const uint64_t* g0_u_w, std::vector<uint64_t>& inst_xy) {
+    using SF = typename CurveInfo<C>::SF;
+    const size_t n = key.n;
+    const int ni = key.ni;
+    inst_xy.assign(B * std::max(ni, 1) * 8, 0);
+    if (ni) {
+        std::vector<Fe<SF>> hv(B * ni * inst_rows);
+        for (size_t i = 0; i < hv.size(); i++) hv[i] = fe_to_mont(fe_from_u64<SF>(instances + 4 * i));
+        if (g_lagrange) {
+            // Params::commit_lagrange: the inst_rows values of a column against the first inst_rows Lagrange points, plus W
+            BZH_TRY(pv.commit_prefix(g_lagrange, hv.data(), inst_rows, B * ni, g0_u_w + 16, inst_xy));
+        } else {
+            uint32_t* inst = pv.dalloc(B * ni * n);
+            uint32_t* inst_polys = pv.dalloc(B * ni * n);
+            if (!inst || !inst_polys) return BZH_E_OOM;
+            BZH_TRY(pv.zero(inst, B * ni * n));
+            if (inst_rows) {
+                uint32_t* tmp = pv.dalloc(hv.size());
+                if (!tmp) return BZH_E_OOM;
+                BZH_TRY(pv.upload(tmp, hv.data(), hv.size()));
+                BZH_TRY(pv.copy2d(inst, n, tmp, inst_rows, inst_rows, B * ni));
+            }
+            BZH_TRY(pv.to_coeff(inst_polys, inst, B * ni));
+            BZH_TRY(pv.commit(srs, inst_polys, B * ni, inst_xy));
+        }
+    }
+    return BZH_OK;
+}
+
 // verify_proof for a batch.  key: what the verifier reads of a key (a bzh_pk's or a bzh_vk's); srs: (g | u | w) with its window
 // table; g_lagrange: (g_lagrange | u | w), or null for instance commitments through the coefficient basis; arena: the (key,
 // ctx) workspace; points_on_device: BZH_VERIFY_POINTS_DEVICE.
@@ -470,10 +105,9 @@ template <class C>
 static int verify_batch_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* srs, const bzh_bases* g_lagrange, Arena& arena,
                           bool points_on_device, size_t batch, const uint64_t* instances, size_t inst_rows, const uint8_t* proofs,
                           size_t proof_stride, const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
-    using SF = typename CurveInfo<C>::SF;
     arena.reset();
     ColumnCommitter<C> pv(ctx, key, arena);
-    const size_t n = key.n, B = batch;
+    const size_t B = batch;
     const int ni = key.ni;
     // BZH_PROVE_TRACE=1: where the call's wall time goes, on stderr (tools/ubench_verify_points.py reads these lines)
     const bool trace = getenv("BZH_PROVE_TRACE") != nullptr;
@@ -518,28 +152,8 @@ static int verify_batch_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* sr
         mark("vp:stage+launch");
     }
     // instance commitments of the whole batch (the verifier recomputes them, as upstream does for IPA)
-    std::vector<uint64_t> inst_xy(B * std::max(ni, 1) * 8, 0);
-    if (ni) {
-        std::vector<Fe<SF>> hv(B * ni * inst_rows);
-        for (size_t i = 0; i < hv.size(); i++) hv[i] = fe_to_mont(fe_from_u64<SF>(instances + 4 * i));
-        if (g_lagrange) {
-            // Params::commit_lagrange: the inst_rows values of a column against the first inst_rows Lagrange points, plus W
-            BZH_TRY(pv.commit_prefix(g_lagrange, hv.data(), inst_rows, B * ni, g0_u_w + 16, inst_xy));
-        } else {
-            uint32_t* inst = pv.dalloc(B * ni * n);
-            uint32_t* inst_polys = pv.dalloc(B * ni * n);
-            if (!inst || !inst_polys) return BZH_E_OOM;
-            BZH_TRY(pv.zero(inst, B * ni * n));
-            if (inst_rows) {
-                uint32_t* tmp = pv.dalloc(hv.size());
-                if (!tmp) return BZH_E_OOM;
-                BZH_TRY(pv.upload(tmp, hv.data(), hv.size()));
-                BZH_TRY(pv.copy2d(inst, n, tmp, inst_rows, inst_rows, B * ni));
-            }
-            BZH_TRY(pv.to_coeff(inst_polys, inst, B * ni));
-            BZH_TRY(pv.commit(srs, inst_polys, B * ni, inst_xy));
-        }
-    }
+    std::vector<uint64_t> inst_xy;
+    BZH_TRY(instance_commitments<C>(pv, key, srs, g_lagrange, B, instances, inst_rows, g0_u_w, inst_xy));
     mark("instance commitments");
     if (np) {
         BZH_TRY(d2h_finish(ctx));   // (already landed when a commitment was read back)
@@ -556,8 +170,7 @@ static int verify_batch_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* sr
         mark("vp:read-back");
     }
     // host pass, one thread per proof
-    const size_t ncommit = (size_t)key.na + 3 * key.nl + key.nsets + 1 + key.npieces + 1 + key.nf + key.perm_columns.size() + ni;
-    const size_t nl_cap = ncommit + 2 * (size_t)key.k + 1 + 3 + 4;
+    const size_t nl_cap = vp_nl_cap(key);
     std::vector<ProofView<C>> views(B);
     {
         const size_t nthreads = std::min<size_t>({B, (size_t)host_thread_budget(), (size_t)32});
@@ -602,5 +215,164 @@ static int verify_batch_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* sr
     BZH_TRY(ipa_check_batch(ctx, srs, Bl, nl_cap, lc_pts.data(), lc_scal.data(), cu.data(), ok.data()));
     for (size_t j = 0; j < Bl; j++) results[live[j]] = ok[j];
     mark("ipa check");
+    return BZH_OK;
+}
+
+// verify_proof for a batch with the per-proof pass on the device (BZH_VERIFY_PASS_DEVICE): after the instance commitments, the
+// proof bytes go up once and nothing comes back but the two Jacobian sums per proof and one reject byte per proof.  Between the
+// upload and that read-back the stream is not waited for (msm_run's own waits aside, and a workspace that has to grow on a first
+// call): one decompress_run over key.vp_offsets, one bzh_transcript_batch walking key.vprog.schedule, k_vp_scalars over the
+// key's tape, the gather of the left side's points, ipa_check_batch_device.  A proof whose length is not the key's is rejected
+// here and its row is zero-filled.
+template <class C>
+static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* srs, const bzh_bases* g_lagrange, Arena& arena,
+                                 size_t batch, const uint64_t* instances, size_t inst_rows, const uint8_t* proofs, size_t proof_stride,
+                                 const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
+    const VerifyTape& vp = key.vprog;
+    if (!vp.ok) {
+        ctx->last_error = "bzh_verify_batch: this key's host pass has no device program (BZH_VERIFY_PASS_DEVICE)";
+        return BZH_E_RANGE;
+    }
+    arena.reset();
+    ColumnCommitter<C> pv(ctx, key, arena);
+    const size_t B = batch, np = key.vp_offsets.size(), np_all = B * np, kk = key.k, nl_cap = vp.nl_cap;
+    const size_t ni = (size_t)key.ni, ni1 = std::max<size_t>(ni, 1), plen = vp.proof_len, pstride = (plen + 31) & ~(size_t)31;
+    const bool trace = getenv("BZH_PROVE_TRACE") != nullptr;
+    auto t_last = std::chrono::steady_clock::now();
+    auto mark = [&](const char* name) {
+        if (!trace) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[bzh_verify_batch] %-22s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(now - t_last).count());
+        t_last = now;
+    };
+    std::vector<uint64_t> inst_xy;
+    BZH_TRY(instance_commitments<C>(pv, key, srs, g_lagrange, B, instances, inst_rows, g0_u_w, inst_xy));
+    mark("instance commitments");
+    // the key's program and points, this call's operands: device memory out of the (key, ctx) workspace
+    auto words = [&](size_t w) { return (uint32_t*)arena.alloc(w * 4); };
+    auto put = [&](const void* src, size_t bytes, uint32_t** d) -> int {
+        *d = (uint32_t*)arena.alloc(bytes + 16);
+        if (!*d) return BZH_E_OOM;
+        return h2d_small(ctx, *d, src, (bytes + 15) & ~(size_t)15);
+    };
+    // (h2d_small copies whole 16-byte units: the sources below are padded copies)
+    auto padded = [](const void* p, size_t bytes) {
+        std::vector<uint8_t> v((bytes + 15) & ~(size_t)15, 0);
+        if (bytes) memcpy(v.data(), p, bytes);
+        return v;
+    };
+    VerifyPassArgs a;
+    a.batch = B, a.pstride = pstride;
+    a.nops = (uint32_t)vp.nops(), a.nslots = vp.nslots, a.nch = vp.nch, a.nev = (uint32_t)vp.ev_offsets.size();
+    a.nl_cap = (uint32_t)nl_cap, a.ncu = (uint32_t)(kk + 1), a.np = (uint32_t)np, a.ni = (uint32_t)ni1, a.nfixed = (uint32_t)(key.fixed_commitments.size() / 8);
+    uint32_t *d_ops, *d_consts, *d_evo, *d_outs, *d_ptsrc, *d_vpo, *d_key_xy, *d_srs_xy, *d_inst_xy, *d_vk, *d_pre;
+    {
+        const auto v = padded(vp.ops.data(), vp.ops.size() * 4);
+        BZH_TRY(put(v.data(), v.size(), &d_ops));
+    }
+    {
+        const auto v = padded(vp.consts.data(), vp.consts.size() * 4);
+        BZH_TRY(put(v.data(), v.size(), &d_consts));
+    }
+    {
+        const auto v = padded(vp.ev_offsets.data(), vp.ev_offsets.size() * 4);
+        BZH_TRY(put(v.data(), v.size(), &d_evo));
+    }
+    {
+        const auto v = padded(vp.out_slots.data(), vp.out_slots.size() * 4);
+        BZH_TRY(put(v.data(), v.size(), &d_outs));
+    }
+    {
+        const auto v = padded(vp.pt_src.data(), vp.pt_src.size() * 4);
+        BZH_TRY(put(v.data(), v.size(), &d_ptsrc));
+    }
+    {
+        const auto v = padded(key.vp_offsets.data(), key.vp_offsets.size() * 4);
+        BZH_TRY(put(v.data(), v.size(), &d_vpo));
+    }
+    {
+        std::vector<uint64_t> kx(key.fixed_commitments);
+        kx.insert(kx.end(), key.sigma_commitments.begin(), key.sigma_commitments.end());
+        kx.resize(kx.size() + 8, 0);
+        BZH_TRY(put(kx.data(), kx.size() * 8, &d_key_xy));
+    }
+    BZH_TRY(put(g0_u_w, 3 * 64, &d_srs_xy));
+    BZH_TRY(put(inst_xy.data(), inst_xy.size() * 8, &d_inst_xy));
+    BZH_TRY(put(key.vk_repr, 32, &d_vk));
+    std::vector<uint32_t> pre((B + 3) & ~(size_t)3, 0);
+    for (size_t b = 0; b < B; b++) pre[b] = proof_lens[b] != plen ? 1u : 0u;
+    std::vector<uint8_t> pre8((B + 15) & ~(size_t)15, 0);
+    for (size_t b = 0; b < B; b++) pre8[b] = (uint8_t)pre[b];
+    BZH_TRY(put(pre8.data(), pre8.size(), &d_pre));
+    uint8_t* d_rows = (uint8_t*)arena.alloc(B * pstride + 16);
+    uint32_t* d_in = words(np_all * 8 + 8);
+    uint32_t* d_xy = words(np_all * 16 + 16);
+    uint8_t* d_st = (uint8_t*)arena.alloc(np_all + 16);
+    uint32_t* d_ch = words((size_t)vp.nch * B * 8);
+    uint32_t* d_slots = words((size_t)vp.nslots * 8 * B);
+    uint32_t* d_lc_scal = words(B * nl_cap * 8);
+    uint32_t* d_lc_pts = words(B * nl_cap * 16);
+    uint32_t* d_cu = words(B * (kk + 1) * 8);
+    uint32_t* d_flags = words(B + 4);
+    uint8_t* d_reject = (uint8_t*)arena.alloc(pre8.size());
+    if (!d_rows || !d_in || !d_xy || !d_st || !d_ch || !d_slots || !d_lc_scal || !d_lc_pts || !d_cu || !d_flags || !d_reject) return BZH_E_OOM;
+    {   // the proofs: one upload
+        char* slot = nullptr;
+        BZH_TRY(h2d_stage(ctx, B * pstride, &slot));
+        for (size_t b = 0; b < B; b++) {
+            char* dst = slot + b * pstride;
+            if (pre[b]) {
+                memset(dst, 0, pstride);
+            } else {
+                memcpy(dst, proofs + b * proof_stride, plen);
+                if (pstride > plen) memset(dst + plen, 0, pstride - plen);
+            }
+        }
+        BZH_TRY(h2d_commit(ctx, d_rows, slot, B * pstride));
+    }
+    a.d_proofs = d_rows, a.d_ops = d_ops, a.d_consts = d_consts, a.d_ev_offsets = d_evo, a.d_out_slots = d_outs, a.d_pt_src = d_ptsrc;
+    a.d_vp_offsets = d_vpo, a.d_ch = d_ch, a.d_slots = d_slots, a.d_lc_scal = d_lc_scal, a.d_cu = d_cu, a.d_flags = d_flags;
+    a.d_proof_xy = d_xy, a.d_key_xy = d_key_xy, a.d_inst_xy = d_inst_xy, a.d_srs_xy = d_srs_xy, a.d_point_status = d_st;
+    a.d_pre_reject = (const uint8_t*)d_pre, a.d_lc_pts = d_lc_pts, a.d_reject = d_reject;
+    BZH_TRY(vp_gather_points(ctx, a, d_in));
+    BZH_TRY(decompress_run(ctx, C::id, d_in, np_all, BZH_FORM_CANONICAL, d_xy, d_st));
+    mark("vd:stage+decompress");
+    // the transcripts of the whole batch, in lockstep
+    bzh_transcript_batch* tb = nullptr;
+    BZH_TRY(tb_new_locked(ctx, C::id, B, &tb));
+    struct TbGuard {
+        bzh_transcript_batch* t;
+        ~TbGuard() { tb_free_locked(t); }
+    } tb_guard{tb};
+    for (size_t i = 0; i + 2 < vp.schedule.size(); i += 3) {
+        const uint32_t kind = vp.schedule[i], first = vp.schedule[i + 1], count = vp.schedule[i + 2];
+        switch (kind) {
+            case VP_TS_VK: BZH_TRY(tb_absorb_locked(tb, 2, d_vk, 1, 0, BZH_FORM_CANONICAL, nullptr)); break;
+            case VP_TS_INST: BZH_TRY(tb_absorb_locked(tb, 0, d_inst_xy, count, ni1, BZH_FORM_CANONICAL, nullptr)); break;
+            case VP_TS_POINTS: BZH_TRY(tb_absorb_locked(tb, 0, d_xy + (size_t)first * 16, count, np, BZH_FORM_CANONICAL, d_st + first)); break;
+            case VP_TS_SQUEEZE: BZH_TRY(tb_squeeze_locked(tb, BZH_FORM_MONTGOMERY, d_ch + (size_t)first * B * 8)); break;
+            default: BZH_TRY(tb_absorb_locked(tb, 2, d_rows + first, count, pstride / 32, BZH_FORM_CANONICAL, nullptr));
+        }
+    }
+    a.d_tb_status = tb_status_device(tb);
+    mark("vd:transcripts");
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    if (trace && hipEventCreate(&ev_a) == hipSuccess && hipEventCreate(&ev_b) == hipSuccess) (void)hipEventRecord(ev_a, ctx->stream);
+    BZH_TRY(vp_scalars_run(ctx, C::id, a));
+    if (ev_b) (void)hipEventRecord(ev_b, ctx->stream);
+    BZH_TRY(vp_assemble_run(ctx, a));
+    std::vector<uint8_t> rej(pre8.size(), 1);
+    BZH_TRY(d2h_async(ctx, rej.data(), d_reject, rej.size()));
+    std::vector<int> ok(B, 0);
+    BZH_TRY(ipa_check_batch_device(ctx, srs, B, nl_cap, d_lc_pts, d_lc_scal, d_cu, ok.data()));
+    if (ev_b) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ev_a, ev_b) == hipSuccess)
+            fprintf(stderr, "[bzh_verify_batch] %-22s %8.3f ms  (%zu proofs, %zu ops, %zu inversions)\n", "vd:scalars", (double)ms, B, vp.nops(), vp.n_inv);
+    }
+    if (ev_a) (void)hipEventDestroy(ev_a);
+    if (ev_b) (void)hipEventDestroy(ev_b);
+    for (size_t b = 0; b < B; b++) results[b] = (ok[b] && !rej[b]) ? 1 : 0;
+    mark("vd:ipa check");
     return BZH_OK;
 }

@@ -376,6 +376,17 @@ int bzh_pk_lookup_selected(bzh_pk* pk, int* where);
 typedef enum { BZH_VERIFY_POINTS_HOST = 0, BZH_VERIFY_POINTS_DEVICE = 1 } bzh_verify_points_where;
 int bzh_pk_verify_select(bzh_pk* pk, int where);
 int bzh_pk_verify_selected(bzh_pk* pk, int* where);
+/* Where bzh_verify_batch runs the per-proof pass between the instance commitments and the IPA check -- the transcript replay,
+ * the point decompressions, expected h(x), the multiopen recombination and the IPA scalars: BZH_VERIFY_PASS_HOST on host threads,
+ * one proof each (every new key's default); BZH_VERIFY_PASS_DEVICE on the ctx's stream for the whole batch in lockstep -- the
+ * proof bytes go up once, one decompression launch, one batch of device transcripts, the key's scalar program one lane per
+ * proof (csrc/verify_program.hpp) -- and only two Jacobian sums and one reject byte per proof come back.  It implies device
+ * decompression whatever bzh_pk_verify_select says.  Same results[] either way; its speed has not been measured (DESIGN.md
+ * section 7).  BZH_E_ARG: NULL key or an unknown value, and the key keeps its selection.  A verify call under
+ * BZH_VERIFY_PASS_DEVICE on a key whose shape has no program (a degree no circuit reaches) is BZH_E_RANGE. */
+typedef enum { BZH_VERIFY_PASS_HOST = 0, BZH_VERIFY_PASS_DEVICE = 1 } bzh_verify_pass_where;
+int bzh_pk_verify_pass_select(bzh_pk* pk, int where);
+int bzh_pk_verify_pass_selected(bzh_pk* pk, int* where);
 /* Host only (no ctx, no GPU): the quotient program of a circuit blob as the source text of a BUILTIN kernel (namespace
  * bzh_q_<hash> with the kernel bzh_quotient_<hash> and a host function `launch`), and the program hash.  This is what the
  * build-time generator calls; BZH_E_RANGE if the circuit does not fit the evaluator (such circuits use the VM v1 fold). */
@@ -461,6 +472,11 @@ int bzh_vk_free(bzh_vk* vk);
 int bzh_verify_batch_vk(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch,
                         const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
                         const size_t* proof_lens, const uint64_t* g0_u_w, int* results);
+/* bzh_verify_batch_vk with the choice of bzh_verify_pass_where per call (a bzh_vk is immutable and shared between threads, so
+ * it carries no selection): bzh_verify_batch_vk is pass_where = BZH_VERIFY_PASS_HOST.  BZH_E_ARG for an unknown value. */
+int bzh_verify_batch_vk_with(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, int pass_where,
+                             size_t batch, const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
+                             const size_t* proof_lens, const uint64_t* g0_u_w, int* results);
 
 /* create_proof with the randomness drawn inside the library, as the reference does from OsRng (benches/shot.rs:68): proof b's
  * stream is ChaCha20 keyed by seeds[b] (32 bytes; 64-bit block counter from 0, zero nonce), block i being the i-th 64-byte draw
