@@ -204,7 +204,9 @@ class NativeProvingKey:
 
     # ---- where the lookup argument's columns are permuted ----------------------------------------------------
     def lookup_selected(self) -> int:
-        """LOOKUP_HOST (pinned round trip + host sorts) or LOOKUP_DEVICE (csrc/lookup_permute.hip on the ctx's stream)"""
+        """LOOKUP_DEVICE (csrc/lookup_permute.hip on the ctx's stream; every new key's default) or LOOKUP_HOST (pinned round
+        trip + host sorts).  A key on which lookup_select was never called reports LOOKUP_DEVICE and takes the host path for
+        batches of fewer than 8 proofs (include/bzh2.h)"""
         L = _bind()
         L.bzh_pk_lookup_selected.argtypes = [_VP, ctypes.POINTER(ctypes.c_int)]
         w = ctypes.c_int()

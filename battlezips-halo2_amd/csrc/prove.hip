@@ -352,6 +352,7 @@ int bzh_pk_lookup_select(bzh_pk* pk, int where) {
     if (!pk || (where != BZH_LOOKUP_HOST && where != BZH_LOOKUP_DEVICE)) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(pk->mu);
     pk->lk_select = where;
+    pk->lk_chosen = true;
     return BZH_OK;
 }
 

@@ -45,6 +45,7 @@ struct Prover : DeviceColumns<C> {
     struct Lk {
         uint32_t *a_c, *s_c, *as, *polys, *cosets;   // compressed input, table | permuted (a, s) pair | its coefficients | cosets
         std::vector<Fe<SF>> blinds;  // (a, s) per proof
+        std::vector<int32_t> status; // device permutation: one word per proof, landed by the d2h_finish of this lookup's commitment
     };
     std::vector<Lk> lk;
     uint32_t *zs = nullptr, *z_polys = nullptr, *z_cosets = nullptr;   // grand products: permutation sets, then lookups
@@ -468,22 +469,33 @@ struct Prover : DeviceColumns<C> {
         return to_extended(adv_cosets, adv_polys, B * na);
     }
 
+    // A key on which bzh_pk_lookup_select was never called permutes on the device from this batch size up and on the host below
+    // it.  Measured per bzh_prove_batch call on one MI355X box (Board, k = 14, seeded, HOST and DEVICE alternating on one key,
+    // median of five): B = 1 HOST 14.96 ms, DEVICE 15.03; B = 8 HOST 26.02, DEVICE 25.76; B = 64 HOST 103.94, DEVICE 101.66 --
+    // and `bench.py --batch 1 --concurrency 1 --no-kernel-timers` 9.51 ms per proof on the host path against 9.61 on the device
+    // (three runs each, the host path's spread 0.04 ms): with one pair the device path is a chain of one- and two-workgroup
+    // launches.  8 is the smallest size measured at which DEVICE is not worse.
+    static constexpr size_t kLookupDeviceMinBatch = 8;
+
     // The lookup permutation on the device (csrc/lookup_permute.hip), straight from the Montgomery columns into d.as in its
-    // (B, 2, n) layout; only the B status words come back.  reads d.a_c, d.s_c; fills d.as up to `usable`
+    // (B, 2, n) layout.  Nothing is waited for here: the B status words are queued with d2h_async into d.status (a member of Lk,
+    // so the destination outlives this scope) and land at the d2h_finish of this lookup's own commitment; lookups() reads them
+    // there, before anything of this lookup goes into a transcript.  Committing the columns of a pair that turns out to have
+    // failed is safe: such a pair keeps every index in bounds and still writes every row below `usable` of both columns with a
+    // reduced field element (it has more leftovers than repeated rows and drops the surplus: csrc/lookup_permute.hip).
+    // The workspace goes back to the arena when the scope ends, before the device has run any of this: its kernels and the copy
+    // of the status words are queued on the ctx's stream, and so is everything that takes the same arena memory afterwards (all
+    // device work of a prove call runs on that one stream), so the later work cannot overtake them.
+    // reads d.a_c, d.s_c; fills d.as up to `usable`, queues d.status
     int permute_on_device(Lk& d) {
         mark(" lk:compress");
-        std::vector<int32_t> lk_status(B, 0);
-        {
-            ArenaScope scope(arena);
-            void* ws = arena.alloc(lookup_permute_ws_bytes(usable, B));
-            if (!ws) return BZH_E_OOM;
-            int32_t* d_status = nullptr;
-            BZH_TRY(lookup_permute(ctx, field, d.a_c, d.s_c, n, usable, B, BZH_FORM_MONTGOMERY, d.as, d.as + n * 8, 2 * n, n, ws, &d_status));
-            BZH_TRY(d2h_async(ctx, lk_status.data(), d_status, B * sizeof(int32_t)));
-            BZH_TRY(d2h_finish(ctx));
-        }
-        for (int32_t rc : lk_status)
-            if (rc) return rc;
+        d.status.assign(B, 0);
+        ArenaScope scope(arena);
+        void* ws = arena.alloc(lookup_permute_ws_bytes(usable, B));
+        if (!ws) return BZH_E_OOM;
+        int32_t* d_status = nullptr;
+        BZH_TRY(lookup_permute(ctx, field, d.a_c, d.s_c, n, usable, B, BZH_FORM_MONTGOMERY, d.as, d.as + n * 8, 2 * n, n, ws, &d_status));
+        BZH_TRY(d2h_async(ctx, d.status.data(), d_status, B * sizeof(int32_t)));
         mark(" lk:permute");
         return BZH_OK;
     }
@@ -536,11 +548,12 @@ struct Prover : DeviceColumns<C> {
         return BZH_OK;
     }
 
-    // 3. lookups: compress, permute (host sort or device kernels: bzh_pk_lookup_select), blind and commit; then beta, gamma.
+    // 3. lookups: compress, permute (device kernels or host sort: bzh_pk_lookup_select), blind and commit; then beta, gamma.
     // reads adv, inst, env[SY_THETA]; fills lk (all but the cosets), inst_cosets, adv_cosets, env[SY_BETA], env[SY_GAMMA]
     int lookups() {
         const bool lk_device = [&] {
             std::lock_guard<std::mutex> g(pk.mu);
+            if (!pk.lk_chosen) return B >= kLookupDeviceMinBatch;
             return pk.lk_select == BZH_LOOKUP_DEVICE;
         }();
         lk.resize(nl);
@@ -571,6 +584,8 @@ struct Prover : DeviceColumns<C> {
             }
             BZH_TRY(to_coeff(d.polys, d.as, B * 2));
             BZH_TRY(commit_columns(d.as, d.polys, B * 2, d.blinds, xy));
+            for (int32_t rc : d.status)   // (device permutation) landed with the commitments; the first failed pair's status
+                if (rc) return rc;
             for (size_t b = 0; b < B; b++) {
                 bzh_transcript_write_point(T[b], C::id, &xy[(2 * b) * 8]);
                 bzh_transcript_write_point(T[b], C::id, &xy[(2 * b + 1) * 8]);
@@ -1145,5 +1160,8 @@ static int prove_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint32_t*
     }
     const int rc = pv.prove(d_advice, instances, inst_rows, proofs, proof_stride, proof_lens);
     (void)hipStreamSynchronize(ctx->stream);
+    // a phase that failed between a d2h_async and its d2h_finish leaves read-backs whose destinations die with `pv`: they must
+    // not land at the next call's d2h_finish
+    if (rc) ctx->pending_d2h.clear();
     return rc;
 }

@@ -44,7 +44,8 @@ struct bzh_pk : bzh::KeyShape {
     hipModule_t q_module = nullptr;
     hipFunction_t q_fn = nullptr;
     int q_select = BZH_QUOTIENT_INTERPRETER;
-    int lk_select = BZH_LOOKUP_HOST;   // BZH_LOOKUP_*: where the lookup argument's columns are permuted (bzh_pk_lookup_select)
+    int lk_select = BZH_LOOKUP_DEVICE;   // BZH_LOOKUP_*: where the lookup argument's columns are permuted (bzh_pk_lookup_select)
+    bool lk_chosen = false;   // bzh_pk_lookup_select was called: lk_select holds for every batch size (else see kLookupDeviceMinBatch, prover.hpp)
     int vpass_select = BZH_VERIFY_PASS_HOST;  // BZH_VERIFY_PASS_*: where bzh_verify_batch runs the per-proof pass (bzh_pk_verify_pass_select)
     int vp_select = BZH_VERIFY_POINTS_HOST;   // BZH_VERIFY_POINTS_*: where bzh_verify_batch decompresses the proofs' points (bzh_pk_verify_select)
     // per-call workspaces: one grow-only arena per ctx that has used the key (several worker streams share ONE key)

@@ -361,10 +361,14 @@ int bzh_pk_quotient_source(bzh_pk* pk, char* buf, size_t cap, size_t* len);
 int bzh_pk_set_quotient_module(bzh_ctx* ctx, bzh_pk* pk, const void* code_object, size_t len);
 int bzh_pk_quotient_select(bzh_pk* pk, int flavour);
 int bzh_pk_quotient_selected(bzh_pk* pk, int* flavour, int* builtin_available);
-/* Where bzh_prove_batch permutes the lookup argument's columns: BZH_LOOKUP_HOST moves the compressed columns to pinned host
- * memory and sorts them on host threads (bzh_permute_expression_pair per proof); BZH_LOOKUP_DEVICE runs
- * bzh_permute_expression_pair_batch's kernels on the ctx's stream and reads back one status word per proof.  Same proof bytes
- * and statuses either way.  BZH_E_ARG: NULL key or an unknown value. */
+/* Where bzh_prove_batch permutes the lookup argument's columns: BZH_LOOKUP_DEVICE (every new key's default) runs
+ * bzh_permute_expression_pair_batch's kernels on the ctx's stream; the one status word per proof comes back with the lookup's
+ * commitments, without a stream synchronisation of its own.  BZH_LOOKUP_HOST moves the compressed columns to pinned host memory
+ * and sorts them on host threads (bzh_permute_expression_pair per proof).  Same proof bytes and statuses either way: a lookup
+ * input without a table copy is BZH_E_RANGE, and nothing of that batch is written.  A key on which bzh_pk_lookup_select was never
+ * called reports BZH_LOOKUP_DEVICE and chooses per call: the device for a batch of 8 proofs or more, the host path below that
+ * (a single proof is 0.1 ms slower with the one-workgroup launches the device path makes for it); a call of
+ * bzh_pk_lookup_select fixes the choice for every batch size.  BZH_E_ARG: NULL key or an unknown value. */
 typedef enum { BZH_LOOKUP_HOST = 0, BZH_LOOKUP_DEVICE = 1 } bzh_lookup_where;
 int bzh_pk_lookup_select(bzh_pk* pk, int where);
 int bzh_pk_lookup_selected(bzh_pk* pk, int* where);
