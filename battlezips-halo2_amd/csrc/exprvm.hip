@@ -16,15 +16,13 @@
 #include "ctx.hpp"
 #include "field.cuh"
 #include "host_field.hpp"
+#include "vm2_isa.hpp"
 
 namespace bzh {
 
 static constexpr int kExprSlots = 24;
 
-struct ExprOp {  // mirrors bzh_expr_op
-    uint8_t op, dst, a_kind, b_kind;
-    int32_t a_idx, b_idx, a_rot, b_rot;
-};
+using ExprOp = bzh_expr_op;
 
 template <class P>
 __device__ __forceinline__ Fe<P> expr_operand(int kind, int idx, int rot, const Fe<P>* slots, const uint32_t* const* cols,
@@ -163,17 +161,12 @@ int expr_eval(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint3
 //     [slot][half][thread] of uint4, conflict-free ds_read/write_b128;
 //   * leaves (column at a rotation, constant, LDS slot) are operands of the instruction that consumes them.
 // Instruction forms: SS r[p] = r[p] op r[p+1];  SL r[p] = r[p] op leaf;  LL r[p] = leafA op leafB;  unary NEG / LOAD /
-// STORE.  op in {ADD, SUB, MUL, RSUB (b - a)}.  Modular-integer VALU work, no MFMA.
+// STORE.  op in {ADD, SUB, MUL, RSUB (b - a)}: the instruction word and its encoding are csrc/vm2_isa.hpp.
+// Modular-integer VALU work, no MFMA.
 // ---------------------------------------------------------------------------------------------------------------
-struct ExprOp2 {
-    uint8_t code, a_kind, b_kind, pad;
-    int32_t a_idx, b_idx;
-    int16_t a_rot, b_rot;
-};
-static_assert(sizeof(ExprOp2) == 16, "ExprOp2 layout");
 
 // rows per workgroup: 128, or 64 for a program whose slot file would not fit 64 KB of LDS at 128 (more than 16 slots: the
-// quotient programs with column leaves in slots, csrc/quotient_program.hpp)
+// quotient programs with column leaves in slots, csrc/quotient_compiler.hpp)
 static constexpr int kVm2Threads = 128, kVm2ThreadsSmall = 64;
 
 template <class P, int kRows>
@@ -202,17 +195,17 @@ __global__ void __launch_bounds__(kRows) k_expr_vm2(const ExprOp2* __restrict__ 
         vm2_lds[((size_t)idx * 2) * kRows + t] = make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]);
         vm2_lds[((size_t)idx * 2 + 1) * kRows + t] = make_uint4(x.l[4], x.l[5], x.l[6], x.l[7]);
     };
-#define VM2_ARITH(OP, A, B) ((OP) == 0 ? fe_add(A, B) : ((OP) == 1 ? fe_sub(A, B) : ((OP) == 2 ? fe_mul(A, B) : fe_sub(B, A))))
-#define VM2_SS(OP, P0, RA, RB) case (0 << 4) | ((OP) << 2) | (P0): RA = VM2_ARITH(OP, RA, RB); break;
-#define VM2_SL(OP, P0, RA)     case (1 << 4) | ((OP) << 2) | (P0): { const Fe<P> b_ = leaf(op.b_kind, op.b_idx, op.b_rot); RA = VM2_ARITH(OP, RA, b_); } break;
-#define VM2_LL(OP, P0, RA)     case (2 << 4) | ((OP) << 2) | (P0): { const Fe<P> a_ = leaf(op.a_kind, op.a_idx, op.a_rot); const Fe<P> b_ = leaf(op.b_kind, op.b_idx, op.b_rot); RA = VM2_ARITH(OP, a_, b_); } break;
-#define VM2_ALLOPS_SS(P0, RA, RB) VM2_SS(0, P0, RA, RB) VM2_SS(1, P0, RA, RB) VM2_SS(2, P0, RA, RB) VM2_SS(3, P0, RA, RB)
-#define VM2_ALLOPS_SL(P0, RA) VM2_SL(0, P0, RA) VM2_SL(1, P0, RA) VM2_SL(2, P0, RA) VM2_SL(3, P0, RA)
-#define VM2_ALLOPS_LL(P0, RA) VM2_LL(0, P0, RA) VM2_LL(1, P0, RA) VM2_LL(2, P0, RA)
+#define VM2_ARITH(OP, A, B) ((OP) == V2_ADD ? fe_add(A, B) : ((OP) == V2_SUB ? fe_sub(A, B) : ((OP) == V2_MUL ? fe_mul(A, B) : fe_sub(B, A))))
+#define VM2_SS(OP, P0, RA, RB) case ExprOp2::encode(V2_SS, OP, P0): RA = VM2_ARITH(OP, RA, RB); break;
+#define VM2_SL(OP, P0, RA)     case ExprOp2::encode(V2_SL, OP, P0): { const Fe<P> b_ = leaf(op.b_kind, op.b_idx, op.b_rot); RA = VM2_ARITH(OP, RA, b_); } break;
+#define VM2_LL(OP, P0, RA)     case ExprOp2::encode(V2_LL, OP, P0): { const Fe<P> a_ = leaf(op.a_kind, op.a_idx, op.a_rot); const Fe<P> b_ = leaf(op.b_kind, op.b_idx, op.b_rot); RA = VM2_ARITH(OP, a_, b_); } break;
+#define VM2_ALLOPS_SS(P0, RA, RB) VM2_SS(V2_ADD, P0, RA, RB) VM2_SS(V2_SUB, P0, RA, RB) VM2_SS(V2_MUL, P0, RA, RB) VM2_SS(V2_RSUB, P0, RA, RB)
+#define VM2_ALLOPS_SL(P0, RA) VM2_SL(V2_ADD, P0, RA) VM2_SL(V2_SUB, P0, RA) VM2_SL(V2_MUL, P0, RA) VM2_SL(V2_RSUB, P0, RA)
+#define VM2_ALLOPS_LL(P0, RA) VM2_LL(V2_ADD, P0, RA) VM2_LL(V2_SUB, P0, RA) VM2_LL(V2_MUL, P0, RA)
 #define VM2_UN(P0, RA)                                                                                   \
-    case (3 << 4) | (0 << 2) | (P0): RA = fe_neg(RA); break;                                              \
-    case (3 << 4) | (1 << 2) | (P0): RA = leaf(op.a_kind, op.a_idx, op.a_rot); break;                     \
-    case (3 << 4) | (2 << 2) | (P0): store(op.a_idx, RA); break;
+    case ExprOp2::encode(V2_UN, V2_NEG, P0): RA = fe_neg(RA); break;                                      \
+    case ExprOp2::encode(V2_UN, V2_LOAD, P0): RA = leaf(op.a_kind, op.a_idx, op.a_rot); break;             \
+    case ExprOp2::encode(V2_UN, V2_STORE, P0): store(op.a_idx, RA); break;
     ExprOp2 nxt = prog[0];
     for (int i = 0; i < nops; i++) {
         const ExprOp2 op = nxt;       // wave-uniform: scalar loads, scalar branch

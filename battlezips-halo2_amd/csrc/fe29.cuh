@@ -194,7 +194,7 @@ BZH_HD Fe29<P> fe29_sub(const Fe29<P>& a, const Fe29<P>& b) {
 }
 // a - b + K p WITHOUT the carry pass, the bias written as J copies of (K / J) p: b's limbs 0..7 may be anything up to
 // J (2^30 - 2) and its top limb up to K 2^22 - 2 J; the result's limbs grow by up to J (2^30 + 2^29) over a's.  For callers that
-// track limb bounds themselves (the quotient generator, quotient_program.hpp: a carry pass only where a product or a
+// track limb bounds themselves (the quotient generator, quotient_emit.hpp: a carry pass only where a product or a
 // subtrahend needs it).
 template <class P, int K, int J>
 BZH_HD Fe29<P> fe29_sub_lazy(const Fe29<P>& a, const Fe29<P>& b) {

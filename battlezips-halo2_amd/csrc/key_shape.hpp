@@ -17,7 +17,7 @@ struct CNode {
 };
 
 // registry keys
-enum { K_ADV = 1, K_FIX, K_INST, K_SIGMA, K_IDENT, K_PZ, K_LA, K_LS, K_LZ, K_MISC };
+enum { K_ADV = 1, K_FIX, K_INST, K_SIGMA, K_IDENT, K_PZ, K_LA, K_LS, K_LZ, K_MISC, K_HOIST };
 enum { M_L0, M_LLAST, M_LBLIND, M_X, M_TINV, M_AC, M_SC, M_A, M_S, M_ACC, M_Q, M_R, M_F, M_H0 /* + i */ };
 static inline uint64_t key(int kind, uint64_t i) { return ((uint64_t)kind << 32) | i; }
 

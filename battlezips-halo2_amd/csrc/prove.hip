@@ -42,13 +42,16 @@
 #include "curve.cuh"
 #include "fe29.cuh"
 #include "host_field.hpp"
+#include "vm2_isa.hpp"
 
 // the table of quotient kernels generated at build time (quotient_builtin.hip); absent (null) in the generator's own link
 extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __attribute__((weak));
 
 #include "prove_kernels.cuh"     // opens namespace bzh { namespace {
 #include "key_shape.hpp"         // what both keys share: blob reader, arena, KeyShape and its parser (host only)
-#include "quotient_program.hpp"  // the compiler (host only)
+#include "expr_compiler.hpp"     // the expression pool, the VM v1 compiler (host only)
+#include "quotient_compiler.hpp" // the quotient's VM v2 program (host only)
+#include "quotient_emit.hpp"     // ... as HIP source, in two limb forms (host only)
 #include "proving_key.hpp"       // closes them around the global struct bzh_pk, reopens; keygen
 #include "verifying_key.hpp"     // likewise around bzh_vk; its byte format and host-only entry points
 #include "device_columns.hpp"     // columns on the device, their commitments: shared by prover, verifier and keygen_vk
@@ -130,7 +133,7 @@ static int quotient_histogram_t(const uint8_t* circuit, size_t circuit_len, uint
     const int rc = bzh::pk_parse_t<C>(circuit, circuit_len, pk, po);
     if (rc) return rc;
     bzh::Cols reg;
-    bzh::quotient_registry(pk, bzh::QuotientPtrs{}, reg);
+    bzh::quotient_registry(pk, bzh::QuotientPtrs{}, false, reg);
     bzh::EPool ep;
     int tinv = -1;
     const std::vector<int> terms = bzh::quotient_terms<SF>(pk, reg, ep, &tinv);
@@ -236,7 +239,7 @@ int bzh_pk_quotient_stats(bzh_pk* pk, uint32_t* ops, uint32_t* multiplications, 
     if (pk->q_ok) {
         no = (uint32_t)pk->qprog.ops.size();
         nl = (uint32_t)pk->qprog.nlds;
-        for (auto& o : pk->qprog.ops) nm += ((o.code >> 4) < 3 && ((o.code >> 2) & 3) == bzh::V2_MUL);
+        nm = (uint32_t)bzh::program2_muls(pk->qprog);
     }
     if (ops) *ops = no;
     if (multiplications) *multiplications = nm;
@@ -297,9 +300,7 @@ int bzh_quotient_program_for_circuit(int curve, const uint8_t* circuit, size_t c
     *nops = pg.ops.size();
     *nconsts = pg.consts.size();
     if (stats8) {
-        uint32_t nm = 0;
-        for (auto& o : pg.ops) nm += ((o.code >> 4) < 3 && ((o.code >> 2) & 3) == bzh::V2_MUL);
-        const uint32_t st[8] = {(uint32_t)pg.ops.size(), nm, (uint32_t)pg.nlds, (uint32_t)bzh::program2_loads(pg), (uint32_t)pg.leaf_slots,
+        const uint32_t st[8] = {(uint32_t)pg.ops.size(), (uint32_t)bzh::program2_muls(pg), (uint32_t)pg.nlds, (uint32_t)bzh::program2_loads(pg), (uint32_t)pg.leaf_slots,
                                 (uint32_t)pg.leaf_base, (uint32_t)pk.hoist_cols, 0};
         memcpy(stats8, st, sizeof(st));
     }

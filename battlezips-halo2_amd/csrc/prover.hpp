@@ -265,105 +265,53 @@ struct Prover : DeviceColumns<C> {
                          per_proof ? nc : 0, size, pg.result_slot, B, nslots, d_out);
     }
 
-    // the quotient through VM v2 (the program compiled at bzh_pk_create), as the builtin kernel, the caller's module or the
-    // interpreter.  Returns BZH_E_RANGE when the circuit does not fit VM v2 (the caller falls back to the plain fold through `run`).
-    // The builtin kernel in unsaturated limbs.  qp holds fe29 PLANE buffers here (to_extended wrote them: [proof][column][9 size
-    // words]); the key's columns were converted at bzh_pk_create, the constants are converted on the host.  The column order is
-    // quotient_registry's (the program's column indices refer to it), followed by the hoisted columns.
-    int run_quotient29(const QuotientPtrs& qp, size_t size, uint32_t* d_out) {
-        const Program2& pg = pk.qprog;
-        const size_t nc = pg.consts.size(), col = 9 * size;
-        std::vector<const uint32_t*> ptrs;
-        std::vector<size_t> strides;
-        auto add = [&](const uint32_t* p, size_t stride_words) {
-            ptrs.push_back(p);
-            strides.push_back(stride_words);
-        };
-        const uint32_t *k_fixed = pk.key29, *k_sigma = k_fixed + (size_t)nf * col, *k_misc = k_sigma + m * col, *k_hoist = k_misc + 5 * col;
-        for (int i = 0; i < na; i++) add(qp.adv + (size_t)i * col, (size_t)na * col);
-        for (int i = 0; i < nf; i++) add(k_fixed + (size_t)i * col, 0);
-        for (int i = 0; i < ni; i++) add(qp.inst + (size_t)i * col, (size_t)ni * col);
-        for (size_t j = 0; j < m; j++) add(k_sigma + j * col, 0);
-        for (int i = 0; i < nsets; i++) add(qp.z + (size_t)i * col, (size_t)nz * col);
-        for (int i = 0; i < nl; i++) {
-            add(qp.lk[(size_t)i], 2 * col);
-            add(qp.lk[(size_t)i] + col, 2 * col);
-            add(qp.z + (size_t)(nsets + i) * col, (size_t)nz * col);
-        }
-        for (int i = 0; i < 5; i++) add(k_misc + (size_t)i * col, 0);     // l0, l_last, l_blind, X, 1 / (X^n - 1)
-        {   // the same shape as the saturated registry, or the program's column indices would point elsewhere
-            Cols check;
-            quotient_registry(pk, QuotientPtrs{}, check);
-            if (check.ptr.size() != ptrs.size()) return BZH_E_ARG;
-        }
-        for (size_t hi = 0; hi < pk.hoist_cols; hi++) add(k_hoist + hi * col, 0);
-        std::vector<uint32_t> cv;   // 9 limbs in a 12-word slot
-        BZH_TRY(fill_consts(pg.consts, B, 12, [](uint32_t* dst, const Fe<SF>& v) {
-            const Fe29<SF> w = fe29_from_sat_reduced(v);
-            memcpy(dst, w.l, 36);
-        }, cv));
-        ProgramArgs pa;
-        BZH_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), 0, ptrs.data(), strides.data(), ptrs.size(), pa));
-        if (ctx->profiling) {
-            double cols_read = 0;
-            for (size_t i = 0; i < strides.size() - pk.hoist_cols; i++) cols_read += strides[i] ? (double)B : 1.0;
-            ctx->alg_bytes[BZH_T_QUOTIENT] += (cols_read + (double)B) * (double)size * 32.0;
-        }
-        ScopedTimer t(ctx, BZH_T_QUOTIENT);
-        pk.q_builtin29((unsigned)(size / 128), (unsigned)B, (void*)st, (const uint32_t* const*)pa.ptrs, (const size_t*)pa.strides, pa.consts, nc, size, d_out);
-        BZH_HIP_TRY(ctx, hipGetLastError());
-        return BZH_OK;
+    // The quotient through VM v2 (the program compiled at bzh_pk_create), in one of four flavours: the builtin kernel in unsaturated
+    // limbs (q29: `reg` then holds fe29 PLANES -- to_extended wrote the per-proof ones, the key's were converted at bzh_pk_create --
+    // and the constants are converted here, 9 limbs in a 12-word slot), the builtin kernel in saturated limbs, the caller's module,
+    // the interpreter.  Returns BZH_E_RANGE when the circuit does not fit VM v2 (the caller falls back to the plain fold through `run`).
+    static void put_fe29(uint32_t* dst, const Fe<SF>& v) {
+        const Fe29<SF> w = fe29_from_sat_reduced(v);
+        memcpy(dst, w.l, 36);
     }
-
     int run_quotient(const Cols& reg, size_t size, uint32_t* d_out) {
         if (!pk.q_ok || size % 128 || size != pk.en) return BZH_E_RANGE;
         hipFunction_t q_fn = nullptr;
         bzh_quotient_launch_fn q_builtin = nullptr;
-        {
+        if (q29) {
+            q_builtin = pk.q_builtin29;
+        } else {
             std::lock_guard<std::mutex> lk(pk.mu);
             if (pk.q_select == BZH_QUOTIENT_MODULE) q_fn = pk.q_fn;
             else if (pk.q_select == BZH_QUOTIENT_BUILTIN) q_builtin = pk.q_builtin;
         }
-        const Program2* pgp = &pk.qprog;
-        const Program2& pg = *pgp;
-        if (!pg.ok) return BZH_E_RANGE;
-        const size_t nc = pg.consts.size(), ncols = reg.ptr.size() + pk.hoist_cols;
-        std::vector<const uint32_t*> ptrs(reg.ptr);
-        std::vector<size_t> strides(reg.stride);
-        for (size_t hi = 0; hi < pk.hoist_cols; hi++) {
-            ptrs.push_back(pk.hoist + hi * size * 8);
-            strides.push_back(0);
-        }
+        const Program2& pg = pk.qprog;
+        const size_t nc = pg.consts.size(), ncols = reg.ptr.size();
         std::vector<uint32_t> cv;
-        BZH_TRY(fill_consts(pg.consts, B, 8, put_saturated, cv));
-        ProgramArgs pa;
-        BZH_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), pg.ops.size() * sizeof(ExprOp2), ptrs.data(), strides.data(), ncols, pa));
-        uint32_t* d_consts = pa.consts;
-        char *d_prog = pa.prog, *d_ptrs = pa.ptrs, *d_strides = pa.strides;
+        BZH_TRY(fill_consts(pg.consts, B, q29 ? 12 : 8, q29 ? put_fe29 : put_saturated, cv));
+        ProgramArgs pa;   // (the unsaturated kernel's launch carries no instructions: only the interpreter reads them)
+        BZH_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), q29 ? 0 : pg.ops.size() * sizeof(ExprOp2), reg.ptr.data(), reg.stride.data(), ncols, pa));
+        const uint32_t* const* d_ptrs = (const uint32_t* const*)pa.ptrs;
+        const size_t* d_strides = (const size_t*)pa.strides;
+        const uint32_t* d_consts = pa.consts;
         if (ctx->profiling) {   // the quotient pass reads every extended column once and writes h: per-proof columns
-            double cols_read = 0;   // count per proof, columns of the key once per launch
-            for (size_t i = 0; i < reg.stride.size(); i++) cols_read += reg.stride[i] ? (double)B : 1.0;
+            double cols_read = 0;   // count per proof, columns of the key once per launch (the hoisted ones not at all)
+            for (size_t i = 0; i < ncols - pk.hoist_cols; i++) cols_read += reg.stride[i] ? (double)B : 1.0;
             ctx->alg_bytes[BZH_T_QUOTIENT] += (cols_read + (double)B) * (double)size * 32.0;
         }
         if (q_builtin) {   // the same program as a kernel generated at build time
             ScopedTimer t(ctx, BZH_T_QUOTIENT);
-            q_builtin((unsigned)(size / 128), (unsigned)B, (void*)st, (const uint32_t* const*)d_ptrs, (const size_t*)d_strides, d_consts, nc, size, d_out);
+            q_builtin((unsigned)(size / 128), (unsigned)B, (void*)st, d_ptrs, d_strides, d_consts, nc, size, d_out);
             BZH_HIP_TRY(ctx, hipGetLastError());
             return BZH_OK;
         }
         if (q_fn) {   // the same program as a code object of the caller's (bzh_pk_set_quotient_module)
             ScopedTimer t(ctx, BZH_T_QUOTIENT);
-            const uint32_t* const* a_cols = (const uint32_t* const*)d_ptrs;
-            const size_t* a_strides = (const size_t*)d_strides;
-            const uint32_t* a_consts = d_consts;
             size_t a_nc = nc, a_size = size;
-            uint32_t* a_out = d_out;
-            void* args[] = {&a_cols, &a_strides, &a_consts, &a_nc, &a_size, &a_out};
+            void* args[] = {&d_ptrs, &d_strides, &d_consts, &a_nc, &a_size, &d_out};
             BZH_HIP_TRY(ctx, hipModuleLaunchKernel(q_fn, (unsigned)(size / 128), (unsigned)B, 1, 128, 1, 1, 0, st, args, nullptr));
             return BZH_OK;
         }
-        return expr_eval2(ctx, field, d_prog, (int)pg.ops.size(), (const uint32_t* const*)d_ptrs, (const size_t*)d_strides, d_consts, nc, size, B,
-                          pg.nlds, d_out);
+        return expr_eval2(ctx, field, pa.prog, (int)pg.ops.size(), d_ptrs, d_strides, d_consts, nc, size, B, pg.nlds, d_out);
     }
 
     // ---- the phases of create_proof, in protocol order ---------------------------------------------------------------------
@@ -700,9 +648,9 @@ struct Prover : DeviceColumns<C> {
         QuotientPtrs qp;
         qp.adv = adv_cosets, qp.inst = inst_cosets, qp.z = z_cosets;
         for (int i = 0; i < nl; i++) qp.lk.push_back(lk[i].cosets);
-        quotient_registry(pk, qp, reg);   // (q29: the per-proof pointers are plane buffers; only run_quotient29 reads them)
+        quotient_registry(pk, qp, q29, reg);
         // VM v2 (gate-factored fold, shared subexpressions in LDS); the plain Horner fold through VM v1 if it does not fit
-        int qrc = q29 ? run_quotient29(qp, en, h) : (getenv("BZH_QUOTIENT_V1") ? BZH_E_RANGE : run_quotient(reg, en, h));
+        int qrc = !q29 && getenv("BZH_QUOTIENT_V1") ? BZH_E_RANGE : run_quotient(reg, en, h);
         if (qrc == BZH_E_RANGE && !q29) {
             qrc = run(key(40, 0), [&](EPool& ep) {
                 int tinv = -1;

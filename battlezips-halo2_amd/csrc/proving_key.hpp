@@ -38,7 +38,7 @@ struct bzh_pk : bzh::KeyShape {
     // q_select: BZH_QUOTIENT_* -- which of the three runs.
     bzh_quotient_launch_fn q_builtin = nullptr;
     // the builtin kernel's unsaturated-limb flavour (csrc/fe29.cuh) and the key-owned columns it reads as fe29 planes, converted
-    // once at bzh_pk_create: fixed cosets | sigma cosets | l0, l_last, l_blind, X, 1/(X^n - 1) | hoisted columns (9 en words each)
+    // once at bzh_pk_create (Key29Layout)
     bzh_quotient_launch_fn q_builtin29 = nullptr;
     uint32_t* key29 = nullptr;
     hipModule_t q_module = nullptr;
@@ -76,6 +76,23 @@ struct bzh_pk : bzh::KeyShape {
 
 namespace bzh {
 namespace {
+
+// column registry of one batched evaluation: (device pointer, elements between consecutive proofs; 0 = shared)
+struct Cols {
+    std::vector<const uint32_t*> ptr;
+    std::vector<size_t> stride;
+    std::map<uint64_t, int> index;
+    int add(uint64_t key, const uint32_t* p, size_t s) {
+        auto it = index.find(key);
+        if (it != index.end()) return it->second;
+        const int i = (int)ptr.size();
+        index[key] = i;
+        ptr.push_back(p);
+        stride.push_back(s);
+        return i;
+    }
+    int at(uint64_t key) const { return index.at(key); }
+};
 
 // circuit expression -> evaluator expression over `reg` (columns looked up by (kind, index))
 static int lower(const bzh_pk& pk, int i, EPool& ep, const Cols& reg, int rot_scale) {
@@ -122,28 +139,43 @@ struct QuotientPtrs {
     const uint32_t* z = nullptr;      // nsets + nl grand products
     std::vector<const uint32_t*> lk;  // per lookup: A' | S'
 };
+// The key's columns as fe29 planes (pk.key29), where each block begins, in columns of 9 en words:
+// fixed cosets | sigma cosets | l0, l_last, l_blind, X, 1/(X^n - 1) | hoisted columns
+struct Key29Layout {
+    size_t fixed, sigma, misc, hoist, end;
+    explicit Key29Layout(const bzh_pk& pk)
+        : fixed(0), sigma((size_t)pk.nf), misc(sigma + pk.perm_columns.size()), hoist(misc + 5), end(hoist + pk.hoist_cols) {}
+};
 // The registry fixes the column INDEX every instruction of the compiled program refers to: it must be built by this one
-// function, for the compile and for every launch.  stride = elements between consecutive proofs, 0 = shared (key-owned).
-static void quotient_registry(const bzh_pk& pk, const QuotientPtrs& q, Cols& reg) {
-    const size_t en = pk.en, m = pk.perm_columns.size();
+// function, for the compile, the hoisted columns' evaluation and every launch.  The per-proof columns and the key's are
+//   saturated elements (planes = false): 8 words an element, stride = ELEMENTS between consecutive proofs, the key's own columns; or
+//   fe29 planes (planes = true): 9 en words a column, stride = WORDS between consecutive proofs, the key's columns out of pk.key29;
+// stride 0 = shared (key-owned).  The hoisted columns come last.  Cols::add keeps what it has: compile_quotient calls this a
+// second time, once it knows how many hoisted columns there are.
+static void quotient_registry(const bzh_pk& pk, const QuotientPtrs& q, bool planes, Cols& reg) {
+    const size_t en = pk.en, m = pk.perm_columns.size(), w = planes ? 9 : 8, su = planes ? 9 * en : en;
     const int na = pk.na, nf = pk.nf, ni = pk.ni, nsets = pk.nsets, nl = pk.nl, nz = pk.nsets + pk.nl;
-    auto at = [](const uint32_t* base, size_t elems) -> const uint32_t* { return base ? base + elems * 8 : nullptr; };
-    for (int i = 0; i < na; i++) reg.add(key(K_ADV, i), at(q.adv, (size_t)i * en), (size_t)na * en);
-    for (int i = 0; i < nf; i++) reg.add(key(K_FIX, i), at(pk.fixed_cosets, (size_t)i * en), 0);
-    for (int i = 0; i < ni; i++) reg.add(key(K_INST, i), at(q.inst, (size_t)i * en), (size_t)ni * en);
-    for (size_t j = 0; j < m; j++) reg.add(key(K_SIGMA, j), at(pk.sigma_cosets, j * en), 0);
-    for (int i = 0; i < nsets; i++) reg.add(key(K_PZ, i), at(q.z, (size_t)i * en), (size_t)nz * en);
+    auto at = [&](const uint32_t* base, size_t elems) -> const uint32_t* { return base ? base + elems * w : nullptr; };
+    const Key29Layout k29(pk);
+    // (l0, l_last, l_blind, X, 1/(X^n - 1) are consecutive columns of the key's allocation too)
+    const uint32_t* k_fixed = planes ? at(pk.key29, k29.fixed * en) : pk.fixed_cosets;
+    const uint32_t* k_sigma = planes ? at(pk.key29, k29.sigma * en) : pk.sigma_cosets;
+    const uint32_t* k_misc = planes ? at(pk.key29, k29.misc * en) : pk.l0;
+    const uint32_t* k_hoist = planes ? at(pk.key29, k29.hoist * en) : pk.hoist;
+    for (int i = 0; i < na; i++) reg.add(key(K_ADV, i), at(q.adv, (size_t)i * en), (size_t)na * su);
+    for (int i = 0; i < nf; i++) reg.add(key(K_FIX, i), at(k_fixed, (size_t)i * en), 0);
+    for (int i = 0; i < ni; i++) reg.add(key(K_INST, i), at(q.inst, (size_t)i * en), (size_t)ni * su);
+    for (size_t j = 0; j < m; j++) reg.add(key(K_SIGMA, j), at(k_sigma, j * en), 0);
+    for (int i = 0; i < nsets; i++) reg.add(key(K_PZ, i), at(q.z, (size_t)i * en), (size_t)nz * su);
     for (int i = 0; i < nl; i++) {
         const uint32_t* c = (size_t)i < q.lk.size() ? q.lk[i] : nullptr;
-        reg.add(key(K_LA, i), c, 2 * en);
-        reg.add(key(K_LS, i), at(c, en), 2 * en);
-        reg.add(key(K_LZ, i), at(q.z, (size_t)(nsets + i) * en), (size_t)nz * en);
+        reg.add(key(K_LA, i), c, 2 * su);
+        reg.add(key(K_LS, i), at(c, en), 2 * su);
+        reg.add(key(K_LZ, i), at(q.z, (size_t)(nsets + i) * en), (size_t)nz * su);
     }
-    reg.add(key(K_MISC, M_L0), pk.l0, 0);
-    reg.add(key(K_MISC, M_LLAST), pk.l_last, 0);
-    reg.add(key(K_MISC, M_LBLIND), pk.l_blind, 0);
-    reg.add(key(K_MISC, M_X), pk.x_col, 0);
-    reg.add(key(K_MISC, M_TINV), pk.tinv_col, 0);
+    static const int misc[5] = {M_L0, M_LLAST, M_LBLIND, M_X, M_TINV};
+    for (size_t i = 0; i < 5; i++) reg.add(key(K_MISC, misc[i]), at(k_misc, i * en), 0);
+    for (size_t hi = 0; hi < pk.hoist_cols; hi++) reg.add(key(K_HOIST, hi), at(k_hoist, hi * en), 0);
 }
 
 // every term of the quotient's numerator in protocol order (gates, permutation argument, lookups); *tinv = the 1 / (X^n - 1) column
@@ -211,7 +243,7 @@ static void compile_quotient(bzh_pk& pk) {
     pk.hoist_cols = 0;
     if (pk.en % 128) return;   // VM v2 runs whole 128-row workgroups (tiny test domains take the plain fold)
     Cols reg;
-    quotient_registry(pk, QuotientPtrs{}, reg);
+    quotient_registry(pk, QuotientPtrs{}, false, reg);
     EPool ep;
     int tinv = -1;
     const std::vector<int> terms = quotient_terms<SF>(pk, reg, ep, &tinv);
@@ -248,33 +280,33 @@ static void compile_quotient(bzh_pk& pk) {
         }
         std::sort(picked.begin(), picked.end());
         if (!picked.empty() && picked.size() <= 512) {
-            const size_t ncols = reg.ptr.size();
+            pk.hoist_cols = picked.size();
+            quotient_registry(pk, QuotientPtrs{}, false, reg);   // ... and the hoisted columns
             for (size_t hi = 0; hi < picked.size(); hi++) {
                 Compiler c1(ep);
                 c1.prog.result_slot = c1.emit(picked[hi]);
                 if (c1.overflow) {
                     pk.hoist_progs.clear();
+                    pk.hoist_cols = 0;
                     return;   // does not fit the evaluators' slot file: the prover folds through VM v1
                 }
                 pk.hoist_progs.push_back(std::move(c1.prog));
-                cc.hoisted[picked[hi]] = (int)(ncols + hi);
+                cc.hoisted[picked[hi]] = reg.at(key(K_HOIST, hi));
             }
         }
     }
     cc.quotient(terms, tinv);
     cc.prog.nlds = cc.nlds();
     if (getenv("BZH_PROVE_TRACE")) {
-        size_t muls = 0;
-        for (auto& o : cc.prog.ops) muls += ((o.code >> 4) < 3 && ((o.code >> 2) & 3) == V2_MUL);
+        const size_t muls = program2_muls(cc.prog);
         fprintf(stderr, "[bzh_pk_create] quotient program (VM v2): %zu terms, %zu ops, %zu multiplications, %d LDS slots, %zu constants, %zu hoisted columns%s\n",
                 terms.size(), cc.prog.ops.size(), muls, cc.prog.nlds, cc.prog.consts.size(), pk.hoist_progs.size(), cc.prog.ok ? "" : " -- NOT usable");
         // instruction mix: form (SS/SL/LL/UN) x operation, and the kinds of the memory operands
         size_t hist[4][4] = {{0}}, kinds[4] = {0};
         for (auto& o : cc.prog.ops) {
-            const int form = o.code >> 4, oo = (o.code >> 2) & 3;
-            hist[form & 3][oo]++;
-            if (form == V2_SL || form == V2_LL) kinds[o.b_kind & 3]++;
-            if (form == V2_LL || (form == V2_UN && oo != V2_NEG)) kinds[o.a_kind & 3]++;
+            hist[o.form()][o.op()]++;
+            if (o.reads_b()) kinds[o.b_kind & 3]++;
+            if (o.reads_a() || o.is_store()) kinds[o.a_kind & 3]++;   // (the slot a STORE writes counts as an operand here)
         }
         fprintf(stderr, "[bzh_pk_create]   mix  SS add/sub/mul/rsub %zu/%zu/%zu/%zu  SL %zu/%zu/%zu/%zu  LL %zu/%zu/%zu/%zu  UN neg/load/store %zu/%zu/%zu ; operands column/const/lds %zu/%zu/%zu\n",
                 hist[0][0], hist[0][1], hist[0][2], hist[0][3], hist[1][0], hist[1][1], hist[1][2], hist[1][3], hist[2][0], hist[2][1],
@@ -295,11 +327,11 @@ template <class SF>
 static int materialize_hoist(bzh_ctx* ctx, bzh_pk& pk) {
     if (!pk.q_ok || pk.hoist_progs.empty()) return BZH_OK;
     const size_t size = pk.en;
-    Cols reg;
-    quotient_registry(pk, QuotientPtrs{}, reg);   // hoisted programs read key-owned columns only
-    const size_t ncols = reg.ptr.size();
     BZH_HIP_TRY(ctx, hipMalloc((void**)&pk.hoist, pk.hoist_cols * size * 32));
     pk.hoist_bytes = pk.hoist_cols * size * 32;
+    Cols reg;
+    quotient_registry(pk, QuotientPtrs{}, false, reg);   // hoisted programs read key-owned columns only
+    const size_t ncols = reg.ptr.size();
     size_t stage_bytes = 0;
     for (const Program& pg : pk.hoist_progs)
         stage_bytes = std::max(stage_bytes, std::max<size_t>(pg.consts.size(), 1) * 32 + pg.ops.size() * sizeof(bzh_expr_op) + ncols * 16 + 1024);
@@ -566,19 +598,17 @@ static int pk_create_t(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* blob, 
     }
     if constexpr (fe29_supported<SF>()) {
         if (pk.q_builtin29 && !getenv("BZH_QUOTIENT_SATURATED")) {
-            const size_t cols29 = (size_t)pk.nf + m + 5 + pk.hoist_cols;
-            BZH_HIP_TRY(ctx, hipMalloc((void**)&pk.key29, cols29 * 9 * en * 4));
-            pk.key29_bytes = cols29 * 9 * en * 4;
+            const Key29Layout k29(pk);
+            BZH_HIP_TRY(ctx, hipMalloc((void**)&pk.key29, k29.end * 9 * en * 4));
+            pk.key29_bytes = k29.end * 9 * en * 4;
             const dim3 blk(256);
-            uint32_t* d = pk.key29;
-            auto conv = [&](const uint32_t* src, size_t ncols) {
-                if (ncols) hipLaunchKernelGGL((k_sat_to_fe29_planes<SF>), dim3((unsigned)((en + 255) / 256), (unsigned)ncols), blk, 0, st, src, d, en);
-                d += ncols * 9 * en;
+            auto conv = [&](const uint32_t* src, size_t first, size_t ncols) {
+                if (ncols) hipLaunchKernelGGL((k_sat_to_fe29_planes<SF>), dim3((unsigned)((en + 255) / 256), (unsigned)ncols), blk, 0, st, src, pk.key29 + first * 9 * en, en);
             };
-            conv(pk.fixed_cosets, (size_t)pk.nf);
-            conv(pk.sigma_cosets, m);
-            conv(pk.l0, 5);       // l0, l_last, l_blind, x_col, tinv_col are consecutive columns of the key's allocation
-            conv(pk.hoist, pk.hoist_cols);
+            conv(pk.fixed_cosets, k29.fixed, (size_t)pk.nf);
+            conv(pk.sigma_cosets, k29.sigma, m);
+            conv(pk.l0, k29.misc, 5);       // l0, l_last, l_blind, x_col, tinv_col are consecutive columns of the key's allocation
+            conv(pk.hoist, k29.hoist, pk.hoist_cols);
             BZH_HIP_TRY(ctx, hipGetLastError());
         } else {
             pk.q_builtin29 = nullptr;

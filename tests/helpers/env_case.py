@@ -1,7 +1,8 @@
 """One process = one setting of the library's tuning / fallback environment variables (they are read once per process).
 Prints a digest of (a) a window-table MSM and a paired-free plain MSM on fixed inputs, (b) the proofs of two fixed
 ShotCircuit witnesses under fixed seeds.  tests/test_gpu_env_paths.py compares the digests across settings: every path must
-produce the same group elements and the same proof bytes."""
+produce the same group elements and the same proof bytes.  BZH_TEST_QUOTIENT_MODULE=1 is a switch of this script, not of the
+library: the key then runs the quotient as a module compiled here from bzh_pk_quotient_source."""
 import hashlib
 import os
 import random
@@ -33,6 +34,11 @@ def main():
     # (b) two real ShotCircuit proofs, fixed witnesses and seeds
     lay = Cm.CircuitLayout(Cm.SHOT, k)
     pk = N.NativeProvingKey(ctx, lay.blob(), bzh2.CURVE_VESTA, params=prm)
+    if os.environ.get("BZH_TEST_QUOTIENT_MODULE"):   # (this script's own switch) the quotient program as a code object of the caller's
+        code = N.compile_quotient_source(pk.quotient_source())
+        assert code is not None, "hipcc did not compile the quotient module"
+        pk.set_quotient_module(code)
+        assert pk.quotient_selected()[0] == N.QUOTIENT_MODULE
     r = random.Random(77)
     deck = [(3, 3, True), (5, 4, False), (0, 1, False), (0, 5, True), (6, 1, False)]
     _, state = Cm.board_witness(deck, None)

@@ -1,6 +1,7 @@
 """The library's tuning knobs and fallback paths (environment variables read once per process) must not change a single
 bit: the quotient VM v1 fallback, no hoisted columns, other shared-subexpression slot counts, the interpreted quotient,
-the LDS-tile NTT kernel, and the opening's generator collapse off / forced at several rounds and tail windows.  Each setting
+the saturated builtin quotient kernel and the caller's quotient module (with the default, the unsaturated builtin kernel, that
+is every flavour of the quotient launch on one batch of two distinct ShotCircuit witnesses), the LDS-tile NTT kernel, and the opening's generator collapse off / forced at several rounds and tail windows.  Each setting
 runs tests/helpers/env_case.py in its own process; all digests
 (MSM results + the bytes of two real ShotCircuit proofs under fixed seeds) must equal the default's."""
 import os
@@ -25,6 +26,7 @@ SETTINGS = [
     {"BZH_NTT_LDS": "1"},
     {"BZH_ACC_SATURATED": "1"},                             # bucket accumulation in saturated 8 x 32 limbs (default: unsaturated 9 x 29, csrc/fe29.cuh)
     {"BZH_QUOTIENT_SATURATED": "1"},                        # the builtin quotient kernel in saturated limbs (default: its unsaturated-limb flavour)
+    {"BZH_TEST_QUOTIENT_MODULE": "1"},                      # (tests/helpers/env_case.py's switch) the quotient as a module compiled by the caller
     {"BZH_RED_WG_MAX": "0"},                                # latency-mode reductions: one wave per segment everywhere
     {"BZH_RED_WG_MAX": "4096"},                             # ... the workgroup flavour everywhere
     {"BZH_MSM_NO_QUAD": "1"},                               # bucket reductions without the four-lanes-per-addition latency mode
@@ -42,7 +44,7 @@ SETTINGS = [
 def _digest(extra):
     env = dict(os.environ)
     for k in ("BZH_QUOTIENT_V1", "BZH_NO_HOIST", "BZH_VM2_CSE", "BZH_QUOTIENT", "BZH_NTT_LDS",
-              "BZH_IPA_COLLAPSE", "BZH_IPA_TAIL_C", "BZH_NO_COMMIT_SHIFT", "BZH_MSM_NO_QUAD", "BZH_ACC_NO_XCD_MAP", "BZH_ACC_SATURATED", "BZH_QUOTIENT_SATURATED", "BZH_RED_WG_MAX", "BZH_VM2_GLOBAL"):
+              "BZH_IPA_COLLAPSE", "BZH_IPA_TAIL_C", "BZH_NO_COMMIT_SHIFT", "BZH_MSM_NO_QUAD", "BZH_ACC_NO_XCD_MAP", "BZH_ACC_SATURATED", "BZH_QUOTIENT_SATURATED", "BZH_RED_WG_MAX", "BZH_VM2_GLOBAL", "BZH_TEST_QUOTIENT_MODULE"):
         env.pop(k, None)
     env.update(extra)
     out = subprocess.run([sys.executable, CASE], env=env, capture_output=True, text=True, timeout=600)

@@ -1,4 +1,4 @@
-"""Column leaves in slots (csrc/quotient_program.hpp, Compiler2::select_leaves; BZH_VM2_LEAF) change no proof byte: the
+"""Column leaves in slots (csrc/quotient_compiler.hpp, Compiler2::select_leaves; BZH_VM2_LEAF) change no proof byte: the
 builtin kernel generated from the leaf-slot program, the interpreter running that same program, and the interpreter running
 the BZH_VM2_LEAF=0 program (every use of a column loads it, as before) give the same proofs of the reference's real circuits
 at their smallest tables -- ShotCircuit k = 11 (benches/shot.rs:22), BoardCircuit k = 12 (benches/board.rs:22) -- for the same

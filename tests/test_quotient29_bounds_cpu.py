@@ -1,4 +1,4 @@
-"""The unsaturated-limb quotient kernels (csrc/quotient_program.hpp, program2_source29) skip the carry pass after an addition
+"""The unsaturated-limb quotient kernels (csrc/quotient_emit.hpp, program2_source29) skip the carry pass after an addition
 or subtraction wherever the emitter's limb bounds say the consumer does not need it.  A wrong bound there would not show in
 any parity test -- the inputs that reach a worst case are astronomically rare -- so this test re-derives every bound
 INDEPENDENTLY from the emitted source text: it walks the straight-line code of the Board and Shot kernels statement by

@@ -1,4 +1,4 @@
-"""Column leaves in cross-group slots (csrc/quotient_program.hpp, Compiler2::select_leaves; BZH_VM2_LEAF).  The quotient
+"""Column leaves in cross-group slots (csrc/quotient_compiler.hpp, Compiler2::select_leaves; BZH_VM2_LEAF).  The quotient
 program re-loaded the same (column, rotation) leaf in nearly every gate group; hot leaves are now loaded once into a slot
 (V2_UN/V2_LOAD + V2_STORE when their residence begins) and read from it (slot operands) until it ends.  Host only: the
 programs come from bzh_quotient_program_for_circuit, and are evaluated here by a small integer evaluator that mirrors
@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 P_FP = 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001
-COLUMN, CONST, LDS = 1, 2, 3            # operand kinds (include/bzh2.h BZH_EXPR_COLUMN / BZH_EXPR_CONST; csrc/quotient_program.hpp BZH_EXPR_LDS)
+COLUMN, CONST, LDS = 1, 2, 3            # operand kinds (include/bzh2.h BZH_EXPR_COLUMN / BZH_EXPR_CONST; csrc/vm2_isa.hpp BZH_EXPR_LDS)
 SS, SL, LL, UN = 0, 1, 2, 3             # instruction forms
 ADD, SUB, MUL, RSUB = 0, 1, 2, 3
 NEG, LOAD, STORE = 0, 1, 2
