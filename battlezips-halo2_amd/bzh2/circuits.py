@@ -21,6 +21,7 @@ from . import FORM_CANONICAL, FORM_MONTGOMERY, MEM_DEVICE, MEM_HOST, BzhError, i
 from .game import BinaryValue
 
 SHOT, BOARD, NUM2BITS_TEST, BITS2NUM_TEST = 0, 1, 2, 3
+SYNTH_HOST, SYNTH_DEVICE = 0, 1
 _VP = ctypes.c_void_p
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 
@@ -37,6 +38,8 @@ def _bind():
     L.bzh_circuit_info.argtypes = [_VP] + [ctypes.POINTER(ctypes.c_uint32)] * 6
     L.bzh_synthesize_shot.argtypes = [_VP, _VP, ctypes.c_size_t, _VP, _VP, _VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_uint]
     L.bzh_synthesize_board.argtypes = [_VP, _VP, ctypes.c_size_t, _VP, _VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_uint]
+    L.bzh_synthesize_shot_with.argtypes = L.bzh_synthesize_shot.argtypes + [ctypes.c_int]
+    L.bzh_synthesize_board_with.argtypes = L.bzh_synthesize_board.argtypes + [ctypes.c_int]
     L.bzh_synthesize_bitify_test.argtypes = [_VP, _VP, _VP, _VP]
     L.bzh_board_witness.argtypes = [_VP, _VP, _VP, _VP]
     L.bzh_shot_serialize.argtypes = [_VP, _VP, ctypes.c_size_t, _VP]
@@ -129,11 +132,16 @@ class CircuitLayout:
         _check(L.bzh_circuit_describe(self.handle, buf, n.value, ctypes.byref(n)), "bzh_circuit_describe")
         return json.loads(buf.value.decode())
 
-    def synthesize(self, circuits, ctx=None, device_ptr: int | None = None, form: int = FORM_CANONICAL, threads: int = 0):
+    def synthesize(self, circuits, ctx=None, device_ptr: int | None = None, form: int = FORM_CANONICAL, threads: int = 0, where: str = "host"):
         """Circuit::synthesize for every circuit of the list.  Returns (advice, instances): advice is a
         (batch, num_advice, n, 4) uint64 host array in `form`, or None when the tensor was written to `device_ptr`
-        (Montgomery, on ctx's stream); instances is a list of per-proof public-input columns [[...]] (ints)."""
+        (Montgomery, on ctx's stream); instances is a list of per-proof public-input columns [[...]] (ints).
+        where="device" computes the witness on ctx's device (bzh_synthesize_*_with, BZH_SYNTH_DEVICE): it needs ctx and
+        device_ptr."""
         L = _bind()
+        if where not in ("host", "device"):
+            raise ValueError("where is 'host' or 'device'")
+        wh = SYNTH_DEVICE if where == "device" else SYNTH_HOST
         B = len(circuits)
         inst = np.zeros((B, max(self.num_instance_rows, 1), 4), dtype=np.uint64)
         if device_ptr is not None:
@@ -147,14 +155,14 @@ class CircuitLayout:
             traps = _limbs([c.board_commitment_trapdoor for c in circuits])
             shots = _limbs([c.shot.value for c in circuits])
             hits = _limbs([c.hit.value for c in circuits])
-            rc = L.bzh_synthesize_shot(ctxh, self.handle, B, _VP(boards.ctypes.data), _VP(traps.ctypes.data), _VP(shots.ctypes.data),
-                                       _VP(hits.ctypes.data), adv_p, form, mem, _VP(inst.ctypes.data), threads)
+            rc = L.bzh_synthesize_shot_with(ctxh, self.handle, B, _VP(boards.ctypes.data), _VP(traps.ctypes.data), _VP(shots.ctypes.data),
+                                            _VP(hits.ctypes.data), adv_p, form, mem, _VP(inst.ctypes.data), threads, wh)
         elif self.kind == BOARD:
             ships = _limbs([s.value for c in circuits for s in c.ship_commitments])
             boards = _limbs([c.board.value for c in circuits])
             traps = _limbs([c.board_commitment_trapdoor for c in circuits])
-            rc = L.bzh_synthesize_board(ctxh, self.handle, B, _VP(ships.ctypes.data), _VP(boards.ctypes.data), _VP(traps.ctypes.data),
-                                        adv_p, form, mem, _VP(inst.ctypes.data), threads)
+            rc = L.bzh_synthesize_board_with(ctxh, self.handle, B, _VP(ships.ctypes.data), _VP(boards.ctypes.data), _VP(traps.ctypes.data),
+                                             adv_p, form, mem, _VP(inst.ctypes.data), threads, wh)
         else:
             raise ValueError("use synthesize_bitify_test")
         _check(rc, "bzh_synthesize")

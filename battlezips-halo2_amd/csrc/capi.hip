@@ -247,6 +247,7 @@ int bzh_ctx_destroy(bzh_ctx* ctx) {
         if (ctx->ws[i]) (void)hipFree(ctx->ws[i]);
     if (ctx->d_add_counter) (void)hipFree(ctx->d_add_counter);
     if (ctx->ped_tbl) (void)hipFree(ctx->ped_tbl);
+    if (ctx->syn_tbl) (void)hipFree(ctx->syn_tbl);
     for (uint32_t* t : ctx->sqrt_tbl)
         if (t) (void)hipFree(t);
     if (ctx->pin) (void)hipHostFree(ctx->pin);

@@ -20,6 +20,7 @@
 #include "pedersen_generators.hpp"
 #include "circuit/chips.hpp"
 #include "ctx.hpp"
+#include "synthesize_device.hpp"
 
 using namespace bzc;
 
@@ -463,9 +464,107 @@ static int synthesize_compact(const bzh_circuit& c, size_t batch, const BatchInp
     return status.load();
 }
 
+// ---- BZH_SYNTH_DEVICE: what the kernels of csrc/synthesize_device.hip need from the circuit object ------------------------------
+// The regions in the order the two `synthesize` functions of chips.hpp assign them; the rows come from region_starts.
+static int synth_layout_of(const bzh_circuit& c, bzh::SynLayout* out) {
+    using namespace bzh;
+    SynLayout L;
+    memset(&L, 0, sizeof(L));
+    const bool shot = c.kind == BZH_CIRCUIT_SHOT;
+    if (!shot && c.kind != BZH_CIRCUIT_BOARD) return BZH_E_ARG;
+    const std::vector<size_t>& rs = c.region_starts;
+    if (rs.size() != (shot ? 12u : 35u) || (size_t)c.cs.num_advice < 11) return BZH_E_ARG;
+    L.kind = (uint32_t)c.kind;
+    L.n = (uint32_t)c.keygen.n;
+    L.rows_used = (uint32_t)c.rows_used;
+    L.num_advice = (uint32_t)c.cs.num_advice;
+    L.in_words = shot ? 16 : 48;
+    for (int i = 0; i < 10; i++) L.col[i] = (uint32_t)(shot ? c.shot.advice[i] : c.board.advice[i]).index;
+    L.col[10] = (uint32_t)(shot ? c.shot.input : c.board.advice[10]).index;
+    L.src_board = shot ? 0 : 10;
+    L.src_trapdoor = shot ? 1 : 11;
+    static const int ship_len[5] = {5, 4, 3, 3, 2};
+    for (int i = 0; i < 5; i++) {
+        L.place_len[i] = (uint32_t)ship_len[i];
+        for (int j = 0; j < BOARD_SIZE; j++) {
+            if (!(j % 10 + ship_len[i] > 10)) L.place_mask[i][j / 64] |= (uint64_t)1 << (j % 64);
+        }
+    }
+    uint32_t r = 0;
+    auto add = [&](uint32_t type, uint32_t rows, uint32_t arg) { L.reg[r] = SynRegion{type, (uint32_t)rs[r], rows, arg}, r++; };
+    const uint32_t B = BOARD_SIZE;
+    if (shot) {
+        L.load = (uint32_t)rs[0];
+        add(SYN_R_SHOT_LOAD, 5, 0);
+        add(SYN_R_BITIFY, B + 1, 0 | 5 << 8);      // board
+        add(SYN_R_BITIFY, B + 1, 2 | 5 << 8);      // shot
+        add(SYN_R_SHOT_SUM, B + 1, 0);
+        add(SYN_R_SHOT_OUT, 1, 0);
+    } else {
+        L.load = (uint32_t)rs[0];
+        add(SYN_R_BOARD_LOAD, 1, 0);
+        for (uint32_t i = 0; i < 10; i++) add(SYN_R_BITIFY, B + 1, i | 0 << 8);
+        for (uint32_t i = 0; i < 5; i++) {
+            add(SYN_R_PLACE_A, B, i);
+            add(SYN_R_PLACE_B, B + 1, i);
+            add(SYN_R_PLACE_C, 1, i);
+        }
+        add(SYN_R_TRANSPOSE, B, 0);
+        add(SYN_R_BITIFY, B + 1, 10 | 0 << 8);     // bits2num of the board bits
+    }
+    // pedersen_synthesize's seven regions
+    L.inc[0] = (uint32_t)rs[r];
+    add(SYN_R_BF_Z, ECC_NUM_WINDOWS + 1, 0);
+    L.add[0] = (uint32_t)rs[r];
+    add(SYN_R_SKIP, 2, 0);
+    add(SYN_R_WITNESS, 14, 0);
+    add(SYN_R_CANON, 3, 0);
+    L.inc[1] = (uint32_t)rs[r];
+    add(SYN_R_FW_WIN, ECC_NUM_WINDOWS, 0);
+    L.add[1] = (uint32_t)rs[r];
+    add(SYN_R_SKIP, 2, 0);
+    L.final_add = (uint32_t)rs[r];
+    add(SYN_R_SKIP, 2, 0);
+    L.nregions = r;
+    if (r != rs.size()) return BZH_E_ARG;
+    for (uint32_t i = 0; i < r; i++) {
+        if ((size_t)L.reg[i].start + L.reg[i].rows > c.rows_used || c.rows_used > c.keygen.n) return BZH_E_ARG;   // every write stays inside the tensor
+    }
+    for (int i = 0; i < 11; i++) {
+        if (L.col[i] >= L.num_advice) return BZH_E_ARG;
+    }
+    *out = L;
+    return BZH_OK;
+}
+// points[w][k] and u[w][k] of V then R as the kernels gather them: x, y, u in Montgomery form
+static const std::vector<uint32_t>& synth_table() {
+    static std::once_flag once;
+    static std::vector<uint32_t> tbl;
+    std::call_once(once, [] {
+        const BoardFixedBases& fb = fixed_bases();
+        tbl.resize(bzh::SYN_TBL_ENTRIES * bzh::SYN_TBL_WORDS);
+        uint32_t* o = tbl.data();
+        for (const FixedBase* b : {&fb.v, &fb.r}) {
+            for (int w = 0; w < ECC_NUM_WINDOWS; w++) {
+                for (int k = 0; k < ECC_H; k++, o += bzh::SYN_TBL_WORDS) {
+                    memcpy(o, b->points[w][k].x.l, 32);
+                    memcpy(o + 8, b->points[w][k].y.l, 32);
+                    memcpy(o + 16, b->u[w][k].fe.l, 32);
+                }
+            }
+        }
+    });
+    return tbl;
+}
+
 static thread_local std::string g_circuit_error;
 
 }  // namespace
+
+namespace bzh {
+int synth_layout(const bzh_circuit* c, SynLayout* out) { return (c && out) ? synth_layout_of(*c, out) : BZH_E_ARG; }
+const uint32_t* synth_table_host() { return synth_table().data(); }
+}  // namespace bzh
 
 extern "C" {
 
@@ -548,11 +647,71 @@ int bzh_circuit_vk_repr(const bzh_circuit* c, uint8_t* out_repr, int* is_placeho
     return BZH_OK;
 }
 
+// BZH_SYNTH_DEVICE: the inputs are checked and staged here, the witness is computed by csrc/synthesize_device.hip's kernels
+static int synthesize_device(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const BatchInputs& bi, uint64_t* advice, uint64_t* instances) {
+    bzh::SynLayout L;
+    BZH_TRY(bzh::synth_layout(c, &L));
+    const bool shot = c->kind == BZH_CIRCUIT_SHOT;
+    std::vector<uint64_t> in(batch * L.in_words);
+    try {
+        // the host path's refusals that depend on the inputs alone, before anything is launched, with its error texts
+        for (size_t i = 0; i < batch; i++) {
+            AnyInput a;
+            input_at(*c, bi, i, a);
+            uint64_t* o = in.data() + i * L.in_words;
+            if (shot) {
+                memcpy(o, bi.a + 4 * i, 32), memcpy(o + 4, bi.b + 4 * i, 32), memcpy(o + 8, bi.c + 4 * i, 32), memcpy(o + 12, bi.d + 4 * i, 32);
+            } else {
+                for (int j = 0; j < 5; j++) (void)a.board.ship_commitments[2 * j].zip(a.board.ship_commitments[2 * j + 1]);
+                memcpy(o, bi.a + 40 * i, 320), memcpy(o + 40, bi.b + 4 * i, 32), memcpy(o + 44, bi.c + 4 * i, 32);
+            }
+        }
+    } catch (const std::exception& e) {
+        g_circuit_error = e.what();
+        ctx->last_error = e.what();
+        return BZH_E_RANGE;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> status(batch);
+    std::vector<uint64_t> cm(instances ? batch * 8 : 0);
+    bzh::SynRun run;
+    run.layout = &L, run.batch = batch, run.inputs = in.data(), run.table = bzh::synth_table_host(), run.d_advice = (uint32_t*)advice;
+    run.commitments = instances ? cm.data() : nullptr, run.status = status.data();
+    BZH_TRY(bzh::synth_device_run(ctx, run));
+    for (size_t i = 0; i < batch; i++) {
+        if (!status[i]) continue;
+        const char* what = (status[i] & bzh::SYN_ST_MESSAGE)       ? "pedersen_commit: message repr is not a canonical scalar"
+                           : (status[i] & bzh::SYN_ST_WINDOW_X0)   ? "fixed-base mul: window point with x = 0"
+                                                                   : "incomplete addition: exceptional case";
+        g_circuit_error = what;
+        ctx->last_error = what;
+        return BZH_E_RANGE;
+    }
+    if (instances) {
+        const size_t ni = (size_t)c->num_instance_rows;
+        for (size_t i = 0; i < batch; i++) {
+            uint64_t* o = instances + i * ni * 4;
+            memcpy(o, cm.data() + i * 8, 64);
+            if (shot) {
+                const uint64_t pub[2][4] = {{bi.c[4 * i], bi.c[4 * i + 1], 0, 0}, {bi.d[4 * i], bi.d[4 * i + 1], 0, 0}};   // from_u128(lower_u128())
+                memcpy(o + 8, pub, 64);
+            }
+        }
+    }
+    return BZH_OK;
+}
+
 static int synthesize_any(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const BatchInputs& bi, uint64_t* advice, int form, int mem,
-                          uint64_t* instances, unsigned threads) {
+                          uint64_t* instances, unsigned threads, int where = BZH_SYNTH_HOST) {
     if (!c || !batch || batch > 65536 || !advice) return BZH_E_ARG;
     if ((form != BZH_FORM_CANONICAL && form != BZH_FORM_MONTGOMERY) || (mem != BZH_MEM_HOST && mem != BZH_MEM_DEVICE)) return BZH_E_ARG;
     if (mem == BZH_MEM_DEVICE && (!ctx || form != BZH_FORM_MONTGOMERY)) return BZH_E_ARG;
+    if (where != BZH_SYNTH_HOST && where != BZH_SYNTH_DEVICE) return BZH_E_ARG;
+    if (where == BZH_SYNTH_DEVICE) {
+        if (!ctx || mem != BZH_MEM_DEVICE || form != BZH_FORM_MONTGOMERY) return BZH_E_ARG;
+        return synthesize_device(ctx, c, batch, bi, advice, instances);
+    }
     const size_t na = (size_t)c->cs.num_advice, n = c->keygen.n, stride = std::max<size_t>(c->rows_used, 1);
     std::string err;
     if (mem == BZH_MEM_HOST) {
@@ -607,6 +766,20 @@ int bzh_synthesize_board(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const
     BatchInputs bi;
     bi.a = ship_commitments, bi.b = boards, bi.c = trapdoors;
     return synthesize_any(ctx, c, batch, bi, advice, form, mem, instances, threads);
+}
+int bzh_synthesize_shot_with(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const uint64_t* boards, const uint64_t* trapdoors, const uint64_t* shots,
+                             const uint64_t* hits, uint64_t* advice, int form, int mem, uint64_t* instances, unsigned threads, int where) {
+    if (!c || c->kind != BZH_CIRCUIT_SHOT || !boards || !trapdoors || !shots || !hits) return BZH_E_ARG;
+    BatchInputs bi;
+    bi.a = boards, bi.b = trapdoors, bi.c = shots, bi.d = hits;
+    return synthesize_any(ctx, c, batch, bi, advice, form, mem, instances, threads, where);
+}
+int bzh_synthesize_board_with(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const uint64_t* ship_commitments, const uint64_t* boards,
+                              const uint64_t* trapdoors, uint64_t* advice, int form, int mem, uint64_t* instances, unsigned threads, int where) {
+    if (!c || c->kind != BZH_CIRCUIT_BOARD || !ship_commitments || !boards || !trapdoors) return BZH_E_ARG;
+    BatchInputs bi;
+    bi.a = ship_commitments, bi.b = boards, bi.c = trapdoors;
+    return synthesize_any(ctx, c, batch, bi, advice, form, mem, instances, threads, where);
 }
 int bzh_synthesize_bitify_test(const bzh_circuit* c, const uint64_t* value, const uint64_t* binary, uint64_t* advice) {
     if (!c || (c->kind != BZH_CIRCUIT_NUM2BITS_TEST && c->kind != BZH_CIRCUIT_BITS2NUM_TEST) || !value || !binary) return BZH_E_ARG;

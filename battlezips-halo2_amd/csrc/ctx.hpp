@@ -66,6 +66,7 @@ struct bzh_ctx {
     };
     std::vector<PendingD2H> pending_d2h;
     uint32_t* ped_tbl = nullptr;   // bzh_pedersen_commit_batch's direct-lookup table of V and R (csrc/pedersen.hip), built on first use
+    uint32_t* syn_tbl = nullptr;   // device synthesis' copy of the circuits' fixed-base window tables (csrc/synthesize_device.hip), on first use
     uint32_t* sqrt_tbl[4] = {nullptr, nullptr, nullptr, nullptr};   // per field: g^(2^i), i <= S, for the square root (csrc/sqrt_decompress.hip), on first use
 };
 

@@ -599,6 +599,17 @@ int bzh_synthesize_shot(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const 
                         const uint64_t* hits, uint64_t* advice, int form, int mem, uint64_t* instances, unsigned threads);
 int bzh_synthesize_board(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const uint64_t* ship_commitments, const uint64_t* boards,
                          const uint64_t* trapdoors, uint64_t* advice, int form, int mem, uint64_t* instances, unsigned threads);
+/* The same two calls with the place of the arithmetic chosen (`where`).  BZH_SYNTH_HOST is bzh_synthesize_shot / _board exactly.
+ * BZH_SYNTH_DEVICE computes the witness on the ctx's device, straight into the advice tensor: it needs a ctx, BZH_MEM_DEVICE and
+ * BZH_FORM_MONTGOMERY (BZH_E_ARG otherwise); the inputs stay host pointers and `instances` host memory (or NULL).  Same tensor,
+ * same instances, same statuses: an input the host path refuses gives BZH_E_RANGE and bzh_circuit_last_error's text.  The call
+ * returns after one read-back (status words and commitments), its only stream synchronisation; `threads` is ignored. */
+#define BZH_SYNTH_HOST 0
+#define BZH_SYNTH_DEVICE 1
+int bzh_synthesize_shot_with(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const uint64_t* boards, const uint64_t* trapdoors, const uint64_t* shots,
+                             const uint64_t* hits, uint64_t* advice, int form, int mem, uint64_t* instances, unsigned threads, int where);
+int bzh_synthesize_board_with(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const uint64_t* ship_commitments, const uint64_t* boards,
+                              const uint64_t* trapdoors, uint64_t* advice, int form, int mem, uint64_t* instances, unsigned threads, int where);
 int bzh_synthesize_bitify_test(const bzh_circuit* c, const uint64_t* value, const uint64_t* binary, uint64_t* advice);
 int bzh_board_witness(const int8_t* ships, const int32_t* options, uint64_t* ship_commitments, uint64_t* state);
 int bzh_shot_serialize(const uint8_t* xs, const uint8_t* ys, size_t count, uint64_t* out);
