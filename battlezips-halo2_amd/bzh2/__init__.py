@@ -729,6 +729,46 @@ class TranscriptBatch:
         """overwrite the state and proof bytes of `batch` Transcript objects (bzh_transcript_batch_to_host)"""
         self._check(_bind_transcript_batch().bzh_transcript_batch_to_host(self.h, self._handles(transcripts)), "bzh_transcript_batch_to_host")
 
+    def ipa_open(self, bases: "Bases", polys, blinds, x3s, rng, *, form: int = FORM_CANONICAL, mem: int = MEM_HOST, out_v=None,
+                 status=None, rng_stride: int | None = None, batch: int | None = None):
+        """`batch` openings against this device-resident batch (bzh_ipa_open_batch_device): S, (L_j, R_j)*, c, f go into the
+        transcripts, byte for byte what Context.ipa_open_batch writes into host transcripts.
+        MEM_HOST: polys (batch, n, 4) uint64 in `form`; blinds, x3s: (batch, 4) uint64 in `form`, or lists of ints; rng: one byte
+        string of 64 * (n + 1 + 2k) draws per proof.  Returns (v, status): (batch, 4) uint64 in `form` and (batch,) uint8 -- nonzero
+        where a round challenge was zero.
+        MEM_DEVICE: every operand is a device pointer (int, 16-byte aligned; `status` any alignment, or None), the draws of proof b
+        at rng + b * rng_stride; out_v is required.  Enqueues only, returns None.
+        The number of openings is the number of rng strings (MEM_HOST) or `batch` (MEM_DEVICE, default: this batch's size); the
+        library refuses one that is not this batch's size."""
+        L = load()
+        vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+        L.bzh_ipa_open_batch_device.argtypes = [vp, vp, vp, ci, ci, sz, vp, vp, vp, sz, vp, vp, vp]
+        ctxh = self.ctx.handle if self.ctx is not None else None
+        bh = bases.handle if bases is not None else None
+        where = "bzh_ipa_open_batch_device"
+        if mem == MEM_DEVICE:
+            ptr = lambda v: ctypes.c_void_p(int(v)) if v else None  # noqa: E731
+            self._check(L.bzh_ipa_open_batch_device(ctxh, bh, ptr(polys), form, mem, self.batch if batch is None else batch, ptr(blinds),
+                                                    ptr(x3s), ptr(rng), rng_stride or 0, self.h, ptr(out_v), ptr(status)), where)
+            return None
+        B = len(rng)
+
+        def limbs(v):
+            if isinstance(v, np.ndarray):
+                return np.ascontiguousarray(v, dtype=np.uint64).reshape(B, 4)
+            return np.ascontiguousarray(np.stack([int_to_limbs(x) for x in v]))
+
+        p = np.ascontiguousarray(np.asarray(polys, dtype=np.uint64).reshape(B, -1, 4))
+        bl, xs = limbs(blinds), limbs(x3s)
+        stride = len(rng[0])
+        assert all(len(r) == stride for r in rng)
+        raw = np.frombuffer(b"".join(rng), dtype=np.uint8)
+        v = np.zeros((B, 4), dtype=np.uint64)
+        st = np.zeros(B, dtype=np.uint8)
+        self._check(L.bzh_ipa_open_batch_device(ctxh, bh, _vp(p), form, mem, B, _vp(bl), _vp(xs), _vp(raw), stride, self.h, _vp(v), _vp(st)),
+                    where)
+        return v, st
+
     def close(self):
         if self.h is not None:
             load().bzh_transcript_batch_free(self.h)
@@ -742,7 +782,7 @@ class TranscriptBatch:
 
 
 # ---- IPA opening --------------------------------------------------------------------------------
-EXPORTS += ["bzh_ipa_open", "bzh_ipa_open_batch", "bzh_ipa_verify"]
+EXPORTS += ["bzh_ipa_open", "bzh_ipa_open_batch", "bzh_ipa_open_batch_device", "bzh_ipa_verify"]
 EXPORTS += ["bzh_pk_create", "bzh_pk_free", "bzh_pk_set_lagrange", "bzh_pk_quotient_stats", "bzh_pk_quotient_source", "bzh_pk_set_quotient_module", "bzh_pk_info", "bzh_prove_batch", "bzh_prove_batch_seeded", "bzh_rng_expand", "bzh_verify_batch",
             "bzh_vk_digest", "bzh_pk_vk_repr"]
 EXPORTS += ["bzh_vk_create", "bzh_vk_from_pk", "bzh_vk_write", "bzh_vk_read", "bzh_vk_info", "bzh_vk_vk_repr", "bzh_vk_device_bytes",

@@ -809,6 +809,66 @@ int bzh_ipa_open_batch(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* pol
     return ipa_open(ctx, bases, d_polys, batch, blinds, x3s, rng, rng_stride, transcripts, out_v);
 }
 
+int bzh_ipa_open_batch_device(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* polys, int form, int mem, size_t batch,
+                              const uint64_t* blinds, const uint64_t* x3s, const uint8_t* rng, size_t rng_stride,
+                              bzh_transcript_batch* transcripts, uint64_t* out_v, uint8_t* status) {
+    if (!ctx || !bases || !polys || !blinds || !x3s || !rng || !transcripts || !out_v || !valid_form(form) || !valid_mem(mem))
+        return BZH_E_ARG;
+    if (bases->n < 3 || bases->device != ctx->device || !batch || batch > 65535) return BZH_E_ARG;
+    const size_t n = bases->n - 2;
+    if (n & (n - 1)) return BZH_E_ARG;
+    unsigned k = 0;
+    while (((size_t)1 << k) < n) k++;
+    const size_t nrand = n + 1 + 2 * (size_t)k;
+    if (rng_stride < 64 * nrand) return BZH_E_ARG;
+    const TbInfo ti = tb_info(transcripts);
+    if (ti.ctx != ctx || ti.curve != bases->curve || ti.batch != batch) return BZH_E_ARG;   // (a host-resident batch has no ctx)
+    if (mem == BZH_MEM_DEVICE &&
+        (((uintptr_t)polys | (uintptr_t)blinds | (uintptr_t)x3s | (uintptr_t)rng | (uintptr_t)out_v) & 15))
+        return BZH_E_ARG;
+    if (ti.proof_len + 32 * (1 + 2 * (size_t)k) + 64 > ti.proof_cap) return BZH_E_RANGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int field = 0;
+    BZH_TRY(with_curve(bases->curve, [&](auto c) {
+        field = CurveInfo<decltype(c)>::scalar_field;
+        return BZH_OK;
+    }));
+    const bool host = mem == BZH_MEM_HOST, canonical = form == BZH_FORM_CANONICAL;
+    const size_t st_bytes = (batch + 15) & ~(size_t)15;
+    // workspace slot 3 (the opening itself works in slots 0-2, 4 and 5): host operands are staged up here once, and canonical
+    // coefficients get their Montgomery copy here
+    Stager s{ctx, field, form};
+    BZH_TRY(s.begin(((host || canonical) ? batch * n * 32 + 64 : 0) + (host ? batch * (96 + nrand * 64) + st_bytes + 5 * 64 : 0)));
+    const uint32_t* d_polys = (const uint32_t*)polys;
+    if (host) {
+        uint32_t* d = nullptr;
+        BZH_TRY(s.in(polys, batch * n, &d));
+        d_polys = d;
+    } else if (canonical) {
+        uint32_t* d = s.carve(batch * n * 32);
+        BZH_HIP_TRY(ctx, hipMemcpyAsync(d, polys, batch * n * 32, hipMemcpyDeviceToDevice, ctx->stream));
+        BZH_TRY(field_convert(ctx, field, d, batch * n, 1));
+        d_polys = d;
+    }
+    if (!host)
+        return ipa_open_device(ctx, bases, d_polys, batch, (const uint32_t*)blinds, (const uint32_t*)x3s, form, rng, rng_stride, transcripts,
+                               (uint32_t*)out_v, status);
+    uint32_t *d_blinds = s.carve(batch * 32), *d_x3s = s.carve(batch * 32), *d_v = s.carve(batch * 32);
+    uint8_t* d_rng = (uint8_t*)s.carve(batch * nrand * 64);
+    uint8_t* d_st = (uint8_t*)s.carve(st_bytes);
+    BZH_TRY(h2d_small(ctx, d_blinds, blinds, batch * 32));
+    BZH_TRY(h2d_small(ctx, d_x3s, x3s, batch * 32));
+    for (size_t b = 0; b < batch; b++) BZH_TRY(h2d_small(ctx, d_rng + b * nrand * 64, rng + b * rng_stride, nrand * 64));
+    BZH_TRY(ipa_open_device(ctx, bases, d_polys, batch, d_blinds, d_x3s, form, d_rng, nrand * 64, transcripts, d_v, d_st));
+    std::vector<uint8_t> st(st_bytes);
+    BZH_TRY(d2h_async(ctx, out_v, d_v, batch * 32));
+    BZH_TRY(d2h_async(ctx, st.data(), d_st, st_bytes));
+    BZH_TRY(d2h_finish(ctx));
+    if (status) memcpy(status, st.data(), batch);
+    return BZH_OK;
+}
+
 int bzh_ipa_open(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* poly, int form, int mem, const uint64_t* blind,
                  const uint64_t* x3, const uint8_t* rng, size_t rng_len, bzh_transcript* transcript, uint64_t* out_v) {
     return bzh_ipa_open_batch(ctx, bases, poly, form, mem, 1, blind, x3, rng, rng_len, &transcript, out_v);

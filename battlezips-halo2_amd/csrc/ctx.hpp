@@ -327,6 +327,12 @@ int random_field(bzh_ctx* ctx, int field, const uint32_t* d_raw, size_t count, u
 int ipa_open(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint64_t* blinds,
              const uint64_t* x3s, const uint8_t* rng_bytes, size_t rng_stride, bzh_transcript* const* trs, uint64_t* out_v,
              const uint32_t* d_raw_in = nullptr);  // d_raw_in: the draws already on the device (batch x (n + 1 + 2k) x 64 B) instead of rng_bytes
+// the same opening against a device-resident transcript batch of this ctx (the caller holds ctx->mu and has checked its curve, size
+// and proof room): every operand in device memory, 16-byte aligned; d_polys Montgomery, d_blinds / d_x3s / d_out_v in `form`, draws
+// of proof b at d_rng + b * rng_stride, d_status one byte per proof or null.  Enqueues only.
+int ipa_open_device(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint32_t* d_blinds,
+                    const uint32_t* d_x3s, int form, const uint8_t* d_rng, size_t rng_stride, bzh_transcript_batch* tb,
+                    uint32_t* d_out_v, uint8_t* d_status);
 int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                const uint8_t* proof, size_t proof_len, bzh_transcript* tr, const uint64_t* g0_u_w_xy);
 int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
@@ -349,14 +355,23 @@ int normalize_run(bzh_ctx* ctx, int curve, const void* d_xyz, size_t n, int form
 // between the two kernels and after k_map_to_curve.
 int h2c_generators_run(bzh_ctx* ctx, uint32_t first, size_t count, uint32_t* d_out_xy, uint8_t* d_status, hipEvent_t* ev = nullptr);
 // transcript_batch.hip: a device-resident bzh_transcript_batch for a caller that holds ctx->mu; device operands, enqueue only.
-// kind 0: common points (d_pre: a BZH_POINT_* byte per point at [b * stride + i], or null), kind 2: common scalars; item i of
-// transcript b lies at d_base + (b * stride + i) items -- stride 0 gives every transcript the same items.  tb_squeeze_locked writes
-// batch x 32 bytes.  tb_free_locked waits for the stream.
+// kind 0 / 1: common / write points (d_pre: a BZH_POINT_* byte per point at [b * stride + i], or null), kind 2 / 3: common / write
+// scalars; item i of transcript b lies at d_base + (b * stride + i) items -- stride 0 gives every transcript the same items.  A
+// write appends to the proofs without a capacity check: the caller has made it (tb_info).  tb_write_jacobian_locked is
+// bzh_transcript_batch_write_jacobian for device operands.  tb_squeeze_locked writes batch x 32 bytes.  tb_free_locked waits for
+// the stream.
+struct TbInfo {
+    bzh_ctx* ctx;   // null: host-resident
+    int curve;
+    size_t batch, proof_cap, proof_len;
+};
 int tb_new_locked(bzh_ctx* ctx, int curve, size_t batch, bzh_transcript_batch** out);
 void tb_free_locked(bzh_transcript_batch* tb);
 int tb_absorb_locked(bzh_transcript_batch* tb, int kind, const void* d_base, size_t count, size_t stride, int form, const uint8_t* d_pre);
+int tb_write_jacobian_locked(bzh_transcript_batch* tb, const void* d_xyz, size_t count, size_t stride, int form);
 int tb_squeeze_locked(bzh_transcript_batch* tb, int form, uint32_t* d_out);
 const uint8_t* tb_status_device(const bzh_transcript_batch* tb);
+TbInfo tb_info(const bzh_transcript_batch* tb);
 // verify_pass.hip: the kernels of the verifier's device pass (BZH_VERIFY_PASS_DEVICE); device pointers, enqueue only
 struct VerifyPassArgs {
     size_t batch = 0, pstride = 0;           // proofs: batch rows of pstride bytes (a multiple of 32)

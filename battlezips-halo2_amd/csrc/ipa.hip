@@ -27,6 +27,7 @@
 // (k = 14, j* = 4: 168 n against 336 n).  The group elements L_j, R_j are the same, hence the proof bytes.  Used when the
 // batch is large enough to be throughput-bound (the collapse is two long per-lane chains: it would lengthen a single
 // proof); BZH_IPA_COLLAPSE = 0 disables it, = j forces round j at any batch size; BZH_IPA_TAIL_C sets the tail window.
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -34,6 +35,7 @@
 #include "ctx.hpp"
 #include "curve.cuh"
 #include "host_field.hpp"
+#include "ipa_scalars.hpp"
 
 namespace bzh {
 
@@ -74,8 +76,8 @@ struct DevBuf {
 // MSM launch of 2*batch vectors, one device->host copy and one host<-device challenge upload.
 // Per-proof vectors are compact: p, b are (batch, m) and s is (batch, n/m) in round j (m = n >> j).
 // ---------------------------------------------------------------------------
-// host-written constants per proof (d_hc): [0] x3, [1] xi, [2] z, [3] u, [4] u_inv   (stride kHc)
-static constexpr size_t kHc = 8;
+// constants per proof (d_hc, csrc/ipa_scalars.hpp): [0] x3, [1] xi, [2] z, [3] u, [4] u_inv   (stride kHc); written by the host, or by
+// the scalar kernels of the device-transcript opening
 
 template <class P>
 __global__ void k_sub_at0_batch(uint32_t* __restrict__ v, size_t stride, const uint32_t* __restrict__ s, size_t batch) {
@@ -219,18 +221,288 @@ __global__ void __launch_bounds__(256) k_ipa_round_fold(const uint32_t* __restri
     }
 }
 
+// ---------------------------------------------------------------------------
+// The opening has one round loop (ipa_open_t) and two transcript drivers.  Everything that is on the device anyway -- the arena,
+// k_reduce_wide, the commit scalars, the axpy and the evaluation, the round vectors, the two MSM flavours, the fold, the collapse
+// at jstar -- is the loop's; a driver supplies what happens between those launches:
+//   draws   the 64-byte draws into d_raw           begin   x3 -> hc[0] (and what the driver keeps of the drawn scalars)
+//   head    S -> transcript, xi, z -> hc[1..2], f  keep_v  v = p'(x3) is in d_dv now
+//   round   (L_j, R_j) -> transcript, u_j, u_j^-1 -> hc[3..4], f += l_j u_j^-1 + r_j u_j
+//   ones    s <- (1) at the collapse               tail    c, f -> transcript, v -> the caller
+// IpaHostDriver is bzh_ipa_open(_batch) and the prover: host bzh_transcript objects, one read-back and one upload per step.
+// IpaDeviceDriver is bzh_ipa_open_batch_device: a device-resident bzh_transcript_batch, every step a launch.
+// ---------------------------------------------------------------------------
+struct IpaArena {
+    size_t B, n, nrand;
+    unsigned k;
+    uint32_t *d_raw, *d_rand, *d_hc, *d_dv, *d_extra;   // d_extra: Driver::kExtraWords words per proof
+    uint32_t* d_out;                                    // 2 B Jacobian points: S in [0, B), then (L_j, R_j) of proof b at [2b, 2b + 1]
+};
+
 template <class C>
-static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint64_t* blinds,
-                      const uint64_t* x3s, const uint8_t* rng_bytes, size_t rng_stride, bzh_transcript* const* trs,
-                      uint64_t* out_v, const uint32_t* d_raw_in) {
+struct IpaHostDriver {
     using SF = typename CurveInfo<C>::SF;
     using PB = typename C::Base;
+    static constexpr size_t kExtraWords = 0;
+    const uint64_t *blinds, *x3s;
+    const uint8_t* rng_bytes;
+    size_t rng_stride;
+    bzh_transcript* const* trs;
+    uint64_t* out_v;
+    const uint32_t* d_raw_in;
+    size_t ntail = 0;
+    std::vector<Fe<SF>> tail, hc, f, vm, us, us_inv;
+    std::vector<uint64_t> jac, xy;
+
+    int push_hc(bzh_ctx* ctx, const IpaArena& A) { return h2d_small(ctx, A.d_hc, hc.data(), A.B * kHc * 32); }
+    int draws(bzh_ctx* ctx, const IpaArena& A) {
+        if (d_raw_in) {  // the 64-byte draws are already on the device (batch x nrand, proof-major)
+            BZH_HIP_TRY(ctx, hipMemcpyAsync(A.d_raw, d_raw_in, A.B * A.nrand * 64, hipMemcpyDeviceToDevice, ctx->stream));
+        } else {
+            for (size_t b = 0; b < A.B; b++)
+                BZH_TRY(h2d_small(ctx, A.d_raw + b * A.nrand * 16, rng_bytes + b * rng_stride, A.nrand * 64));
+        }
+        return BZH_OK;
+    }
+    int begin(bzh_ctx* ctx, const IpaArena& A) {
+        const size_t B = A.B;
+        ntail = 1 + 2 * (size_t)A.k;
+        // the scalars the host needs (s_blind and the round blinds) come back in one strided copy
+        tail.resize(B * ntail);
+        for (size_t b = 0; b < B; b++) BZH_TRY(d2h_async(ctx, &tail[b * ntail], A.d_rand + (b * A.nrand + A.n) * 8, ntail * 32));
+        hc.assign(B * kHc, fe_zero<SF>());
+        for (size_t b = 0; b < B; b++) hc[b * kHc] = fe_to_mont(fe_from_u64<SF>(x3s + 4 * b));
+        jac.resize(2 * B * 12), xy.resize(2 * B * 8);
+        f.resize(B), vm.resize(B), us.resize(B);
+        return push_hc(ctx, A);
+    }
+    int head(bzh_ctx* ctx, const IpaArena& A) {
+        const size_t B = A.B;
+        BZH_TRY(d2h_async(ctx, jac.data(), A.d_out, B * 96));
+        BZH_TRY(d2h_finish(ctx));
+        h_jac_to_affine<PB>(jac.data(), B, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, xy.data());
+        uint64_t ch[4];
+        for (size_t b = 0; b < B; b++) {
+            BZH_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + b * 8));
+            BZH_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
+            const Fe<SF> xi = fe_to_mont(fe_from_u64<SF>(ch));
+            BZH_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
+            hc[b * kHc + 1] = xi;
+            hc[b * kHc + 2] = fe_to_mont(fe_from_u64<SF>(ch));
+            f[b] = fe_add(fe_mul(tail[b * ntail], xi), fe_to_mont(fe_from_u64<SF>(blinds + 4 * b)));
+        }
+        return push_hc(ctx, A);
+    }
+    int keep_v(bzh_ctx* ctx, const IpaArena& A) { return d2h_async(ctx, vm.data(), A.d_dv, A.B * 32); }  // lands at the next d2h_finish
+    int round(bzh_ctx* ctx, const IpaArena& A, unsigned j) {
+        const size_t B = A.B;
+        BZH_TRY(d2h_async(ctx, jac.data(), A.d_out, 2 * B * 96));
+        BZH_TRY(d2h_finish(ctx));
+        h_jac_to_affine<PB>(jac.data(), 2 * B, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, xy.data());
+        uint64_t ch[4];
+        for (size_t b = 0; b < B; b++) {
+            BZH_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + (2 * b) * 8));
+            BZH_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + (2 * b + 1) * 8));
+            BZH_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
+            us[b] = fe_to_mont(fe_from_u64<SF>(ch));
+        }
+        us_inv = us;
+        if (!h_batch_invert(us_inv.data(), B)) return BZH_E_ARG;  // a zero challenge has no inverse (probability 2^-255)
+        for (size_t b = 0; b < B; b++) {
+            hc[b * kHc + 3] = us[b];
+            hc[b * kHc + 4] = us_inv[b];
+            f[b] = fe_add(f[b], fe_add(fe_mul(tail[b * ntail + 1 + 2 * j], us_inv[b]), fe_mul(tail[b * ntail + 2 + 2 * j], us[b])));
+        }
+        return push_hc(ctx, A);
+    }
+    int ones(bzh_ctx* ctx, const IpaArena& A, uint32_t* s_cur) {
+        std::vector<Fe<SF>> one(A.B, fe_one<SF>());
+        return h2d_small(ctx, s_cur, one.data(), A.B * 32);
+    }
+    int tail_out(bzh_ctx* ctx, const IpaArena& A, const uint32_t* p_cur) {
+        const size_t B = A.B;
+        std::vector<Fe<SF>> c(B);
+        BZH_TRY(d2h_async(ctx, c.data(), p_cur, B * 32));
+        BZH_TRY(d2h_finish(ctx));
+        for (size_t b = 0; b < B; b++) {
+            fe_to_u64<SF>(out_v + 4 * b, fe_from_mont(vm[b]));
+            uint64_t sc[4];
+            fe_to_u64<SF>(sc, fe_from_mont(c[b]));
+            BZH_TRY(bzh_transcript_write_scalar(trs[b], sc));
+            fe_to_u64<SF>(sc, fe_from_mont(f[b]));
+            BZH_TRY(bzh_transcript_write_scalar(trs[b], sc));
+        }
+        return BZH_OK;
+    }
+    void msm_begin(bzh_ctx*) {}
+    void msm_end(bzh_ctx*) {}
+};
+
+// One lane per proof, 1-D grid over B in blocks of 64 (B = 65: a second, partial wave).  For B <= 64 each of these launches, like
+// the normalise and the transcript launches around them, is ONE wave: its time is the length of its dependent chain, not
+// throughput.  A round has two inversion chains of about 330 products each (fe_inv_ct), one after the other -- the normalise's (L_j and R_j
+// share it) and u_j's in k_ipa_round_scalars -- and nothing here tries to hide that.
+static constexpr unsigned kLaneBlock = 64;
+template <class P>
+__global__ void __launch_bounds__(kLaneBlock) k_ipa_x3(const uint32_t* __restrict__ x3s, int canonical, size_t batch,
+                                                       uint32_t* __restrict__ hc, uint8_t* __restrict__ status) {
+    const size_t b = blockIdx.x * (size_t)kLaneBlock + threadIdx.x;
+    if (b >= batch) return;
+    ipa_x3_lane<P>(b, x3s, canonical != 0, hc, status);
+}
+template <class P>
+__global__ void __launch_bounds__(kLaneBlock) k_ipa_head_scalars(const uint32_t* __restrict__ ch, const uint32_t* __restrict__ rands,
+                                                                 size_t nrand, size_t n, const uint32_t* __restrict__ blinds,
+                                                                 int canonical, size_t batch, uint32_t* __restrict__ hc,
+                                                                 uint32_t* __restrict__ f) {
+    const size_t b = blockIdx.x * (size_t)kLaneBlock + threadIdx.x;
+    if (b >= batch) return;
+    ipa_head_lane<P>(b, batch, ch, rands, nrand, n, blinds, canonical != 0, hc, f);
+}
+template <class P>
+__global__ void __launch_bounds__(kLaneBlock) k_ipa_round_scalars(const uint32_t* __restrict__ ch, const uint32_t* __restrict__ rands,
+                                                                  size_t nrand, size_t n, unsigned round, size_t batch,
+                                                                  uint32_t* __restrict__ hc, uint32_t* __restrict__ f,
+                                                                  uint8_t* __restrict__ status) {
+    const size_t b = blockIdx.x * (size_t)kLaneBlock + threadIdx.x;
+    if (b >= batch) return;
+    ipa_round_lane<P>(b, ch, rands, nrand, n, round, hc, f, status);
+}
+template <class P>
+__global__ void __launch_bounds__(kLaneBlock) k_ipa_tail_scalars(const uint32_t* __restrict__ p, const uint32_t* __restrict__ f,
+                                                                 const uint32_t* __restrict__ v, int canonical, size_t batch,
+                                                                 uint32_t* __restrict__ cf, uint32_t* __restrict__ out_v) {
+    const size_t b = blockIdx.x * (size_t)kLaneBlock + threadIdx.x;
+    if (b >= batch) return;
+    ipa_tail_lane<P>(b, p, f, v, canonical != 0, cf, out_v);
+}
+template <class P>
+__global__ void __launch_bounds__(kLaneBlock) k_ipa_fill_one(uint32_t* __restrict__ s, size_t batch) {
+    const size_t b = blockIdx.x * (size_t)kLaneBlock + threadIdx.x;
+    if (b >= batch) return;
+    fe_store(s + b * 8, fe_one<P>());
+}
+
+template <class C>
+struct IpaDeviceDriver {
+    using SF = typename CurveInfo<C>::SF;
+    static constexpr size_t kExtraWords = 2 * 8 + 8 + 2 * 8;   // per proof: two challenges | f | (c, f)
+    bzh_transcript_batch* tb;
+    const uint32_t *d_blinds, *d_x3s;
+    const uint8_t* d_rng;
+    size_t rng_stride;
+    uint32_t* d_out_v;
+    uint8_t* d_status;   // may be null
+    int form;
+    // BZH_PROVE_TRACE=1: the steps' times by events, on stderr (tools/ubench_ipa_open.py reads the line); one wait at the end
+    enum { kNormAbsorb = 0, kSqueeze, kScalars, kMsm, kClasses };
+    bool trace = false;
+    struct Mark {
+        int cls;
+        hipEvent_t a, b;
+    };
+    std::vector<Mark> marks;
+    hipEvent_t msm_a = nullptr;
+
+    dim3 lanes(const IpaArena& A) const { return dim3((unsigned)((A.B + kLaneBlock - 1) / kLaneBlock)); }
+    uint32_t* ch(const IpaArena& A) const { return A.d_extra; }
+    uint32_t* fv(const IpaArena& A) const { return A.d_extra + A.B * 16; }
+    uint32_t* cf(const IpaArena& A) const { return A.d_extra + A.B * 24; }
+    hipEvent_t mark_begin(bzh_ctx* ctx) {
+        hipEvent_t e = nullptr;
+        if (trace && hipEventCreate(&e) == hipSuccess) (void)hipEventRecord(e, ctx->stream);
+        return e;
+    }
+    void mark_end(bzh_ctx* ctx, int cls, hipEvent_t a) {
+        hipEvent_t e = nullptr;
+        if (!trace || !a || hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, ctx->stream);
+        marks.push_back({cls, a, e});
+    }
+    void msm_begin(bzh_ctx* ctx) { msm_a = mark_begin(ctx); }
+    void msm_end(bzh_ctx* ctx) { mark_end(ctx, kMsm, msm_a); }
+    int absorb_points(bzh_ctx* ctx, const IpaArena& A, size_t count) {
+        hipEvent_t a = mark_begin(ctx);
+        BZH_TRY(tb_write_jacobian_locked(tb, A.d_out, count, count, BZH_FORM_MONTGOMERY));
+        mark_end(ctx, kNormAbsorb, a);
+        return BZH_OK;
+    }
+    int squeeze(bzh_ctx* ctx, uint32_t* d_to) {
+        hipEvent_t a = mark_begin(ctx);
+        BZH_TRY(tb_squeeze_locked(tb, BZH_FORM_MONTGOMERY, d_to));
+        mark_end(ctx, kSqueeze, a);
+        return BZH_OK;
+    }
+
+    int draws(bzh_ctx* ctx, const IpaArena& A) {
+        trace = getenv("BZH_PROVE_TRACE") != nullptr;
+        BZH_HIP_TRY(ctx, hipMemcpy2DAsync(A.d_raw, A.nrand * 64, d_rng, rng_stride, A.nrand * 64, A.B, hipMemcpyDeviceToDevice, ctx->stream));
+        return BZH_OK;
+    }
+    int begin(bzh_ctx* ctx, const IpaArena& A) {
+        hipLaunchKernelGGL((k_ipa_x3<SF>), lanes(A), dim3(kLaneBlock), 0, ctx->stream, d_x3s, form == BZH_FORM_CANONICAL ? 1 : 0, A.B, A.d_hc,
+                           d_status);
+        BZH_HIP_TRY(ctx, hipGetLastError());
+        return BZH_OK;
+    }
+    int head(bzh_ctx* ctx, const IpaArena& A) {
+        BZH_TRY(absorb_points(ctx, A, 1));
+        BZH_TRY(squeeze(ctx, ch(A)));
+        BZH_TRY(squeeze(ctx, ch(A) + A.B * 8));
+        hipEvent_t a = mark_begin(ctx);
+        hipLaunchKernelGGL((k_ipa_head_scalars<SF>), lanes(A), dim3(kLaneBlock), 0, ctx->stream, ch(A), A.d_rand, A.nrand, A.n, d_blinds,
+                           form == BZH_FORM_CANONICAL ? 1 : 0, A.B, A.d_hc, fv(A));
+        mark_end(ctx, kScalars, a);
+        BZH_HIP_TRY(ctx, hipGetLastError());
+        return BZH_OK;
+    }
+    int keep_v(bzh_ctx*, const IpaArena&) { return BZH_OK; }   // d_dv is not written again: the tail reads it
+    int round(bzh_ctx* ctx, const IpaArena& A, unsigned j) {
+        BZH_TRY(absorb_points(ctx, A, 2));
+        BZH_TRY(squeeze(ctx, ch(A)));
+        hipEvent_t a = mark_begin(ctx);
+        hipLaunchKernelGGL((k_ipa_round_scalars<SF>), lanes(A), dim3(kLaneBlock), 0, ctx->stream, ch(A), A.d_rand, A.nrand, A.n, j, A.B, A.d_hc,
+                           fv(A), d_status);
+        mark_end(ctx, kScalars, a);
+        BZH_HIP_TRY(ctx, hipGetLastError());
+        return BZH_OK;
+    }
+    int ones(bzh_ctx* ctx, const IpaArena& A, uint32_t* s_cur) {
+        hipLaunchKernelGGL((k_ipa_fill_one<SF>), lanes(A), dim3(kLaneBlock), 0, ctx->stream, s_cur, A.B);
+        BZH_HIP_TRY(ctx, hipGetLastError());
+        return BZH_OK;
+    }
+    int tail_out(bzh_ctx* ctx, const IpaArena& A, const uint32_t* p_cur) {
+        hipLaunchKernelGGL((k_ipa_tail_scalars<SF>), lanes(A), dim3(kLaneBlock), 0, ctx->stream, p_cur, fv(A), A.d_dv,
+                           form == BZH_FORM_CANONICAL ? 1 : 0, A.B, cf(A), d_out_v);
+        BZH_HIP_TRY(ctx, hipGetLastError());
+        BZH_TRY(tb_absorb_locked(tb, 3, cf(A), 2, 2, BZH_FORM_MONTGOMERY, nullptr));
+        if (trace) {
+            double ms[kClasses] = {0, 0, 0, 0};
+            BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            for (auto& m : marks) {
+                float t = 0;
+                (void)hipEventElapsedTime(&t, m.a, m.b);
+                ms[m.cls] += t;
+                (void)hipEventDestroy(m.a), (void)hipEventDestroy(m.b);
+            }
+            marks.clear();
+            fprintf(stderr, "[bzh_ipa_open_batch_device] batch=%zu k=%u io:normalize_absorb_ms=%.4f io:squeeze_ms=%.4f io:round_scalars_ms=%.4f io:msm_ms=%.4f\n",
+                    A.B, A.k, ms[kNormAbsorb], ms[kSqueeze], ms[kScalars], ms[kMsm]);
+        }
+        return BZH_OK;
+    }
+};
+
+template <class C, class D>
+static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, D& drv) {
+    using SF = typename CurveInfo<C>::SF;
     const int field = CurveInfo<C>::scalar_field;
     const size_t n = bases->n - 2, B = batch;
     unsigned k = 0;
     while (((size_t)1 << k) < n) k++;
     if (((size_t)1 << k) != n || !B) return BZH_E_ARG;
-    const size_t nrand = n + 1 + 2 * (size_t)k, ntail = 1 + 2 * (size_t)k;
+    const size_t nrand = n + 1 + 2 * (size_t)k;
     hipStream_t st = ctx->stream;
 
     // The generator collapse: at round jstar the folded generators get their own tables and the rounds continue on m points
@@ -268,8 +540,9 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
     const int tail_nwin = (256 + tail_c - 1) / tail_c;
     const size_t tail_scratch = jstar ? msm_collapse_scratch_bytes(bases, (size_t)1 << jstar, B, tail_c) : 0;
     // device arena (workspace slot 4), per proof: raw rng | rand scalars | s_poly | p x2 | b x2 | s x2 | LR | S scalars | small
+    // | the driver's own
     const size_t per = nrand * 16 + nrand * 8 + n * 8 + 2 * n * 8 + 2 * n * 8 + 2 * n * 8 + 2 * (n + 4) * 8 + (n + 2) * 8 +
-                       (kHc + 4) * 8;
+                       (kHc + 4) * 8 + D::kExtraWords;
     const size_t tail_words = jstar ? B * (tail_m + 2) * (size_t)tail_nwin * (16 + 20) + (tail_scratch + 3) / 4 + 64 : 0;   // table + its fe29 copy
     void* arena = nullptr;
     BZH_TRY(ws_ensure(ctx, 4, (B * per + tail_words) * 4 + 256 + 16 * 16, &arena));   // (+ the roundings of take())
@@ -297,66 +570,39 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
     uint32_t* d_hc = take(B * kHc * 8);
     uint32_t* d_dv = take(B * 8);       // s(x3) / v per proof
     uint32_t* d_vlr = take(B * 2 * 8);  // value_l, value_r per proof
+    uint32_t* d_extra = D::kExtraWords ? take(B * D::kExtraWords) : nullptr;
     void* d_out = nullptr;
     BZH_TRY(ws_ensure(ctx, 5, 2 * B * 96, &d_out));
+    const IpaArena A{B, n, nrand, k, d_raw, d_rand, d_hc, d_dv, d_extra, (uint32_t*)d_out};
 
     const unsigned g256 = 256;
     auto grid2 = [&](size_t c) { return dim3((unsigned)((c + g256 - 1) / g256), (unsigned)B); };
     if (B > 65535) return BZH_E_ARG;
 
     // randomness: upstream draw order = n coefficients of s(X), s_blind, then (l_j, r_j) per round
-    if (d_raw_in) {  // the 64-byte draws are already on the device (batch x nrand, proof-major)
-        BZH_HIP_TRY(ctx, hipMemcpyAsync(d_raw, d_raw_in, B * nrand * 64, hipMemcpyDeviceToDevice, st));
-    } else {
-        for (size_t b = 0; b < B; b++)
-            BZH_TRY(h2d_small(ctx, d_raw + b * nrand * 16, rng_bytes + b * rng_stride, nrand * 64));
-    }
+    BZH_TRY(drv.draws(ctx, A));
     hipLaunchKernelGGL((k_reduce_wide<SF>), dim3((unsigned)((B * nrand + g256 - 1) / g256)), dim3(g256), 0, st, d_raw, B * nrand,
                        d_rand);
     BZH_HIP_TRY(ctx, hipMemcpy2DAsync(d_spoly, n * 32, d_rand, nrand * 32, n * 32, B, hipMemcpyDeviceToDevice, st));
-    // the scalars the host needs (s_blind and the round blinds) come back in one strided copy
-    std::vector<Fe<SF>> tail(B * ntail);
-    for (size_t b = 0; b < B; b++) BZH_TRY(d2h_async(ctx, &tail[b * ntail], d_rand + (b * nrand + n) * 8, ntail * 32));
-
-    std::vector<Fe<SF>> hc(B * kHc, fe_zero<SF>());
-    for (size_t b = 0; b < B; b++) hc[b * kHc] = fe_to_mont(fe_from_u64<SF>(x3s + 4 * b));
-    auto push_hc = [&]() -> int {
-        return h2d_small(ctx, d_hc, hc.data(), B * kHc * 32);
-    };
-    BZH_TRY(push_hc());
+    BZH_TRY(drv.begin(ctx, A));
     // s(X) -= s(x3)
     BZH_TRY(poly_eval(ctx, field, d_spoly, n, B, d_hc, kHc, d_dv));
     hipLaunchKernelGGL((k_sub_at0_batch<SF>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, d_spoly, n, d_dv, B);
     // S = commit(s, s_blind): scalars [s..., 0, s_blind]
     hipLaunchKernelGGL((k_ipa_commit_scalars<SF>), grid2(n + 2), dim3(g256), 0, st, d_spoly, d_rand, n, nrand, d_commit);
     BZH_HIP_TRY(ctx, hipGetLastError());
+    drv.msm_begin(ctx);
     BZH_TRY(msm_run(ctx, bases, d_commit, n + 2, B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
-    std::vector<uint64_t> jac(2 * B * 12), xy(2 * B * 8);
-    BZH_TRY(d2h_async(ctx, jac.data(), d_out, B * 96));
-    BZH_TRY(d2h_finish(ctx));
-    h_jac_to_affine<PB>(jac.data(), B, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, xy.data());
-    uint64_t ch[4];
-    std::vector<Fe<SF>> f(B);
-    for (size_t b = 0; b < B; b++) {
-        BZH_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + b * 8));
-        BZH_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
-        const Fe<SF> xi = fe_to_mont(fe_from_u64<SF>(ch));
-        BZH_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
-        hc[b * kHc + 1] = xi;
-        hc[b * kHc + 2] = fe_to_mont(fe_from_u64<SF>(ch));
-        f[b] = fe_add(fe_mul(tail[b * ntail], xi), fe_to_mont(fe_from_u64<SF>(blinds + 4 * b)));
-    }
-    BZH_TRY(push_hc());
+    drv.msm_end(ctx);
+    BZH_TRY(drv.head(ctx, A));
     // p' = poly + xi * s_poly, then p'[0] -= v with v = p'(x3)
     hipLaunchKernelGGL((k_ipa_axpy<SF>), grid2(n), dim3(g256), 0, st, d_polys, d_spoly, d_hc, n, p_cur);
     BZH_TRY(poly_eval(ctx, field, p_cur, n, B, d_hc, kHc, d_dv));
     hipLaunchKernelGGL((k_sub_at0_batch<SF>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, p_cur, n, d_dv, B);
-    std::vector<Fe<SF>> vm(B);
-    BZH_TRY(d2h_async(ctx, vm.data(), d_dv, B * 32));  // lands at the next d2h_finish
+    BZH_TRY(drv.keep_v(ctx, A));
     hipLaunchKernelGGL((k_ipa_init_b_s<SF>), grid2(n), dim3(g256), 0, st, d_hc, n, b_cur, s_cur);
     BZH_HIP_TRY(ctx, hipGetLastError());
 
-    std::vector<Fe<SF>> us(B), us_inv(B);
     // the instance the rounds run on: the SRS and n points, or (from round jstar on) the per-proof tables and tail_m points
     const bzh_bases* rb = bases;
     bzh_bases tail_bases;
@@ -369,8 +615,7 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
             rn = tail_m;
             j0 = j;
             // s restarts at (1): the folded generators ARE the instance now
-            std::vector<Fe<SF>> ones(B, fe_one<SF>());
-            BZH_TRY(h2d_small(ctx, s_cur, ones.data(), B * 32));
+            BZH_TRY(drv.ones(ctx, A, s_cur));
         }
         const size_t m = n >> j, half = m >> 1, cnt = (size_t)1 << (j - j0);
         hipLaunchKernelGGL((k_ipa_inner2<SF>), dim3((unsigned)B, 2), dim3(256), 0, st, p_cur, b_cur, half, d_vlr);
@@ -378,30 +623,17 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
             hipLaunchKernelGGL((k_ipa_round_vectors_paired<SF>), grid2(rn + 1), dim3(g256), 0, st, p_cur, s_cur, rn, k - j, d_vlr, d_hc,
                                d_rand, nrand, n, j, d_lr);
             BZH_HIP_TRY(ctx, hipGetLastError());
+            drv.msm_begin(ctx);
             BZH_TRY(msm_run_paired(ctx, rb, d_lr, rn, k - j, B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
         } else {
             hipLaunchKernelGGL((k_ipa_round_vectors<SF>), grid2(n + 1), dim3(g256), 0, st, p_cur, s_cur, n, k - j, d_vlr, d_hc,
                                d_rand, nrand, n, j, d_lr);
             BZH_HIP_TRY(ctx, hipGetLastError());
+            drv.msm_begin(ctx);
             BZH_TRY(msm_run(ctx, bases, d_lr, n + 2, 2 * B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
         }
-        BZH_TRY(d2h_async(ctx, jac.data(), d_out, 2 * B * 96));
-        BZH_TRY(d2h_finish(ctx));
-        h_jac_to_affine<PB>(jac.data(), 2 * B, BZH_FORM_MONTGOMERY, BZH_FORM_CANONICAL, xy.data());
-        for (size_t b = 0; b < B; b++) {
-            BZH_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + (2 * b) * 8));
-            BZH_TRY(bzh_transcript_write_point(trs[b], C::id, xy.data() + (2 * b + 1) * 8));
-            BZH_TRY(bzh_transcript_squeeze_challenge(trs[b], ch));
-            us[b] = fe_to_mont(fe_from_u64<SF>(ch));
-        }
-        us_inv = us;
-        if (!h_batch_invert(us_inv.data(), B)) return BZH_E_ARG;  // a zero challenge has no inverse (probability 2^-255)
-        for (size_t b = 0; b < B; b++) {
-            hc[b * kHc + 3] = us[b];
-            hc[b * kHc + 4] = us_inv[b];
-            f[b] = fe_add(f[b], fe_add(fe_mul(tail[b * ntail + 1 + 2 * j], us_inv[b]), fe_mul(tail[b * ntail + 2 + 2 * j], us[b])));
-        }
-        BZH_TRY(push_hc());
+        drv.msm_end(ctx);
+        BZH_TRY(drv.round(ctx, A, j));
         // p' <- p_lo + u^-1 p_hi ; b <- b_lo + u b_hi ; s <- s (x) (1, u)
         hipLaunchKernelGGL((k_ipa_round_fold<SF>), grid2(half > cnt ? half : cnt), dim3(g256), 0, st, p_cur, b_cur, s_cur, half, cnt,
                            d_hc, p_nxt, b_nxt, s_nxt);
@@ -410,18 +642,7 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
         std::swap(b_cur, b_nxt);
         std::swap(s_cur, s_nxt);
     }
-    std::vector<Fe<SF>> c(B);
-    BZH_TRY(d2h_async(ctx, c.data(), p_cur, B * 32));
-    BZH_TRY(d2h_finish(ctx));
-    for (size_t b = 0; b < B; b++) {
-        fe_to_u64<SF>(out_v + 4 * b, fe_from_mont(vm[b]));
-        uint64_t sc[4];
-        fe_to_u64<SF>(sc, fe_from_mont(c[b]));
-        BZH_TRY(bzh_transcript_write_scalar(trs[b], sc));
-        fe_to_u64<SF>(sc, fe_from_mont(f[b]));
-        BZH_TRY(bzh_transcript_write_scalar(trs[b], sc));
-    }
-    return BZH_OK;
+    return drv.tail_out(ctx, A, p_cur);
 }
 
 // ---------------------------------------------------------------------------
@@ -712,7 +933,18 @@ int ipa_open(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size
              const uint64_t* x3s, const uint8_t* rng_bytes, size_t rng_stride, bzh_transcript* const* trs, uint64_t* out_v,
              const uint32_t* d_raw_in) {
     return with_curve(bases->curve, [&](auto c) {
-        return ipa_open_t<decltype(c)>(ctx, bases, d_polys, batch, blinds, x3s, rng_bytes, rng_stride, trs, out_v, d_raw_in);
+        using C = decltype(c);
+        IpaHostDriver<C> drv{blinds, x3s, rng_bytes, rng_stride, trs, out_v, d_raw_in};
+        return ipa_open_t<C>(ctx, bases, d_polys, batch, drv);
+    });
+}
+int ipa_open_device(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint32_t* d_blinds,
+                    const uint32_t* d_x3s, int form, const uint8_t* d_rng, size_t rng_stride, bzh_transcript_batch* tb,
+                    uint32_t* d_out_v, uint8_t* d_status) {
+    return with_curve(bases->curve, [&](auto c) {
+        using C = decltype(c);
+        IpaDeviceDriver<C> drv{tb, d_blinds, d_x3s, d_rng, rng_stride, d_out_v, d_status, form};
+        return ipa_open_t<C>(ctx, bases, d_polys, batch, drv);
     });
 }
 int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,

@@ -234,13 +234,31 @@ int tb_absorb_locked(bzh_transcript_batch* tb, int kind, const void* d_base, siz
     if (!count) return BZH_OK;
     if (kind == 0)
         BZH_TRY(absorb_launch<0>(tb, d_base, count, stride, form, d_pre));
+    else if (kind == 1)
+        BZH_TRY(absorb_launch<1>(tb, d_base, count, stride, form, d_pre));
     else if (kind == 2)
         BZH_TRY(absorb_launch<2>(tb, d_base, count, stride, form, nullptr));
+    else if (kind == 3)
+        BZH_TRY(absorb_launch<3>(tb, d_base, count, stride, form, nullptr));
     else
         return BZH_E_ARG;
-    advance(tb, count, (uint32_t)kKindLen[kind], false);
+    advance(tb, count, (uint32_t)kKindLen[kind], (kind & 1) != 0);
     return BZH_OK;
 }
+// bzh_transcript_batch_write_jacobian's device half: bzh_batch_normalize's launch over the whole span the points lie in, into the
+// batch's own scratch (which grows on first use), then the write kernel
+int tb_write_jacobian_locked(bzh_transcript_batch* tb, const void* d_xyz, size_t count, size_t stride, int form) {
+    if (!count) return BZH_OK;
+    bzh_ctx* ctx = tb->ctx;
+    const size_t n = (tb->batch - 1) * stride + count;
+    BZH_TRY(scratch_ensure(tb, n * 64 + n + 256));
+    uint8_t* d_st = (uint8_t*)tb->d_scratch + n * 64;
+    BZH_TRY(normalize_run(ctx, tb->curve, d_xyz, n, form, tb->d_scratch, nullptr, d_st));
+    BZH_TRY(absorb_launch<1>(tb, tb->d_scratch, count, stride, form, d_st));
+    advance(tb, count, 65, true);
+    return BZH_OK;
+}
+TbInfo tb_info(const bzh_transcript_batch* tb) { return TbInfo{tb->ctx, tb->curve, tb->batch, tb->proof_cap, tb->proof_len}; }
 int tb_squeeze_locked(bzh_transcript_batch* tb, int form, uint32_t* d_out) {
     bzh_ctx* ctx = tb->ctx;
     BZH_TRY(with_curve(tb->curve, [&](auto c) -> int {
@@ -351,7 +369,6 @@ extern "C" int bzh_transcript_batch_write_jacobian(bzh_transcript_batch* tb, con
         bzh_ctx* ctx = tb->ctx;
         std::lock_guard<std::mutex> lk(ctx->mu);
         BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        BZH_TRY(scratch_ensure(tb, n * 64 + n + 256));
         const void* d_in = xyz;
         if (host) {   // staged in workspace slot 3
             const std::vector<uint8_t> jac = compact(xyz, tb->batch, count, stride, 96);
@@ -360,9 +377,7 @@ extern "C" int bzh_transcript_batch_write_jacobian(bzh_transcript_batch* tb, con
             BZH_TRY(h2d_small(ctx, ws, jac.data(), jac.size()));
             d_in = ws;
         }
-        uint8_t* d_st = (uint8_t*)tb->d_scratch + n * 64;
-        BZH_TRY(normalize_run(ctx, tb->curve, d_in, n, form, tb->d_scratch, nullptr, d_st));
-        BZH_TRY(absorb_launch<1>(tb, tb->d_scratch, count, wstride, form, d_st));
+        return tb_write_jacobian_locked(tb, d_in, count, wstride, form);
     }
     advance(tb, count, 65, true);
     return BZH_OK;

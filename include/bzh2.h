@@ -282,6 +282,28 @@ int bzh_ipa_open(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* poly, int
 int bzh_ipa_open_batch(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* polys, int form, int mem, size_t batch,
                        const uint64_t* blinds, const uint64_t* x3s, const uint8_t* rng, size_t rng_stride,
                        bzh_transcript* const* transcripts, uint64_t* out_v);
+/* bzh_ipa_open_batch against a device-resident bzh_transcript_batch, which is declared below (csrc/ipa.hip, csrc/ipa_scalars.hpp): the
+ * same openings, proof for proof and byte for byte -- S, (L_j, R_j) for j < k, then c and f go into transcript b of `transcripts`,
+ * out_v[b] = p_b(x3_b); the message order, the draw order of rng, the generator collapse and BZH_IPA_COLLAPSE / BZH_IPA_TAIL_C
+ * are those of bzh_ipa_open_batch -- with the rounds on the device: every point is normalised and absorbed from HBM, every
+ * challenge squeezed into HBM, and a lane per proof inverts u_j and folds f.  `transcripts` belongs to this ctx, its curve is the
+ * curve of `bases` and its batch is `batch`.  `mem` applies to every data pointer of the call: with BZH_MEM_DEVICE polys, blinds,
+ * x3s, rng, out_v (16-byte aligned) and status are device pointers -- blinds, x3s and out_v batch x 4 limbs in `form`, the 64-byte
+ * draws of proof b at rng + b * rng_stride -- and the call only enqueues: x3, itself a squeezed challenge, never leaves HBM.  With
+ * BZH_MEM_HOST the operands are staged up once at the start and out_v / status read back once at the end.
+ * status (may be NULL): one byte per proof, 0, or nonzero if a round challenge of that proof was zero and so has no inverse
+ * (bzh_ipa_open_batch returns BZH_E_ARG there; without a read-back there is nothing to return it from).  Identity or invalid
+ * points are reported by bzh_transcript_batch_status as ever.
+ * Between its first launch and its last the call copies no point, scalar or challenge to the host, does no host field or curve
+ * arithmetic and adds no stream synchronisation of its own; what bzh_msm itself waits for, and a workspace (the ctx's, or the
+ * batch's normalisation scratch) that grows on first use, stay as they are.
+ * BZH_E_ARG, the batch left as it was: a NULL ctx, bases, transcripts or data pointer; a host-resident batch; a batch of another
+ * ctx, curve or size; n not a power of two; batch == 0 or > 65535; unknown form or mem; a misaligned device pointer; rng_stride
+ * < 64 * (n + 1 + 2k).  BZH_E_RANGE, nothing absorbed: proof_cap cannot take 32 * (1 + 2k) + 64 more bytes. */
+struct bzh_transcript_batch;
+int bzh_ipa_open_batch_device(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* polys, int form, int mem, size_t batch,
+                              const uint64_t* blinds, const uint64_t* x3s, const uint8_t* rng, size_t rng_stride,
+                              struct bzh_transcript_batch* transcripts, uint64_t* out_v, uint8_t* status);
 int bzh_ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                    const uint8_t* proof, size_t proof_len, bzh_transcript* transcript, const uint64_t* g0_u_w);
 
@@ -669,7 +691,9 @@ int bzh_batch_normalize_plan(size_t n, size_t* lanes, size_t* chain);
  * transcript::{Blake2bWrite, Challenge255} in lockstep, resident in HBM -- the step the points of bzh_msm are normalised for.
  * They absorb from device memory and squeeze into device memory, one launch per step for the whole batch:
  *     bzh_msm (BZH_MEM_DEVICE output)  ->  bzh_transcript_batch_write_jacobian  ->  bzh_transcript_batch_squeeze
- * with no read-back in between.  Not used by bzh_prove_batch, bzh_ipa_open(_batch) or the verifier.
+ * with no read-back in between, and on through the opening argument: bzh_ipa_open_batch_device runs its rounds against such a
+ * batch.  Not used by bzh_prove_batch or bzh_ipa_open(_batch), which keep their host transcripts; the verifier's opt-in device
+ * pass drives a batch of its own.
  * Conventions: those of bzh_batch_normalize.  `mem` applies to every data pointer of a call; device buffers are 16-byte aligned;
  * with BZH_MEM_DEVICE a call only enqueues on the ctx's stream; count == 0 returns BZH_OK.  `curve` (Vesta, Pallas, BN254 G1)
  * fixes both fields: coordinates are in the base field, scalars and challenges in the scalar field.  Every call gives every
