@@ -887,6 +887,44 @@ def _ctx_expr_eval(self, field: int, program, columns, form: int = FORM_CANONICA
 
 Context.expr_eval = _ctx_expr_eval
 
+EXPORTS += ["bzh_vm2_eval"]
+# one 16-byte VM v2 instruction word (csrc/vm2_isa.hpp; what bzh_quotient_program_for_circuit hands out)
+VM2_OP_DTYPE = np.dtype([("code", "u1"), ("a_kind", "u1"), ("b_kind", "u1"), ("pad", "u1"), ("a_idx", "<i4"), ("b_idx", "<i4"),
+                         ("a_rot", "<i2"), ("b_rot", "<i2")])
+
+
+def _ctx_vm2_eval(self, field: int, ops, columns, consts, size: int, batch: int = 1, nlds: int = 0, column_strides=None,
+                  const_stride: int = 0, form: int = FORM_CANONICAL, mem: int = MEM_HOST, out=None, nconsts: int | None = None):
+    """Run a VM v2 program (bzh_vm2_eval; `ops`: VM2_OP_DTYPE records) over `batch` vectors of `size` rows and return register r0 of
+    every row, (batch * size, 4) uint64.  columns: (n, 4) uint64 arrays, vector v of column c starting column_strides[c] elements
+    after vector v - 1 (0: shared); consts: (n, 4) uint64 (host), vector v's const_stride elements after (0: shared), nconsts of
+    them per vector (default: all of them, or const_stride).  With MEM_DEVICE the columns and `out` are device addresses.  `out` (MEM_HOST: a (batch * size, 4) uint64 array) is filled and returned when given."""
+    L = load()
+    vp = ctypes.c_void_p
+    L.bzh_vm2_eval.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                               vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                               ctypes.c_int, vp]
+    ops = np.ascontiguousarray(ops, dtype=VM2_OP_DTYPE)
+    if mem == MEM_HOST:
+        columns = [_as_elems(c) for c in columns]
+        if out is None:
+            out = np.zeros((batch * size, 4), dtype=np.uint64)
+    ncols = len(columns)
+    ptrs = (vp * max(ncols, 1))(*[c.ctypes.data if mem == MEM_HOST else int(c) for c in columns])
+    strides = (ctypes.c_size_t * max(ncols, 1))(*(column_strides if column_strides is not None else [0] * ncols))
+    cv = _as_elems(consts) if len(consts) else np.zeros((1, 4), dtype=np.uint64)
+    if nconsts is None:
+        nconsts = (const_stride or cv.shape[0]) if len(consts) else 0
+    log_size = max(size.bit_length() - 1, 0)
+    assert (1 << log_size) == size, "size must be a power of two"
+    rc = L.bzh_vm2_eval(self.handle, field, _vp(ops), len(ops), ptrs, strides, ncols, _vp(cv), nconsts, const_stride, log_size, batch,
+                        nlds, form, mem, _vp(out) if mem == MEM_HOST else vp(int(out)))
+    self._check(rc, "bzh_vm2_eval")
+    return out
+
+
+Context.vm2_eval = _ctx_vm2_eval
+
 
 # ---- multiopen / lookup helpers ---------------------------------------------------------------------
 EXPORTS += ["bzh_kate_division", "bzh_kate_division_batch", "bzh_permute_expression_pair"]

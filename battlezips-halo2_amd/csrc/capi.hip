@@ -9,6 +9,7 @@
 #include "ctx.hpp"
 #include "curve.cuh"
 #include "host_field.hpp"
+#include "vm2_isa.hpp"
 
 namespace bzh {
 void ntt_cache_drop(bzh_ctx* ctx);
@@ -704,6 +705,57 @@ int bzh_permute_expression_pair_batch(bzh_ctx* ctx, int field, const uint64_t* i
     return rc;
 }
 
+// What bzh_expr_eval_batch and bzh_vm2_eval put on the device around their launch: the columns (host columns only), the
+// constants, the program, the column pointer and stride tables, and room for a host caller's output.
+struct ExprStaged {
+    Stager s;
+    uint32_t *d_consts, *d_prog, *d_ptrs, *d_strides, *d_out;
+};
+static int stage_expr(bzh_ctx* ctx, int field, int form, int mem, const void* prog, size_t prog_bytes, const uint64_t* const* columns,
+                      const size_t* column_strides, size_t ncols, const uint64_t* consts, size_t nconsts, size_t const_stride,
+                      size_t size, size_t batch, uint64_t* out, ExprStaged& st) {
+    int rc = BZH_OK;
+    if (mem == BZH_MEM_DEVICE && form != BZH_FORM_MONTGOMERY) return BZH_E_ARG;
+    // host columns: vector v of column c is columns[c] + v * stride * 4 limbs; they are staged as `reps` consecutive copies
+    std::vector<size_t> strides(ncols, 0), reps(ncols, 1);
+    size_t host_elems = 0;
+    for (size_t c = 0; c < ncols; c++) {
+        strides[c] = (column_strides && batch > 1) ? column_strides[c] : 0;
+        if (strides[c] && strides[c] < size) return BZH_E_ARG;
+        reps[c] = strides[c] ? batch : 1;
+        host_elems += reps[c] * size;
+    }
+    const size_t nconst_total = const_stride ? const_stride * (batch - 1) + nconsts : nconsts;
+    Stager& s = st.s;
+    s = Stager{ctx, field, form};
+    if ((rc = s.begin(((mem == BZH_MEM_HOST ? host_elems + batch * size : 0) + nconst_total) * 32 + prog_bytes +
+                      ncols * (sizeof(void*) + sizeof(size_t) + 128) + 1024)))
+        return rc;
+    std::vector<const uint32_t*> ptrs(ncols);
+    for (size_t c = 0; c < ncols; c++) {
+        if (mem == BZH_MEM_HOST) {
+            uint32_t* d = s.carve(reps[c] * size * 32);
+            for (size_t v = 0; v < reps[c]; v++)
+                BZH_HIP_TRY(ctx, hipMemcpyAsync(d + v * size * 8, columns[c] + v * strides[c] * 4, size * 32, hipMemcpyHostToDevice,
+                                                ctx->stream));
+            if (form == BZH_FORM_CANONICAL && (rc = field_convert(ctx, field, d, reps[c] * size, 1))) return rc;
+            ptrs[c] = d;
+            if (strides[c]) strides[c] = size;
+        } else {
+            ptrs[c] = (const uint32_t*)columns[c];
+        }
+    }
+    if ((rc = s.in(consts, nconst_total, &st.d_consts))) return rc;
+    st.d_prog = s.carve(prog_bytes);
+    st.d_ptrs = s.carve(ncols * sizeof(void*) + 8);
+    st.d_strides = s.carve(ncols * sizeof(size_t) + 8);
+    if ((rc = h2d_small(ctx, st.d_prog, prog, prog_bytes))) return rc;
+    if (ncols && (rc = h2d_small(ctx, st.d_ptrs, ptrs.data(), ncols * sizeof(void*)))) return rc;
+    if (ncols && (rc = h2d_small(ctx, st.d_strides, strides.data(), ncols * sizeof(size_t)))) return rc;
+    st.d_out = mem == BZH_MEM_HOST ? s.carve(batch * size * 32) : (uint32_t*)out;
+    return BZH_OK;
+}
+
 int bzh_expr_eval_batch(bzh_ctx* ctx, int field, const bzh_expr_op* prog, size_t nops, const uint64_t* const* columns,
                         const size_t* column_strides, size_t ncols, const uint64_t* consts, size_t nconsts, size_t const_stride,
                         unsigned log_size, int result_slot, size_t batch, int form, int mem, uint64_t* out) {
@@ -726,48 +778,14 @@ int bzh_expr_eval_batch(bzh_ctx* ctx, int field, const bzh_expr_op* prog, size_t
             if (kinds[q] > BZH_EXPR_CONST || kinds[q] < 0) return BZH_E_ARG;
         }
     }
-    if (mem == BZH_MEM_DEVICE && form != BZH_FORM_MONTGOMERY) return BZH_E_ARG;
-    // host columns: vector v of column c is columns[c] + v * stride * 4 limbs; they are staged as `reps` consecutive copies
-    std::vector<size_t> strides(ncols, 0), reps(ncols, 1);
-    size_t host_elems = 0;
-    for (size_t c = 0; c < ncols; c++) {
-        strides[c] = (column_strides && batch > 1) ? column_strides[c] : 0;
-        if (strides[c] && strides[c] < size) return BZH_E_ARG;
-        reps[c] = strides[c] ? batch : 1;
-        host_elems += reps[c] * size;
-    }
-    const size_t nconst_total = const_stride ? const_stride * (batch - 1) + nconsts : nconsts;
-    Stager s{ctx, field, form};
-    if ((rc = s.begin(((mem == BZH_MEM_HOST ? host_elems + batch * size : 0) + nconst_total) * 32 + nops * sizeof(bzh_expr_op) +
-                      ncols * (sizeof(void*) + sizeof(size_t) + 128) + 1024)))
+    ExprStaged st;
+    if ((rc = stage_expr(ctx, field, form, mem, prog, nops * sizeof(bzh_expr_op), columns, column_strides, ncols, consts, nconsts,
+                         const_stride, size, batch, out, st)))
         return rc;
-    std::vector<const uint32_t*> ptrs(ncols);
-    for (size_t c = 0; c < ncols; c++) {
-        if (mem == BZH_MEM_HOST) {
-            uint32_t* d = s.carve(reps[c] * size * 32);
-            for (size_t v = 0; v < reps[c]; v++)
-                BZH_HIP_TRY(ctx, hipMemcpyAsync(d + v * size * 8, columns[c] + v * strides[c] * 4, size * 32, hipMemcpyHostToDevice,
-                                                ctx->stream));
-            if (form == BZH_FORM_CANONICAL && (rc = field_convert(ctx, field, d, reps[c] * size, 1))) return rc;
-            ptrs[c] = d;
-            if (strides[c]) strides[c] = size;
-        } else {
-            ptrs[c] = (const uint32_t*)columns[c];
-        }
-    }
-    uint32_t* d_consts;
-    if ((rc = s.in(consts, nconst_total, &d_consts))) return rc;
-    uint32_t* d_prog = s.carve(nops * sizeof(bzh_expr_op));
-    uint32_t* d_ptrs = s.carve(ncols * sizeof(void*) + 8);
-    uint32_t* d_strides = s.carve(ncols * sizeof(size_t) + 8);
-    if ((rc = h2d_small(ctx, d_prog, prog, nops * sizeof(bzh_expr_op)))) return rc;
-    if (ncols && (rc = h2d_small(ctx, d_ptrs, ptrs.data(), ncols * sizeof(void*)))) return rc;
-    if (ncols && (rc = h2d_small(ctx, d_strides, strides.data(), ncols * sizeof(size_t)))) return rc;
-    uint32_t* d_out = mem == BZH_MEM_HOST ? s.carve(batch * size * 32) : (uint32_t*)out;
-    rc = expr_eval(ctx, field, d_prog, (int)nops, (const uint32_t* const*)d_ptrs, (const size_t*)d_strides, d_consts, const_stride, size,
-                   result_slot, batch, nslots, d_out);
+    rc = expr_eval(ctx, field, st.d_prog, (int)nops, (const uint32_t* const*)st.d_ptrs, (const size_t*)st.d_strides, st.d_consts,
+                   const_stride, size, result_slot, batch, nslots, st.d_out);
     if (rc) return rc;
-    if (mem == BZH_MEM_HOST) return s.out(out, d_out, batch * size);
+    if (mem == BZH_MEM_HOST) return st.s.out(out, st.d_out, batch * size);
     return BZH_OK;  // staging reuse by the next call is stream-ordered
 }
 
@@ -775,6 +793,48 @@ int bzh_expr_eval(bzh_ctx* ctx, int field, const bzh_expr_op* prog, size_t nops,
                   const uint64_t* consts, size_t nconsts, unsigned log_size, int result_slot, int form, int mem, uint64_t* out) {
     return bzh_expr_eval_batch(ctx, field, prog, nops, columns, nullptr, ncols, consts, nconsts, 0, log_size, result_slot, 1, form, mem,
                                out);
+}
+
+// is `o` one of the interpreter's 52 cases, and does everything it indexes exist?  (k_expr_vm2's switch skips a word it has no
+// case for, and nothing on the device checks an index)
+static bool vm2_op_valid(const ExprOp2& o, size_t ncols, size_t nconsts, int nlds) {
+    if (o.code >> 6) return false;
+    if (o.form() == V2_SS ? o.pos() > 2 : (o.form() == V2_LL || o.form() == V2_UN) && o.op() == 3) return false;
+    auto leaf_ok = [&](int kind, int32_t idx) {
+        if (idx < 0) return false;
+        switch (kind) {
+            case BZH_EXPR_COLUMN: return (size_t)idx < ncols;
+            case BZH_EXPR_CONST: return (size_t)idx < nconsts;
+            case BZH_EXPR_LDS: return idx < nlds;
+        }
+        return false;
+    };
+    if (o.reads_a() && !leaf_ok(o.a_kind, o.a_idx)) return false;
+    if (o.reads_b() && !leaf_ok(o.b_kind, o.b_idx)) return false;
+    if (o.is_store() && !leaf_ok(BZH_EXPR_LDS, o.a_idx)) return false;
+    return true;
+}
+
+int bzh_vm2_eval(bzh_ctx* ctx, int field, const void* ops, size_t nops, const uint64_t* const* columns, const size_t* column_strides,
+                 size_t ncols, const uint64_t* consts, size_t nconsts, size_t const_stride, unsigned log_size, size_t batch, int nlds,
+                 int form, int mem, uint64_t* out) {
+    BZH_POLY_PROLOGUE((field != BZH_FIELD_FP && field != BZH_FIELD_FQ) || !ops || !nops || nops > (size_t)INT32_MAX ||
+                      (!columns && ncols) || (!consts && nconsts) || !out || log_size > 30 || !batch || batch > 65535 || nlds < 0 ||
+                      (const_stride && const_stride < nconsts));
+    const size_t size = (size_t)1 << log_size;
+    if (size % 128) return BZH_E_ARG;   // whole workgroups of either kernel
+    const ExprOp2* prog = (const ExprOp2*)ops;
+    for (size_t i = 0; i < nops; i++)
+        if (!vm2_op_valid(prog[i], ncols, nconsts, nlds)) return BZH_E_ARG;
+    ExprStaged st;
+    if ((rc = stage_expr(ctx, field, form, mem, ops, nops * sizeof(ExprOp2), columns, column_strides, ncols, consts, nconsts, const_stride,
+                         size, batch, out, st)))
+        return rc;
+    rc = expr_eval2(ctx, field, st.d_prog, (int)nops, (const uint32_t* const*)st.d_ptrs, (const size_t*)st.d_strides, st.d_consts,
+                    const_stride, size, batch, nlds, st.d_out);
+    if (rc) return rc;
+    if (mem == BZH_MEM_HOST) return st.s.out(out, st.d_out, batch * size);
+    return BZH_OK;  // staging reuse by the next call is stream-ordered
 }
 
 int bzh_ipa_open_batch(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* polys, int form, int mem, size_t batch,

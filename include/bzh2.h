@@ -263,6 +263,20 @@ int bzh_expr_eval_batch(bzh_ctx* ctx, int field, const bzh_expr_op* prog, size_t
                         const size_t* column_strides, size_t ncols, const uint64_t* consts, size_t nconsts, size_t const_stride,
                         unsigned log_size, int result_slot, size_t batch, int form, int mem, uint64_t* out);
 
+/* One VM v2 program -- the quotient interpreter of bzh_prove_batch, run without a proving key -- over `batch` vectors: out holds
+ * batch x 2^log_size values of register r0 after the last instruction.  ops: nops 16-byte instruction words as
+ * bzh_quotient_program_for_circuit hands them out (layout there; the instruction set: csrc/vm2_isa.hpp); operand kinds are
+ * BZH_EXPR_COLUMN, BZH_EXPR_CONST and 3 = slot of the slot file (nlds slots, kept in LDS).  columns, column_strides, consts,
+ * const_stride, form and mem as for bzh_expr_eval_batch.  The registers start at zero; the slot file is NOT cleared, a program
+ * reads only slots it has stored to.  The program is checked before anything is launched.  BZH_E_ARG, out untouched: an
+ * instruction word the interpreter has no case for (form SS at register 3, form LL with RSUB, form UN with operation 3, a code
+ * above 63); an operand that is read and is not a column, a constant or a slot; a column index not below ncols, a constant
+ * index not below nconsts, a slot index (a STORE's target included) not below nlds; 2^log_size not a multiple of 128; batch 0 or
+ * above 65535; a field other than the two Pasta fields.  BZH_E_RANGE: more slots than 64 KB of LDS hold at 64 rows (nlds > 32). */
+int bzh_vm2_eval(bzh_ctx* ctx, int field, const void* ops, size_t nops, const uint64_t* const* columns, const size_t* column_strides,
+                 size_t ncols, const uint64_t* consts, size_t nconsts, size_t const_stride, unsigned log_size, size_t batch, int nlds,
+                 int form, int mem, uint64_t* out);
+
 /* ---- inner-product-argument opening (halo2_proofs poly::commitment::{create_proof, verify_proof}) --
  * Step 9 of plonk::create_proof and the heart of verify_proof (benches/board.rs:80-86).
  * `bases` must hold n + 2 points: the n = 2^k SRS generators followed by U and W (Params.u, Params.w);
