@@ -277,8 +277,9 @@ class NativeProvingKey:
         return kb.value, wb.value
 
     def close(self):
-        """bzh_pk_free.  Refused (BzhError, the key stays open) while a prove / verify call on the key is still running on
-        another ctx: the key's workspaces and code belong to every ctx that uses it."""
+        """bzh_pk_free.  Refused (BzhError, the key stays open) while a prove / verify call on the key has started on any ctx and
+        not returned -- also one that still waits for its ctx: the key's workspaces and code belong to every ctx that uses it.
+        Once this has returned, no thread may start a call on the key."""
         if self.handle is not None:
             self.ctx._check(_bind().bzh_pk_free(self.ctx.handle, self.handle), "bzh_pk_free")
             self.handle = None
@@ -445,7 +446,8 @@ class NativeVerifyingKey:
         return [bool(v) for v in res]
 
     def close(self):
-        """bzh_vk_free.  Refused (BzhError, the key stays open) while a verify_batch on the key is still running."""
+        """bzh_vk_free.  Refused (BzhError, the key stays open) while a verify_batch on the key has started on any ctx and not
+        returned -- also one that still waits for its ctx.  Once this has returned, no thread may start a call on the key."""
         if self.handle is not None:
             _check(_bind().bzh_vk_free(self.handle), "bzh_vk_free")
             self.handle = None

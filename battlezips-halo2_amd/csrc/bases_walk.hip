@@ -71,7 +71,7 @@ int walk_t(bzh_ctx* ctx, const uint64_t* g_xy, int form, size_t n, uint32_t* d_o
         memcpy(g + 8 * c, v.l, 32);
     }
     void* d_g = nullptr;
-    int rc = ws_ensure(ctx, 0, 64, &d_g);
+    int rc = ws_ensure(ctx, WS_SCRATCH_A, 64, &d_g);   // leaf scratch: read by the one kernel below, no callee in between
     if (rc) return rc;
     if ((rc = h2d_small(ctx, d_g, g, 64))) return rc;
     const size_t threads = (n + WALK_L - 1) / WALK_L;
@@ -122,7 +122,7 @@ int bzh_bases_points(bzh_ctx* ctx, const bzh_bases* bases, size_t first, size_t 
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     void* tmp = nullptr;
-    int rc = ws_ensure(ctx, 1, count * 64, &tmp);
+    int rc = ws_ensure(ctx, WS_SCRATCH_B, count * 64, &tmp);   // leaf scratch: one conversion kernel and its read-back, no callee in between
     if (rc) return rc;
     const size_t elems = count * 2;
     const uint32_t* src = bases->d_xy + first * 16;

@@ -11,10 +11,6 @@
 #include "host_field.hpp"
 #include "vm2_isa.hpp"
 
-namespace bzh {
-void ntt_cache_drop(bzh_ctx* ctx);
-}
-
 using namespace bzh;
 
 static bool valid_curve(int c) { return c >= 0 && c <= 2; }
@@ -32,15 +28,16 @@ static unsigned field_two_adicity(int f) {
 
 // ---- host helpers (CPU build of the same field templates) ------------------
 namespace {
-// Staging for BZH_MEM_HOST calls: carve device buffers out of workspace slot 3, copy in, and
-// (canonical form) convert to Montgomery on the device.
+// Staging for BZH_MEM_HOST calls: carve device buffers out of WS_STAGE, copy in, and (canonical form) convert to Montgomery on
+// the device.  The buffers live until the call returns; what runs on them (msm_run*, ntt_run*, poly_*, lookup_permute, ipa_open)
+// takes other slots only.
 struct Stager {
     bzh_ctx* ctx;
     int field, form;
     char* cur = nullptr;
     int begin(size_t total_bytes) {
         void* p = nullptr;
-        int rc = ws_ensure(ctx, 3, total_bytes + 256, &p);
+        int rc = ws_ensure(ctx, WS_STAGE, total_bytes + 256, &p);
         cur = (char*)p;
         return rc;
     }
@@ -243,8 +240,8 @@ int bzh_ctx_destroy(bzh_ctx* ctx) {
     if (!ctx) return BZH_E_ARG;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    ntt_cache_drop(ctx);
-    for (int i = 0; i < bzh_ctx::kWsSlots; i++)
+    ctx->ntt.reset();
+    for (int i = 0; i < kWsSlots; i++)
         if (ctx->ws[i]) (void)hipFree(ctx->ws[i]);
     if (ctx->d_add_counter) (void)hipFree(ctx->d_add_counter);
     if (ctx->ped_tbl) (void)hipFree(ctx->ped_tbl);
@@ -403,7 +400,7 @@ int bzh_msm(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* scalars, size_
     if (mem == BZH_MEM_DEVICE) return msm_run(ctx, bases, (const uint32_t*)scalars, n, batch, form, (uint32_t*)out_xyz);
     void* stage = nullptr;
     const size_t sbytes = batch * n * 32, obytes = batch * 96;
-    int rc = ws_ensure(ctx, 3, sbytes + obytes + 64, &stage);
+    int rc = ws_ensure(ctx, WS_STAGE, sbytes + obytes + 64, &stage);   // held across msm_run, which takes WS_SCRATCH_* only
     if (rc) return rc;
     uint32_t* d_s = (uint32_t*)stage;
     uint32_t* d_o = (uint32_t*)((char*)stage + ((sbytes + 63) & ~(size_t)63));
@@ -425,7 +422,7 @@ int bzh_ntt(bzh_ctx* ctx, int field, uint64_t* data, unsigned log_n, size_t batc
     if (mem == BZH_MEM_DEVICE) return ntt_run(ctx, field, (uint32_t*)data, log_n, batch, omega, coset_shift, inverse, form);
     void* stage = nullptr;
     const size_t bytes = (batch << log_n) * 32;
-    int rc = ws_ensure(ctx, 3, bytes, &stage);
+    int rc = ws_ensure(ctx, WS_STAGE, bytes, &stage);   // held across ntt_run, which takes WS_SCRATCH_A only
     if (rc) return rc;
     BZH_HIP_TRY(ctx, hipMemcpyAsync(stage, data, bytes, hipMemcpyHostToDevice, ctx->stream));
     rc = ntt_run(ctx, field, (uint32_t*)stage, log_n, batch, omega, coset_shift, inverse, form);
@@ -447,8 +444,9 @@ int bzh_coeff_to_extended(bzh_ctx* ctx, int field, const uint64_t* coeffs, unsig
     uint32_t* d_out = (uint32_t*)out;
     void* stage = nullptr;
     if (mem == BZH_MEM_HOST || form == BZH_FORM_CANONICAL) {
-        // staged copy of the coefficients (host memory, or canonical device input that may not be written to)
-        int rc = ws_ensure(ctx, 3, (in_elems + (mem == BZH_MEM_HOST ? out_elems : 0)) * 32, &stage);
+        // staged copy of the coefficients (host memory, or canonical device input that may not be written to); held across
+        // ntt_run_padded, which takes WS_SCRATCH_A only
+        int rc = ws_ensure(ctx, WS_STAGE, (in_elems + (mem == BZH_MEM_HOST ? out_elems : 0)) * 32, &stage);
         if (rc) return rc;
         BZH_HIP_TRY(ctx, hipMemcpyAsync(stage, coeffs, in_elems * 32, mem == BZH_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                                         ctx->stream));
@@ -674,7 +672,8 @@ int bzh_permute_expression_pair_batch(bzh_ctx* ctx, int field, const uint64_t* i
     BZH_POLY_PROLOGUE(!input || !table || !out_input || !out_table || !usable_rows || usable_rows > stride || !batch || batch > 32767 ||
                       stride >> 31);
     void* ws = nullptr;
-    if ((rc = ws_ensure(ctx, 1, lookup_permute_ws_bytes(usable_rows, batch), &ws))) return rc;
+    // leaf scratch: lookup_permute's kernels work in it and call no MSM; the staging below is WS_STAGE
+    if ((rc = ws_ensure(ctx, WS_SCRATCH_B, lookup_permute_ws_bytes(usable_rows, batch), &ws))) return rc;
     const size_t total = batch * stride;
     const uint32_t *d_in = (const uint32_t*)input, *d_tab = (const uint32_t*)table;
     uint32_t *d_oa = (uint32_t*)out_input, *d_os = (uint32_t*)out_table;
@@ -862,7 +861,7 @@ int bzh_ipa_open_batch(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* pol
         return ipa_open(ctx, bases, (const uint32_t*)polys, batch, blinds, x3s, rng, rng_stride, transcripts, out_v);
     }
     int rc;
-    Stager s{ctx, field, form};  // workspace slot 3; the opening itself works in slots 0-2, 4 and 5
+    Stager s{ctx, field, form};  // WS_STAGE; the opening itself works in WS_SCRATCH_*, WS_IPA and WS_IPA_OUT
     if ((rc = s.begin(batch * n * 32))) return rc;
     uint32_t* d_polys;
     if ((rc = s.in(polys, batch * n, &d_polys))) return rc;
@@ -896,7 +895,7 @@ int bzh_ipa_open_batch_device(bzh_ctx* ctx, const bzh_bases* bases, const uint64
     }));
     const bool host = mem == BZH_MEM_HOST, canonical = form == BZH_FORM_CANONICAL;
     const size_t st_bytes = (batch + 15) & ~(size_t)15;
-    // workspace slot 3 (the opening itself works in slots 0-2, 4 and 5): host operands are staged up here once, and canonical
+    // WS_STAGE (the opening itself works in WS_SCRATCH_*, WS_IPA and WS_IPA_OUT): host operands are staged up here once, and canonical
     // coefficients get their Montgomery copy here
     Stager s{ctx, field, form};
     BZH_TRY(s.begin(((host || canonical) ? batch * n * 32 + 64 : 0) + (host ? batch * (96 + nrand * 64) + st_bytes + 5 * 64 : 0)));

@@ -4,9 +4,11 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -30,16 +32,42 @@ struct bzh_bases {
     uint32_t* d_xy29 = nullptr;
 };
 
+namespace bzh {
+// The six grow-only device workspaces of a ctx (ws_ensure).  Calls on a ctx are serialised and stream-ordered, so a slot is shared
+// by everything that names it, under two rules:
+//   WS_SCRATCH_A..C are LEAF scratch.  Their content is dead once the function that took the slot has enqueued its launches, and
+//   whoever holds data in one may call nothing that takes the same slot: msm_run / msm_run_paired take all three, ntt_run /
+//   ntt_run_padded above 2^11 and poly_batch_invert take A, the prefix scans and poly_kate_division take C.
+//   WS_STAGE, WS_IPA and WS_IPA_OUT live for a whole C ABI call.  No internal driver (msm_run*, ntt_run*, poly_*, lookup_permute)
+//   takes them, so their holder may call all of those, but not another holder of the same slot.
+enum WsSlot {
+    WS_SCRATCH_A = 0,   // MSM digits | multi-pass NTT scratch | batch inversion's prefix products | generators of a one-off table build
+    WS_SCRATCH_B = 1,   // MSM buckets | bzh_lookup_permute's working set | Pedersen operands | bzh_bases_read's canonical copy
+    WS_SCRATCH_C = 2,   // MSM window sums | tile totals of the scans and of the Kate division
+    WS_STAGE = 3,       // host staging: BZH_MEM_HOST operands and results of one C ABI call
+    WS_IPA = 4,         // the opening's vectors and collapsed tables | the batch check's scalars and sums
+    WS_IPA_OUT = 5,     // the opening's L / R points of a round
+    kWsSlots = 6
+};
+// The NTT domain tables of one ctx (csrc/ntt.hip), opaque here; ntt.hip creates the cache on first use and sets its deleter.
+struct NttCache;
+// serial number of a ctx: process-wide, never reused (what a key files its per-ctx workspace under, csrc/key_runtime.hpp)
+inline uint64_t next_ctx_serial() {
+    static std::atomic<uint64_t> next{1};
+    return next.fetch_add(1, std::memory_order_relaxed);
+}
+}  // namespace bzh
+
 struct bzh_ctx {
     int device = 0;
+    const uint64_t serial = bzh::next_ctx_serial();
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::mutex mu;
     std::string last_error;
     // grow-only device workspaces (calls on a ctx are serialised and stream-ordered)
-    static constexpr int kWsSlots = 6;  // 0-2 msm / scans, 3 host staging, 4-5 ipa
-    void* ws[kWsSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t ws_bytes[kWsSlots] = {0, 0, 0, 0, 0, 0};
+    void* ws[bzh::kWsSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // by bzh::WsSlot
+    size_t ws_bytes[bzh::kWsSlots] = {0, 0, 0, 0, 0, 0};
     // profiling
     bool profiling = false;
     struct Span {
@@ -68,6 +96,7 @@ struct bzh_ctx {
     uint32_t* ped_tbl = nullptr;   // bzh_pedersen_commit_batch's direct-lookup table of V and R (csrc/pedersen.hip), built on first use
     uint32_t* syn_tbl = nullptr;   // device synthesis' copy of the circuits' fixed-base window tables (csrc/synthesize_device.hip), on first use
     uint32_t* sqrt_tbl[4] = {nullptr, nullptr, nullptr, nullptr};   // per field: g^(2^i), i <= S, for the square root (csrc/sqrt_decompress.hip), on first use
+    std::unique_ptr<bzh::NttCache, void (*)(bzh::NttCache*)> ntt{nullptr, nullptr};   // the transforms' domain tables (csrc/ntt.hip), on first use
 };
 
 #define BZH_HIP_TRY(ctx, expr)                                                                    \
@@ -105,7 +134,7 @@ inline unsigned host_thread_budget() {
 }
 
 // grow-only workspace slot
-inline int ws_ensure(bzh_ctx* ctx, int slot, size_t bytes, void** out) {
+inline int ws_ensure(bzh_ctx* ctx, WsSlot slot, size_t bytes, void** out) {
     if (ctx->ws_bytes[slot] < bytes) {
         if (ctx->ws[slot]) {
             BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -154,11 +183,17 @@ inline int xfer_launch(bzh_ctx* ctx, void* dst, const void* src, size_t bytes, h
     BZH_HIP_TRY(ctx, hipGetLastError());
     return BZH_OK;
 }
-inline int pin_big_ensure(bzh_ctx* ctx, size_t bytes) {
-    if (ctx->pin_big_bytes >= bytes) return BZH_OK;
+// One stream synchronisation, then the staged results are handed to their destinations: afterwards nothing queued reads or
+// writes a pinned slot, so the buffers may be recycled or replaced.
+inline int pin_drain(bzh_ctx* ctx) {
     BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (auto& p : ctx->pending_d2h) memcpy(p.dst, p.slot, p.bytes);
     ctx->pending_d2h.clear();
+    return BZH_OK;
+}
+inline int pin_big_ensure(bzh_ctx* ctx, size_t bytes) {
+    if (ctx->pin_big_bytes >= bytes) return BZH_OK;
+    BZH_TRY(pin_drain(ctx));
     if (ctx->pin_big) BZH_HIP_TRY(ctx, hipHostFree(ctx->pin_big));
     ctx->pin_big = nullptr;
     ctx->pin_big_bytes = 0;
@@ -176,9 +211,7 @@ inline int pin_big_take(bzh_ctx* ctx, size_t bytes, char** out) {
         if (rc) return rc;
     }
     if (ctx->pin_big_off + need > ctx->pin_big_bytes) {
-        BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (auto& p : ctx->pending_d2h) memcpy(p.dst, p.slot, p.bytes);  // staged results leave before their slots are reused
-        ctx->pending_d2h.clear();
+        BZH_TRY(pin_drain(ctx));   // staged results leave before their slots are reused
         ctx->pin_big_off = 0;
     }
     *out = ctx->pin_big + ctx->pin_big_off;
@@ -191,9 +224,7 @@ inline int pin_big_reserve(bzh_ctx* ctx, size_t total) {
     int rc = pin_big_ensure(ctx, total);
     if (rc) return rc;
     if (ctx->pin_big_off + total > ctx->pin_big_bytes) {
-        BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (auto& p : ctx->pending_d2h) memcpy(p.dst, p.slot, p.bytes);
-        ctx->pending_d2h.clear();
+        BZH_TRY(pin_drain(ctx));
         ctx->pin_big_off = 0;
     }
     return BZH_OK;
@@ -207,9 +238,7 @@ inline int pin_ring_take(bzh_ctx* ctx, size_t bytes, char** out) {
     }
     const size_t need = (bytes + 255) & ~(size_t)255;
     if (ctx->pin_off + need > ctx->pin_bytes) {  // wrap: everything queued from the ring has to have landed
-        BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (auto& p : ctx->pending_d2h) memcpy(p.dst, p.slot, p.bytes);
-        ctx->pending_d2h.clear();
+        BZH_TRY(pin_drain(ctx));
         ctx->pin_off = 0;
     }
     *out = ctx->pin + ctx->pin_off;
@@ -241,13 +270,8 @@ inline int d2h_async(bzh_ctx* ctx, void* host_dst, const void* dev_src, size_t b
     ctx->pending_d2h.push_back({host_dst, slot, bytes});
     return BZH_OK;
 }
-// one stream synchronisation, then the staged results are handed to their destinations
-inline int d2h_finish(bzh_ctx* ctx) {
-    BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (auto& p : ctx->pending_d2h) memcpy(p.dst, p.slot, p.bytes);
-    ctx->pending_d2h.clear();
-    return BZH_OK;
-}
+// the end of a group of d2h_async: one stream synchronisation for any number of them
+inline int d2h_finish(bzh_ctx* ctx) { return pin_drain(ctx); }
 
 struct ScopedTimer {
     bzh_ctx* ctx;

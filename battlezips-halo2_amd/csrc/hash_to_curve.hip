@@ -180,10 +180,11 @@ static int run(bzh_ctx* ctx, int kind, const H2fPlan* pl, const void* in, uint32
         return hash_launch<C>(ctx, *pl, (const uint8_t*)d_in, kind == 1, first, n, form, d_out, d_st);
     };
     if (mem == BZH_MEM_DEVICE && status) return launch(in, (uint32_t*)out_xy, status);
-    // staged in workspace slot 3: input | affine points | status bytes (the first two only for host buffers)
+    // staged in WS_STAGE: input | affine points | status bytes (the first two only for host buffers); hash_launch takes no
+    // workspace slot
     const size_t ibytes = mem == BZH_MEM_HOST ? (in_bytes + 15) & ~(size_t)15 : 0, obytes = mem == BZH_MEM_HOST ? n * 64 : 0;
     void* ws = nullptr;
-    BZH_TRY(ws_ensure(ctx, 3, ibytes + obytes + n + 256, &ws));
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, ibytes + obytes + n + 256, &ws));
     const void* d_in = mem == BZH_MEM_HOST ? ws : in;
     uint32_t* d_out = mem == BZH_MEM_HOST ? (uint32_t*)((char*)ws + ibytes) : (uint32_t*)out_xy;
     uint8_t* d_st = (uint8_t*)ws + ibytes + obytes;

@@ -539,13 +539,13 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
     const size_t tail_m = jstar ? n >> jstar : 0;
     const int tail_nwin = (256 + tail_c - 1) / tail_c;
     const size_t tail_scratch = jstar ? msm_collapse_scratch_bytes(bases, (size_t)1 << jstar, B, tail_c) : 0;
-    // device arena (workspace slot 4), per proof: raw rng | rand scalars | s_poly | p x2 | b x2 | s x2 | LR | S scalars | small
-    // | the driver's own
+    // device arena (WS_IPA; the MSMs, the collapse and the poly_* calls of the rounds take WS_SCRATCH_* only), per proof:
+    // raw rng | rand scalars | s_poly | p x2 | b x2 | s x2 | LR | S scalars | small | the driver's own
     const size_t per = nrand * 16 + nrand * 8 + n * 8 + 2 * n * 8 + 2 * n * 8 + 2 * n * 8 + 2 * (n + 4) * 8 + (n + 2) * 8 +
                        (kHc + 4) * 8 + D::kExtraWords;
     const size_t tail_words = jstar ? B * (tail_m + 2) * (size_t)tail_nwin * (16 + 20) + (tail_scratch + 3) / 4 + 64 : 0;   // table + its fe29 copy
     void* arena = nullptr;
-    BZH_TRY(ws_ensure(ctx, 4, (B * per + tail_words) * 4 + 256 + 16 * 16, &arena));   // (+ the roundings of take())
+    BZH_TRY(ws_ensure(ctx, WS_IPA, (B * per + tail_words) * 4 + 256 + 16 * 16, &arena));   // (+ the roundings of take())
     uint32_t* cur = (uint32_t*)arena;
     auto take = [&](size_t w) {   // every piece starts 16-byte aligned (uint4 loads / stores): word counts rounded up to 4
         uint32_t* r = cur;
@@ -572,7 +572,7 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
     uint32_t* d_vlr = take(B * 2 * 8);  // value_l, value_r per proof
     uint32_t* d_extra = D::kExtraWords ? take(B * D::kExtraWords) : nullptr;
     void* d_out = nullptr;
-    BZH_TRY(ws_ensure(ctx, 5, 2 * B * 96, &d_out));
+    BZH_TRY(ws_ensure(ctx, WS_IPA_OUT, 2 * B * 96, &d_out));   // each round's MSM writes here: msm_run* take WS_SCRATCH_* only
     const IpaArena A{B, n, nrand, k, d_raw, d_rand, d_hc, d_dv, d_extra, (uint32_t*)d_out};
 
     const unsigned g256 = 256;
@@ -745,7 +745,7 @@ static int ipa_verify_t(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* co
     }
     BZH_HIP_TRY(ctx, hipMemsetAsync(s_cur + n * 8, 0, 64, st));  // no U / W contribution on the right
     void* d_out = nullptr;
-    BZH_TRY(ws_ensure(ctx, 3, 4 * 96, &d_out));
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, 4 * 96, &d_out));   // the MSMs' result points: msm_run takes WS_SCRATCH_* only (bzh_ipa_verify stages nothing else)
     BZH_TRY(msm_run(ctx, bases, s_cur, n + 2, 1, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
     uint64_t jac[24];
     BZH_HIP_TRY(ctx, hipMemcpyAsync(jac, d_out, 96, hipMemcpyDeviceToHost, st));
@@ -876,7 +876,7 @@ static int ipa_check_batch_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch,
     const size_t na = B * nl;  // every opening's own nl points and scalars, side by side
     const size_t words = B * (n + 2) * 8 + B * (k + 1) * 8 + na * 16 + na * 8 + 2 * B * 24 + 256;
     void* arena = nullptr;
-    BZH_TRY(ws_ensure(ctx, 4, words * 4, &arena));
+    BZH_TRY(ws_ensure(ctx, WS_IPA, words * 4, &arena));   // held across ipa_check_run_t's MSMs, which take WS_SCRATCH_* only
     uint32_t* d_s = (uint32_t*)arena;
     uint32_t* d_cu = d_s + B * (n + 2) * 8;
     uint32_t* d_pts = d_cu + B * (k + 1) * 8;
@@ -901,8 +901,8 @@ int ipa_check_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, s
     unsigned k = 0;
     while (((size_t)1 << k) < n) k++;
     if (((size_t)1 << k) != n || !B || !nl) return BZH_E_ARG;
-    void* arena = nullptr;   // workspace slot 4: the G'_0 scalars and the two sums per opening
-    BZH_TRY(ws_ensure(ctx, 4, (B * (n + 2) * 8 + 2 * B * 24 + 256) * 4, &arena));
+    void* arena = nullptr;   // WS_IPA: the G'_0 scalars and the two sums per opening, held across MSMs (WS_SCRATCH_* only)
+    BZH_TRY(ws_ensure(ctx, WS_IPA, (B * (n + 2) * 8 + 2 * B * 24 + 256) * 4, &arena));
     uint32_t* d_s = (uint32_t*)arena;
     uint32_t* d_out = d_s + B * (n + 2) * 8;
     return with_curve(bases->curve, [&](auto c) { return ipa_check_run_t<decltype(c)>(ctx, bases, B, nl, d_s, d_cu, d_pts, d_scal, d_out, ok); });

@@ -1,5 +1,5 @@
 // Part of the whole-proof translation unit (csrc/prove.hip): what the PROVING key and the VERIFYING key have in common -- the
-// circuit expressions as serialised, the blob reader, the registry keys, the device arena, and KeyShape: the constraint
+// circuit expressions as serialised, the blob reader, the registry keys, the runtime state (csrc/key_runtime.hpp), and KeyShape: the constraint
 // system's shape with the multiopen structure and the key's commitments, i.e. everything the verifier reads of a key.
 // bzh_pk derives from KeyShape, bzh_vk holds one.  Host code only; depends on host_field.hpp and the HIP runtime header (the
 // arena).  Included inside namespace bzh { namespace { (prove_kernels.cuh opens them; tests/helpers/vk_check.hip does the same).
@@ -21,76 +21,8 @@ enum { K_ADV = 1, K_FIX, K_INST, K_SIGMA, K_IDENT, K_PZ, K_LA, K_LS, K_LZ, K_MIS
 enum { M_L0, M_LLAST, M_LBLIND, M_X, M_TINV, M_AC, M_SC, M_A, M_S, M_ACC, M_Q, M_R, M_F, M_H0 /* + i */ };
 static inline uint64_t key(int kind, uint64_t i) { return ((uint64_t)kind << 32) | i; }
 
-// device arena: grow-only blocks, reset at the start of every call
-struct Arena {
-    struct Block {
-        char* p;
-        size_t size, used;
-    };
-    std::vector<Block> blocks;
-    int device = 0;
-    size_t live = 0, peak = 0;  // bytes handed out and not released since the last reset, and their high-water mark
-    // A call's allocation sequence is deterministic, so after the first call of a given shape the arena is ONE block
-    // that every later call bumps through without touching hipMalloc (overflow blocks are merged at the next reset).
-    void reset() {
-        if (blocks.size() > 1) {
-            const size_t want = peak + (peak >> 4) + ((size_t)1 << 20);
-            release();
-            Block nb;
-            nb.size = want;
-            nb.used = 0;
-            if (hipMalloc((void**)&nb.p, nb.size) == hipSuccess) blocks.push_back(nb);
-        }
-        for (auto& b : blocks) b.used = 0;
-        live = peak = 0;
-    }
-    void release() {
-        for (auto& b : blocks) (void)hipFree(b.p);
-        blocks.clear();
-    }
-    // device bytes the arena holds right now (bzh_pk_device_bytes / bzh_vk_device_bytes)
-    size_t held() const {
-        size_t s = 0;
-        for (auto& b : blocks) s += b.size;
-        return s;
-    }
-    void* alloc(size_t bytes) {
-        bytes = (bytes + 255) & ~(size_t)255;
-        live += bytes;
-        peak = std::max(peak, live);
-        for (auto& b : blocks)
-            if (b.size - b.used >= bytes) {
-                void* r = b.p + b.used;
-                b.used += bytes;
-                return r;
-            }
-        Block nb;
-        nb.size = std::max(bytes, (size_t)256 << 20);
-        if (hipMalloc((void**)&nb.p, nb.size) != hipSuccess) return nullptr;
-        nb.used = bytes;
-        blocks.push_back(nb);
-        return nb.p;
-    }
-    // Stack discipline for temporaries (a commitment's scalar vectors, gathered rows): everything allocated after mark() is
-    // handed back by pop().  Work on the buffers was enqueued on the ctx's one stream, so whatever reuses the memory runs
-    // after it.  While the arena is still a list of blocks (a key's first call) only the accounting moves: the merged block
-    // of the next call is sized by the high-water mark.
-    struct Mark {
-        size_t used, live;
-        bool single;
-    };
-    Mark mark() const { return Mark{blocks.size() == 1 ? blocks[0].used : 0, live, blocks.size() == 1}; }
-    void pop(const Mark& m) {
-        live = m.live;
-        if (m.single && blocks.size() == 1) blocks[0].used = m.used;
-    }
-};
-struct ArenaScope {
-    Arena& a;
-    Arena::Mark m;
-    explicit ArenaScope(Arena& ar) : a(ar), m(ar.mark()) {}
-    ~ArenaScope() { a.pop(m); }
-};
+// the device arena and the per-key runtime state (mutex, arenas, call count)
+#include "key_runtime.hpp"
 
 struct Reader {
     const uint8_t* p;

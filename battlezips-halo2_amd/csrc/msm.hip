@@ -1163,10 +1163,10 @@ static int msm_run_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_sca
     const bool acc_u29 = fe29_supported<typename C::Base>() && !acc_sat_env && bases->d_xy29 != nullptr;
     const size_t part_bytes = (size_t)2 * acc_threads * 128 + (acc_u29 ? ((size_t)M_acc + acc_threads) * 16 : 0);
     int rc;
-    if ((rc = ws_ensure(ctx, 0, slice * (size_t)p.nwin * n * sizeof(uint16_t), &d_digits))) return rc;
-    if ((rc = ws_ensure(ctx, 1, slice * segs_per_vec * (seg_bytes + part_bytes), &d_buckets))) return rc;
+    if ((rc = ws_ensure(ctx, WS_SCRATCH_A, slice * (size_t)p.nwin * n * sizeof(uint16_t), &d_digits))) return rc;
+    if ((rc = ws_ensure(ctx, WS_SCRATCH_B, slice * segs_per_vec * (seg_bytes + part_bytes), &d_buckets))) return rc;
     uint4* d_partials = (uint4*)((char*)d_buckets + slice * segs_per_vec * seg_bytes);
-    if ((rc = ws_ensure(ctx, 2, slice * segs_per_vec * nclass * 128, &d_winsums))) return rc;
+    if ((rc = ws_ensure(ctx, WS_SCRATCH_C, slice * segs_per_vec * nclass * 128, &d_winsums))) return rc;
 
     const size_t acc_lds = ((size_t)M_acc + 2 + 32 + acc_threads) * 4 + p.chunk * 2 + 16;
     int red_threads = p.M < 256 ? p.M : 256;

@@ -111,11 +111,12 @@ extern "C" int bzh_batch_normalize(bzh_ctx* ctx, int curve, const uint64_t* xyz,
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (mem == BZH_MEM_DEVICE && status) return normalize_run(ctx, curve, xyz, n, form, out_xy, out32, status);
-    // staged in workspace slot 3: Jacobian points | affine points | encodings | status bytes (the first three only for host buffers)
+    // staged in WS_STAGE: Jacobian points | affine points | encodings | status bytes (the first three only for host buffers);
+    // normalize_run takes no workspace slot
     const bool host = mem == BZH_MEM_HOST;
     const size_t ibytes = host ? n * 96 : 0, xbytes = host && out_xy ? n * 64 : 0, ebytes = host && out32 ? n * 32 : 0;
     void* ws = nullptr;
-    BZH_TRY(ws_ensure(ctx, 3, ibytes + xbytes + ebytes + n + 256, &ws));
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, ibytes + xbytes + ebytes + n + 256, &ws));
     char* const w = (char*)ws;
     const void* d_in = host ? ws : (const void*)xyz;
     void* d_xy = host ? (out_xy ? w + ibytes : nullptr) : (void*)out_xy;
@@ -150,8 +151,8 @@ extern "C" int bzh_affine_compress_batch(bzh_ctx* ctx, int curve, const uint64_t
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (mem == BZH_MEM_DEVICE) return compress_run(ctx, curve, (const uint32_t*)xy, n, form, (uint32_t*)out32);
-    void* ws = nullptr;   // workspace slot 3: affine points | encodings
-    BZH_TRY(ws_ensure(ctx, 3, n * 96, &ws));
+    void* ws = nullptr;   // WS_STAGE: affine points | encodings (compress_run takes no workspace slot)
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, n * 96, &ws));
     uint32_t* d_out = (uint32_t*)((char*)ws + n * 64);
     BZH_TRY(h2d_small(ctx, ws, xy, n * 64));
     BZH_TRY(compress_run(ctx, curve, (const uint32_t*)ws, n, form, d_out));

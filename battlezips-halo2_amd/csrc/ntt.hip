@@ -205,30 +205,15 @@ struct NttDomain {
     size_t off_direct[4];  // per non-final pass: omega^(A*row*j) (x n^-1 on pass 0 of a plain inverse), R x B; 0 = none
 };
 
+// owned by its ctx (bzh_ctx::ntt), which calls are serialised on
 struct NttCache {
     std::vector<NttDomain> doms;
+    ~NttCache() {
+        for (auto& d : doms)
+            if (d.d_tables) (void)hipFree(d.d_tables);
+    }
 };
-static std::mutex g_cache_mu;
-static std::vector<std::pair<bzh_ctx*, NttCache*>> g_caches;
-
-static NttCache* cache_for(bzh_ctx* ctx) {
-    std::lock_guard<std::mutex> lk(g_cache_mu);
-    for (auto& p : g_caches)
-        if (p.first == ctx) return p.second;
-    g_caches.emplace_back(ctx, new NttCache());
-    return g_caches.back().second;
-}
-void ntt_cache_drop(bzh_ctx* ctx) {
-    std::lock_guard<std::mutex> lk(g_cache_mu);
-    for (size_t i = 0; i < g_caches.size(); i++)
-        if (g_caches[i].first == ctx) {
-            for (auto& d : g_caches[i].second->doms)
-                if (d.d_tables) (void)hipFree(d.d_tables);
-            delete g_caches[i].second;
-            g_caches.erase(g_caches.begin() + i);
-            return;
-        }
-}
+static void ntt_cache_delete(NttCache* c) { delete c; }
 
 template <class P>
 static void fill_pows(std::vector<uint32_t>& out, size_t off, const Fe<P>& base, const Fe<P>& first, size_t count) {
@@ -352,7 +337,8 @@ static int ntt_run_t(bzh_ctx* ctx, uint32_t* d_data, unsigned log_n, size_t batc
         w = fe_to_mont(w);
         if (coset_shift) sh = fe_to_mont(sh);
     }
-    NttCache* cache = cache_for(ctx);
+    if (!ctx->ntt) ctx->ntt = {new NttCache(), ntt_cache_delete};
+    NttCache* cache = ctx->ntt.get();
     NttDomain* dom = nullptr;
     for (auto& d : cache->doms) {
         if (d.field == P::id && d.log_n == log_n && d.inverse == (inverse != 0) && d.has_shift == (coset_shift != nullptr) &&
@@ -401,7 +387,7 @@ static int ntt_run_t(bzh_ctx* ctx, uint32_t* d_data, unsigned log_n, size_t batc
     uint32_t* d_scratch = nullptr;
     if (np >= 2) {
         void* sp = nullptr;
-        int rc = ws_ensure(ctx, 0, total * 32, &sp);
+        int rc = ws_ensure(ctx, WS_SCRATCH_A, total * 32, &sp);   // leaf scratch: the passes below call nothing else that takes it
         if (rc) return rc;
         d_scratch = (uint32_t*)sp;
     }

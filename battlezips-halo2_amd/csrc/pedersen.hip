@@ -89,7 +89,7 @@ static int ensure_table(bzh_ctx* ctx) {
             memcpy(gens + b * 16 + c * 8, v.l, 32);
         }
     void* d_gens = nullptr;
-    int rc = ws_ensure(ctx, 0, sizeof(gens), &d_gens);
+    int rc = ws_ensure(ctx, WS_SCRATCH_A, sizeof(gens), &d_gens);   // leaf scratch: read by the one kernel below, no callee in between
     if (rc) return rc;
     if ((rc = h2d_small(ctx, d_gens, gens, sizeof(gens)))) return rc;
     uint32_t* tbl = nullptr;
@@ -119,7 +119,8 @@ extern "C" int bzh_pedersen_commit_batch(bzh_ctx* ctx, const uint64_t* messages,
     int rc = ensure_table(ctx);
     if (rc) return rc;
     void* ws = nullptr;
-    if ((rc = ws_ensure(ctx, 1, n * 128, &ws))) return rc;      // n x (64 B scalars in | 64 B point out)
+    // n x (64 B scalars in | 64 B point out).  Leaf scratch: the commit kernel and the read-back only, no MSM (ensure_table, above, is done)
+    if ((rc = ws_ensure(ctx, WS_SCRATCH_B, n * 128, &ws))) return rc;
     uint32_t *d_sc = (uint32_t*)ws, *d_out = (uint32_t*)ws + n * 16;
     char* slot = nullptr;
     if ((rc = h2d_stage(ctx, n * 64, &slot))) return rc;

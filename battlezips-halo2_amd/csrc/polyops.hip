@@ -224,7 +224,7 @@ template <class P>
 static int batch_invert_t(bzh_ctx* ctx, uint32_t* d, size_t count) {
     if (!count) return BZH_OK;
     void* tmp = nullptr;
-    int rc = ws_ensure(ctx, 0, count * 32, &tmp);
+    int rc = ws_ensure(ctx, WS_SCRATCH_A, count * 32, &tmp);   // leaf scratch: this launch only
     if (rc) return rc;
     size_t nthreads;
     if ((rc = bzh_batch_invert_plan(count, &nthreads))) return rc;
@@ -240,7 +240,7 @@ static int prefix_scan_t(bzh_ctx* ctx, uint32_t* d, size_t n, size_t batch) {
     if (!n || !batch) return BZH_OK;
     const size_t tiles = (n + kScanTile - 1) / kScanTile;
     void* tot = nullptr;
-    int rc = ws_ensure(ctx, 2, tiles * batch * 32, &tot);
+    int rc = ws_ensure(ctx, WS_SCRATCH_C, tiles * batch * 32, &tot);   // leaf scratch: the scan's own launches only
     if (rc) return rc;
     ScopedTimer t(ctx, BZH_T_POLY);
     for (size_t b0 = 0; b0 < batch; b0 += 65535) {
@@ -363,7 +363,7 @@ static int kate_t(bzh_ctx* ctx, const uint32_t* d_c, size_t n, size_t batch, con
     int rc = bzh_kate_division_plan(n, batch, &threads, &L, &S);  // refuses batch > 65535 (the grid's y extent)
     if (rc) return rc;
     void* tot = nullptr;
-    if (S > 1 && (rc = ws_ensure(ctx, 2, (S - 1) * batch * 32, &tot))) return rc;
+    if (S > 1 && (rc = ws_ensure(ctx, WS_SCRATCH_C, (S - 1) * batch * 32, &tot))) return rc;   // leaf scratch: the two launches below only
     ScopedTimer t(ctx, BZH_T_POLY);
     if (S > 1)
         hipLaunchKernelGGL((k_kate_span_totals<P>), dim3((unsigned)(S - 1), (unsigned)batch), dim3(kVecThreads), 0, ctx->stream, d_c, n, d_xs,

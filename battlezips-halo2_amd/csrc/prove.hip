@@ -61,9 +61,9 @@ extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __at
 // pk.get_vk(): the commitments to the fixed and permutation polynomials (blind 1), computed once per key
 template <class C>
 static int pk_fill_vk(bzh_ctx* ctx, bzh_pk* pk) {
-    std::lock_guard<std::mutex> lkv(pk->mu);
+    Arena& arena = pk->rt.arena_for(ctx->serial, ctx->device);   // (before the lock below: arena_for takes it)
+    std::lock_guard<std::mutex> lkv(pk->rt.mu);
     if (pk->vk_ready) return BZH_OK;
-    Arena& arena = *pk->arenas[ctx];   // (the caller made it: arena_for)
     ColumnCommitter<C> cc(ctx, *pk, arena);
     BZH_TRY(cc.commit(pk->srs, pk->fixed_polys, (size_t)pk->nf, pk->fixed_commitments));
     BZH_TRY(cc.commit(pk->srs, pk->sigma_polys, pk->perm_columns.size(), pk->sigma_commitments));
@@ -161,22 +161,6 @@ static int quotient_histogram_t(const uint8_t* circuit, size_t circuit_len, uint
 
 
 namespace {
-// one prove / verify call on a key (bzh_pk or bzh_vk): counted for the whole call, so that bzh_pk_set_quotient_module /
-// bzh_pk_free / bzh_vk_free can refuse
-template <class Key>
-struct KeyCallOf {
-    Key* pk;
-    explicit KeyCallOf(Key* p) : pk(p) {
-        std::lock_guard<std::mutex> lk(pk->mu);
-        pk->calls_in_flight++;
-    }
-    ~KeyCallOf() {
-        std::lock_guard<std::mutex> lk(pk->mu);
-        pk->calls_in_flight--;
-    }
-};
-using KeyCall = KeyCallOf<bzh_pk>;
-
 // G_0, U, W of a table (g | u | w), canonical affine: row 0 of a window table is the raw table
 static int srs_g0_u_w(bzh_ctx* ctx, const bzh_bases* srs, std::vector<uint64_t>& canon) {
     uint64_t m[3 * 8];
@@ -206,20 +190,17 @@ int bzh_pk_create(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* circuit, si
 int bzh_pk_free(bzh_ctx* ctx, bzh_pk* pk) {
     if (!ctx || !pk) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    {
-        std::lock_guard<std::mutex> lkp(pk->mu);
-        if (pk->calls_in_flight) {   // another ctx is proving / verifying on this key: its arena and code would vanish under it
-            ctx->last_error = "bzh_pk_free: a bzh_prove_batch / bzh_verify_batch call on this key is still running";
-            return BZH_E_ARG;
-        }
+    if (!pk->rt.retire()) {   // another ctx is proving / verifying on this key: its arena and code would vanish under it
+        ctx->last_error = "bzh_pk_free: a bzh_prove_batch / bzh_verify_batch call on this key is still running";
+        return BZH_E_ARG;
     }
-    (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();   // every ctx's stream: the arenas below belong to all of them
+    // (retire has synchronised every device the key holds a workspace on; a key without one has run no call, and
+    // bzh_pk_create waited for its own work: nothing queued reads what goes now)
+    (void)hipSetDevice(pk->device);
     if (pk->dev) (void)hipFree(pk->dev);
     if (pk->hoist) (void)hipFree(pk->hoist);
     if (pk->key29) (void)hipFree(pk->key29);
     if (pk->q_module) (void)hipModuleUnload(pk->q_module);
-    for (auto& kv : pk->arenas) kv.second->release();
     delete pk;
     return BZH_OK;
 }
@@ -228,7 +209,7 @@ int bzh_pk_set_lagrange(bzh_pk* pk, const bzh_bases* g_lagrange) {
     if (!pk) return BZH_E_ARG;
     if (g_lagrange && ((g_lagrange->n != pk->n + 2 && g_lagrange->n != pk->n + 3) || g_lagrange->curve != pk->curve || g_lagrange->device != pk->device || !g_lagrange->pre_c))
         return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(pk->mu);
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
     pk->srs_lagrange = g_lagrange;
     return BZH_OK;
 }
@@ -326,7 +307,7 @@ int bzh_quotient_degree_histogram(int curve, const uint8_t* circuit, size_t circ
 
 int bzh_pk_quotient_select(bzh_pk* pk, int flavour) {
     if (!pk) return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(pk->mu);
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
     switch (flavour) {
         case BZH_QUOTIENT_INTERPRETER: break;
         case BZH_QUOTIENT_BUILTIN:
@@ -343,7 +324,7 @@ int bzh_pk_quotient_select(bzh_pk* pk, int flavour) {
 
 int bzh_pk_quotient_selected(bzh_pk* pk, int* flavour, int* builtin_available) {
     if (!pk) return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(pk->mu);
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
     if (flavour) *flavour = pk->q_select;
     if (builtin_available) *builtin_available = pk->q_builtin != nullptr;
     return BZH_OK;
@@ -351,7 +332,7 @@ int bzh_pk_quotient_selected(bzh_pk* pk, int* flavour, int* builtin_available) {
 
 int bzh_pk_lookup_select(bzh_pk* pk, int where) {
     if (!pk || (where != BZH_LOOKUP_HOST && where != BZH_LOOKUP_DEVICE)) return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(pk->mu);
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
     pk->lk_select = where;
     pk->lk_chosen = true;
     return BZH_OK;
@@ -359,35 +340,35 @@ int bzh_pk_lookup_select(bzh_pk* pk, int where) {
 
 int bzh_pk_lookup_selected(bzh_pk* pk, int* where) {
     if (!pk) return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(pk->mu);
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
     if (where) *where = pk->lk_select;
     return BZH_OK;
 }
 
 int bzh_pk_verify_select(bzh_pk* pk, int where) {
     if (!pk || (where != BZH_VERIFY_POINTS_HOST && where != BZH_VERIFY_POINTS_DEVICE)) return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(pk->mu);
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
     pk->vp_select = where;
     return BZH_OK;
 }
 
 int bzh_pk_verify_selected(bzh_pk* pk, int* where) {
     if (!pk) return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(pk->mu);
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
     if (where) *where = pk->vp_select;
     return BZH_OK;
 }
 
 int bzh_pk_verify_pass_select(bzh_pk* pk, int where) {
     if (!pk || (where != BZH_VERIFY_PASS_HOST && where != BZH_VERIFY_PASS_DEVICE)) return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(pk->mu);
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
     pk->vpass_select = where;
     return BZH_OK;
 }
 
 int bzh_pk_verify_pass_selected(bzh_pk* pk, int* where) {
     if (!pk) return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(pk->mu);
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
     if (where) *where = pk->vpass_select;
     return BZH_OK;
 }
@@ -395,9 +376,9 @@ int bzh_pk_verify_pass_selected(bzh_pk* pk, int* where) {
 int bzh_pk_set_quotient_module(bzh_ctx* ctx, bzh_pk* pk, const void* code_object, size_t len) {
     if (!ctx || !pk || pk->device != ctx->device) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    std::lock_guard<std::mutex> lkp(pk->mu);
+    std::lock_guard<std::mutex> lkp(pk->rt.mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (pk->calls_in_flight) {   // a call on another ctx may hold q_fn and be about to launch it
+    if (pk->rt.calls) {   // a call on another ctx may hold q_fn and be about to launch it
         ctx->last_error = "bzh_pk_set_quotient_module: a bzh_prove_batch / bzh_verify_batch call on this key is still running";
         return BZH_E_ARG;
     }
@@ -451,15 +432,15 @@ int bzh_pk_vk_repr(const bzh_pk* pk, uint8_t* out_repr32, int* is_placeholder) {
 int bzh_verify_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* instances, size_t instance_rows, const uint8_t* proofs,
                      size_t proof_stride, const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
     if (!ctx || !pk || !batch || batch > 4096 || !proofs || !proof_lens || !g0_u_w || !results) return BZH_E_ARG;
+    bzh::KeyRuntime::Call in_flight(pk->rt);   // registered before the wait for ctx->mu: a queued call already makes bzh_pk_free refuse
     if (pk->device != ctx->device || (pk->ni && instance_rows && !instances) || instance_rows > pk->usable) return BZH_E_ARG;
     for (size_t b = 0; b < batch; b++)
         if (proof_lens[b] > proof_stride) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    KeyCall in_flight(pk);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // The commitments of the key and G'_0 are computed against pk->srs: the three points the caller passes must be the
     // same SRS's, or every valid proof would be rejected without an error.  Row 0 of the window table is the raw SRS.
-    std::unique_lock<std::mutex> lkp(pk->mu);
+    std::unique_lock<std::mutex> lkp(pk->rt.mu);
     if (pk->srs_g0_u_w.empty()) {
         std::vector<uint64_t> canon;
         BZH_TRY(srs_g0_u_w(ctx, pk->srs, canon));
@@ -472,7 +453,7 @@ int bzh_verify_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* ins
     const bool points_on_device = pk->vp_select == BZH_VERIFY_POINTS_DEVICE;
     const bool pass_on_device = pk->vpass_select == BZH_VERIFY_PASS_DEVICE;
     lkp.unlock();
-    bzh::Arena& arena = pk->arena_for(ctx, ctx->device);
+    bzh::Arena& arena = pk->rt.arena_for(ctx->serial, ctx->device);
     const int rc = bzh::with_pasta_curve(pk->curve, [&](auto c) {
         using C = decltype(c);
         arena.reset();
@@ -489,11 +470,9 @@ int bzh_verify_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* ins
 
 int bzh_pk_device_bytes(const bzh_pk* pk, size_t* key_bytes, size_t* workspace_bytes) {
     if (!pk) return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(const_cast<bzh_pk*>(pk)->mu);
+    std::lock_guard<std::mutex> lk(const_cast<bzh_pk*>(pk)->rt.mu);
     if (key_bytes) *key_bytes = pk->dev_bytes + pk->hoist_bytes + pk->key29_bytes;
-    size_t ws = 0;
-    for (auto& kv : pk->arenas) ws += kv.second->held();
-    if (workspace_bytes) *workspace_bytes = ws;
+    if (workspace_bytes) *workspace_bytes = pk->rt.held_locked();
     return BZH_OK;
 }
 
@@ -505,11 +484,12 @@ int bzh_vk_create(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* circuit, si
 }
 
 int bzh_vk_from_pk(bzh_ctx* ctx, bzh_pk* pk, bzh_vk** out) {
-    if (!ctx || !pk || !out || pk->device != ctx->device) return BZH_E_ARG;
+    if (!ctx || !pk || !out) return BZH_E_ARG;
+    bzh::KeyRuntime::Call in_flight(pk->rt);
+    if (pk->device != ctx->device) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    KeyCall in_flight(pk);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    bzh::Arena& arena = pk->arena_for(ctx, ctx->device);
+    bzh::Arena& arena = pk->rt.arena_for(ctx->serial, ctx->device);
     BZH_TRY(bzh::with_pasta_curve(pk->curve, [&](auto c) {
         arena.reset();
         return bzh::pk_fill_vk<decltype(c)>(ctx, pk);
@@ -533,6 +513,7 @@ int bzh_verify_batch_vk_with(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* sr
                              const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
     if (pass_where != BZH_VERIFY_PASS_HOST && pass_where != BZH_VERIFY_PASS_DEVICE) return BZH_E_ARG;
     if (!ctx || !vk || !srs || !batch || batch > 4096 || !proofs || !proof_lens || !g0_u_w || !results) return BZH_E_ARG;
+    bzh::KeyRuntime::Call in_flight(vk->rt);
     const bzh::KeyShape& key = vk->shape;
     if (srs->device != ctx->device || srs->curve != key.curve || srs->n != key.n + 2) return BZH_E_ARG;
     if (g_lagrange && (g_lagrange->device != ctx->device || g_lagrange->curve != key.curve || (g_lagrange->n != key.n + 2 && g_lagrange->n != key.n + 3)))
@@ -541,7 +522,6 @@ int bzh_verify_batch_vk_with(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* sr
     for (size_t b = 0; b < batch; b++)
         if (proof_lens[b] > proof_stride) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    KeyCallOf<const bzh_vk> in_flight(vk);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // the key's commitments and G'_0 belong to one SRS: the three points the caller passes must be that table's
     std::vector<uint64_t> canon;
@@ -550,7 +530,7 @@ int bzh_verify_batch_vk_with(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* sr
         ctx->last_error = "bzh_verify_batch_vk: g0_u_w are not G_0, U, W of srs";
         return BZH_E_ARG;
     }
-    bzh::Arena& arena = vk->arena_for(ctx, ctx->device);
+    bzh::Arena& arena = vk->rt.arena_for(ctx->serial, ctx->device);
     const int rc = bzh::with_pasta_curve(key.curve, [&](auto c) {
         if (pass_where == BZH_VERIFY_PASS_DEVICE)
             return bzh::verify_batch_device_t<decltype(c)>(ctx, key, srs, g_lagrange, arena, batch, instances, instance_rows, proofs, proof_stride,
@@ -567,19 +547,19 @@ static int prove_batch_entry(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint6
                              size_t instance_rows, const uint8_t* rng, size_t rng_stride, uint8_t* proofs, size_t proof_stride,
                              size_t* proof_lens) {
     if (!ctx || !pk || !batch || batch > 4096 || !advice || !rng || !proofs || !proof_lens) return BZH_E_ARG;
+    bzh::KeyRuntime::Call in_flight(pk->rt);   // until the proofs are in the caller's buffers (prove_batch_t synchronises the stream before it returns)
     if ((form != BZH_FORM_CANONICAL && form != BZH_FORM_MONTGOMERY) || (mem != BZH_MEM_HOST && mem != BZH_MEM_DEVICE)) return BZH_E_ARG;
     if (pk->device != ctx->device || (rng_stride != 0 && rng_stride < pk->rng_bytes) || (pk->ni && instance_rows && !instances) ||
         instance_rows > pk->usable)
         return BZH_E_ARG;
     if (mem == BZH_MEM_DEVICE && form != BZH_FORM_MONTGOMERY) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    KeyCall in_flight(pk);   // until the proofs are in the caller's buffers (prove_batch_t synchronises the stream before it returns)
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t* d_adv = (const uint32_t*)advice;
     void* staged = nullptr;
     const size_t elems = batch * (size_t)pk->na * pk->n;
     if (mem == BZH_MEM_HOST) {
-        int rc = bzh::ws_ensure(ctx, 3, elems * 32 + 256, &staged);
+        int rc = bzh::ws_ensure(ctx, bzh::WS_STAGE, elems * 32 + 256, &staged);
         if (rc) return rc;
         BZH_HIP_TRY(ctx, hipMemcpyAsync(staged, advice, elems * 32, hipMemcpyHostToDevice, ctx->stream));
         if (form == BZH_FORM_CANONICAL && (rc = bzh::field_convert(ctx, pk->field, (uint32_t*)staged, elems, 1))) return rc;

@@ -86,7 +86,7 @@ struct Prover : DeviceColumns<C> {
     // (9 words per element, ntt_store_out) and no saturated copy is ever made.
     const bool q29 = [&] {
         if constexpr (!fe29_supported<SF>()) return false;
-        std::lock_guard<std::mutex> lk(pk.mu);
+        std::lock_guard<std::mutex> lk(pk.rt.mu);
         return pk.q_ok && pk.q_builtin29 && pk.key29 && pk.q_select == BZH_QUOTIENT_BUILTIN && pk.en % 128 == 0 && pk.ek >= 12 &&
                pk.ek <= 27 /* 32-bit byte offsets into a plane (fe29_load_planes_g) */ && !getenv("BZH_QUOTIENT_V1");
     }();
@@ -237,7 +237,7 @@ struct Prover : DeviceColumns<C> {
     int run(uint64_t pkey, Build build, const Cols& reg, size_t size, uint32_t* d_out) {
         const Program* pgp = nullptr;
         {
-            std::lock_guard<std::mutex> lk(pk.mu);   // map nodes are stable: the program outlives the lock
+            std::lock_guard<std::mutex> lk(pk.rt.mu);   // map nodes are stable: the program outlives the lock
             auto it = pk.progs.find(pkey);
             if (it == pk.progs.end()) {
                 EPool ep;
@@ -280,7 +280,7 @@ struct Prover : DeviceColumns<C> {
         if (q29) {
             q_builtin = pk.q_builtin29;
         } else {
-            std::lock_guard<std::mutex> lk(pk.mu);
+            std::lock_guard<std::mutex> lk(pk.rt.mu);
             if (pk.q_select == BZH_QUOTIENT_MODULE) q_fn = pk.q_fn;
             else if (pk.q_select == BZH_QUOTIENT_BUILTIN) q_builtin = pk.q_builtin;
         }
@@ -500,7 +500,7 @@ struct Prover : DeviceColumns<C> {
     // reads adv, inst, env[SY_THETA]; fills lk (all but the cosets), inst_cosets, adv_cosets, env[SY_BETA], env[SY_GAMMA]
     int lookups() {
         const bool lk_device = [&] {
-            std::lock_guard<std::mutex> g(pk.mu);
+            std::lock_guard<std::mutex> g(pk.rt.mu);
             if (!pk.lk_chosen) return B >= kLookupDeviceMinBatch;
             return pk.lk_select == BZH_LOOKUP_DEVICE;
         }();
@@ -1091,7 +1091,7 @@ struct Prover : DeviceColumns<C> {
 template <class C>
 static int prove_batch_t(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint32_t* d_advice, const uint64_t* instances, size_t inst_rows,
                          const uint8_t* rng, size_t rng_stride, uint8_t* proofs, size_t proof_stride, size_t* proof_lens) {
-    Arena& arena = pk->arena_for(ctx, ctx->device);
+    Arena& arena = pk->rt.arena_for(ctx->serial, ctx->device);
     arena.reset();
     Prover<C> pv(ctx, *pk, batch, arena);
     if (rng_stride == 0) {  // seeded: rng holds batch x 32 bytes

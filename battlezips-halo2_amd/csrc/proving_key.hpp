@@ -48,30 +48,17 @@ struct bzh_pk : bzh::KeyShape {
     bool lk_chosen = false;   // bzh_pk_lookup_select was called: lk_select holds for every batch size (else see kLookupDeviceMinBatch, prover.hpp)
     int vpass_select = BZH_VERIFY_PASS_HOST;  // BZH_VERIFY_PASS_*: where bzh_verify_batch runs the per-proof pass (bzh_pk_verify_pass_select)
     int vp_select = BZH_VERIFY_POINTS_HOST;   // BZH_VERIFY_POINTS_*: where bzh_verify_batch decompresses the proofs' points (bzh_pk_verify_select)
-    // per-call workspaces: one grow-only arena per ctx that has used the key (several worker streams share ONE key)
-    std::map<const bzh_ctx*, std::unique_ptr<bzh::Arena>> arenas;
     size_t rng_bytes = 0;
-    // bzh_prove_batch / bzh_verify_batch calls running on this key right now, over all ctxs (guarded by `mu`):
-    // bzh_pk_set_quotient_module and bzh_pk_free refuse while it is non-zero -- they unload code / free arenas that a
-    // call on ANOTHER ctx may be launching from
-    int calls_in_flight = 0;
     // verifying key: the KeyShape's commitments to the fixed and permutation polynomials are computed at the first verification
     bool vk_ready = false;
     // the constraint-system part of the blob the key was made from, as bzh_vk keeps it (csrc/verifying_key.hpp)
     std::vector<uint8_t> cs_bytes;
     // The key is immutable after bzh_pk_create except for caches filled on first use (programs, hoisted columns, the vk
-    // commitments, G_0/U/W, the quotient module, the arena map): `mu` guards those in short sections.  Calls through different
-    // ctxs run concurrently on one key; a call holds its ctx's mutex throughout (lock order: ctx->mu, then pk->mu).
-    std::mutex mu;
-    bzh::Arena& arena_for(const bzh_ctx* ctx, int dev) {
-        std::lock_guard<std::mutex> lk(mu);
-        auto& a = arenas[ctx];
-        if (!a) {
-            a.reset(new bzh::Arena());
-            a->device = dev;
-        }
-        return *a;
-    }
+    // commitments, G_0/U/W, the quotient module) and the runtime state: `rt.mu` guards those in short sections.  Calls through
+    // different ctxs run concurrently on one key; a call holds its ctx's mutex throughout (lock order: ctx->mu, then pk->rt.mu).
+    // rt: the per-(key, ctx) workspaces and the count of running calls -- bzh_pk_set_quotient_module and bzh_pk_free refuse while
+    // it is non-zero: they unload code / free arenas that a call on ANOTHER ctx may be launching from.
+    bzh::KeyRuntime rt;
 };
 
 namespace bzh {

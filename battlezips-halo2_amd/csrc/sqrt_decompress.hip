@@ -172,10 +172,10 @@ extern "C" int bzh_batch_sqrt(bzh_ctx* ctx, int field, uint64_t* data, size_t co
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (mem == BZH_MEM_DEVICE && status) return batch_sqrt_run(ctx, field, (uint32_t*)data, count, form, status);
-    // the statuses come back to the host: staged in workspace slot 3, elements | status bytes
+    // the statuses come back to the host: staged in WS_STAGE, elements | status bytes (batch_sqrt_run takes no workspace slot)
     const size_t ebytes = mem == BZH_MEM_HOST ? count * 32 : 0;
     void* ws = nullptr;
-    BZH_TRY(ws_ensure(ctx, 3, ebytes + count + 256, &ws));
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, ebytes + count + 256, &ws));
     uint32_t* d = mem == BZH_MEM_HOST ? (uint32_t*)ws : (uint32_t*)data;
     uint8_t* d_st = (uint8_t*)ws + ebytes;
     if (mem == BZH_MEM_HOST) BZH_TRY(h2d_small(ctx, d, data, count * 32));
@@ -210,10 +210,11 @@ extern "C" int bzh_affine_decompress(bzh_ctx* ctx, int curve, const uint8_t* in3
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (mem == BZH_MEM_DEVICE && status) return decompress_run(ctx, curve, (const uint32_t*)in32, n, form, (uint32_t*)out_xy, status);
-    // staged in workspace slot 3: compressed points | affine points | status bytes (the first two only for host buffers)
+    // staged in WS_STAGE: compressed points | affine points | status bytes (the first two only for host buffers); decompress_run
+    // takes no workspace slot
     const size_t ibytes = mem == BZH_MEM_HOST ? n * 32 : 0, obytes = mem == BZH_MEM_HOST ? n * 64 : 0;
     void* ws = nullptr;
-    BZH_TRY(ws_ensure(ctx, 3, ibytes + obytes + n + 256, &ws));
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, ibytes + obytes + n + 256, &ws));
     const uint32_t* d_in = mem == BZH_MEM_HOST ? (const uint32_t*)ws : (const uint32_t*)in32;
     uint32_t* d_out = mem == BZH_MEM_HOST ? (uint32_t*)((char*)ws + ibytes) : (uint32_t*)out_xy;
     uint8_t* d_st = (uint8_t*)ws + ibytes + obytes;

@@ -94,12 +94,13 @@ int synth_device_run(bzh_ctx* ctx, const SynRun& run) {
         }
         ctx->syn_tbl = tbl;
     }
-    // workspace: layout | inputs | flags (2 per proof) | status (1 per proof) | commitments (16 words per proof)
+    // WS_STAGE: layout | inputs | flags (2 per proof) | status (1 per proof) | commitments (16 words per proof); the synthesis
+    // kernels below are all that runs while it is held
     const size_t o_in = up16(sizeof(SynLayout)), in_bytes = batch * L.in_words * 8, o_flags = o_in + up16(in_bytes);
     const size_t o_status = o_flags + up16(batch * 8), status_bytes = up16(batch * 4), o_inst = o_status + status_bytes;
     const size_t rb_bytes = status_bytes + batch * 64, total = o_inst + batch * 64;
     void* ws = nullptr;
-    BZH_TRY(ws_ensure(ctx, 3, total, &ws));
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, total, &ws));
     char* d = (char*)ws;
     char* slot = nullptr;
     BZH_TRY(h2d_stage(ctx, o_flags, &slot));

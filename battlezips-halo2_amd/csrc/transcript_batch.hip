@@ -159,10 +159,10 @@ static int absorb(bzh_transcript_batch* tb, const uint64_t* p, size_t count, siz
         std::lock_guard<std::mutex> lk(ctx->mu);
         BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
         const void* d_base = p;
-        if (mem == BZH_MEM_HOST) {   // staged in workspace slot 3, the items side by side
+        if (mem == BZH_MEM_HOST) {   // staged in WS_STAGE, the items side by side (absorb_launch takes no workspace slot)
             const std::vector<uint8_t> v = compact(p, tb->batch, count, stride, item);
             void* ws = nullptr;
-            BZH_TRY(ws_ensure(ctx, 3, v.size() + 256, &ws));
+            BZH_TRY(ws_ensure(ctx, WS_STAGE, v.size() + 256, &ws));
             BZH_TRY(h2d_small(ctx, ws, v.data(), v.size()));
             d_base = ws;
             stride = count;
@@ -370,10 +370,10 @@ extern "C" int bzh_transcript_batch_write_jacobian(bzh_transcript_batch* tb, con
         std::lock_guard<std::mutex> lk(ctx->mu);
         BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
         const void* d_in = xyz;
-        if (host) {   // staged in workspace slot 3
+        if (host) {   // staged in WS_STAGE (tb_write_jacobian_locked takes no workspace slot)
             const std::vector<uint8_t> jac = compact(xyz, tb->batch, count, stride, 96);
             void* ws = nullptr;
-            BZH_TRY(ws_ensure(ctx, 3, jac.size() + 256, &ws));
+            BZH_TRY(ws_ensure(ctx, WS_STAGE, jac.size() + 256, &ws));
             BZH_TRY(h2d_small(ctx, ws, jac.data(), jac.size()));
             d_in = ws;
         }
@@ -400,7 +400,7 @@ extern "C" int bzh_transcript_batch_squeeze(bzh_transcript_batch* tb, int form, 
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     void* d_out = out;
-    if (mem == BZH_MEM_HOST) BZH_TRY(ws_ensure(ctx, 3, tb->batch * 32 + 256, &d_out));
+    if (mem == BZH_MEM_HOST) BZH_TRY(ws_ensure(ctx, WS_STAGE, tb->batch * 32 + 256, &d_out));   // the squeeze kernel and its read-back only
     BZH_TRY(with_curve(tb->curve, [&](auto c) -> int {
         {
             ScopedTimer tm(ctx, BZH_T_POLY);

@@ -34,20 +34,9 @@
 struct bzh_vk {
     bzh::KeyShape shape;
     std::vector<uint8_t> cs;   // the constraint-system bytes
-    // the only mutable state: per-call device workspaces, one per ctx that has verified on the key, and the count of running
-    // calls (bzh_vk_free refuses while it is non-zero); guarded by `mu`
-    mutable std::mutex mu;
-    mutable std::map<const bzh_ctx*, std::unique_ptr<bzh::Arena>> arenas;
-    mutable int calls_in_flight = 0;
-    bzh::Arena& arena_for(const bzh_ctx* ctx, int dev) const {
-        std::lock_guard<std::mutex> lk(mu);
-        auto& a = arenas[ctx];
-        if (!a) {
-            a.reset(new bzh::Arena());
-            a->device = dev;
-        }
-        return *a;
-    }
+    // the only mutable state (csrc/key_runtime.hpp): per-call device workspaces, one per ctx that has verified on the key, and the
+    // count of running calls (bzh_vk_free refuses while it is non-zero)
+    mutable bzh::KeyRuntime rt;
 };
 
 namespace bzh {
@@ -204,26 +193,15 @@ int bzh_vk_vk_repr(const bzh_vk* vk, uint8_t* out_repr32, int* is_placeholder) {
 
 int bzh_vk_device_bytes(const bzh_vk* vk, size_t* key_bytes, size_t* workspace_bytes) {
     if (!vk) return BZH_E_ARG;
-    std::lock_guard<std::mutex> lk(vk->mu);
+    std::lock_guard<std::mutex> lk(vk->rt.mu);
     if (key_bytes) *key_bytes = 0;   // a bzh_vk has no member that could hold a device pointer
-    size_t ws = 0;
-    for (auto& kv : vk->arenas) ws += kv.second->held();
-    if (workspace_bytes) *workspace_bytes = ws;
+    if (workspace_bytes) *workspace_bytes = vk->rt.held_locked();
     return BZH_OK;
 }
 
 int bzh_vk_free(bzh_vk* vk) {
     if (!vk) return BZH_E_ARG;
-    {
-        std::lock_guard<std::mutex> lk(vk->mu);
-        if (vk->calls_in_flight) return BZH_E_ARG;   // a bzh_verify_batch_vk is running out of one of the workspaces below
-    }
-    for (auto& kv : vk->arenas) {
-        if (kv.second->blocks.empty()) continue;
-        (void)hipSetDevice(kv.second->device);
-        (void)hipDeviceSynchronize();
-        kv.second->release();
-    }
+    if (!vk->rt.retire()) return BZH_E_ARG;   // a bzh_verify_batch_vk is running out of one of the key's workspaces
     delete vk;
     return BZH_OK;
 }

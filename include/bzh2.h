@@ -343,8 +343,10 @@ int bzh_ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitm
  *                  inside the library.  Calls through one ctx are serialised as everywhere else.
  *                  bzh_pk_free and bzh_pk_set_quotient_module change what those calls run on (workspaces of every ctx, the
  *                  loaded code object): both return BZH_E_ARG, leaving the key as it was, while a bzh_prove_batch /
- *                  bzh_verify_batch on the key is still running on any ctx, and synchronise the whole device before they
- *                  release anything.  Join the proving threads first. */
+ *                  bzh_verify_batch / bzh_vk_from_pk on the key has started on any ctx and not returned -- a call counts from
+ *                  its entry into the library, also while it waits for its ctx -- and synchronise every device the key has a
+ *                  workspace on before they release anything.  Starting a call on a key after its bzh_pk_free has returned
+ *                  BZH_OK is the caller's error: join the proving threads first. */
 typedef struct bzh_pk bzh_pk;
 /* THE VERIFYING-KEY DIGEST.  The first thing upstream's create_proof and verify_proof absorb is pk.get_vk().hash_into(transcript)
  * (halo2_proofs 0.2.0 plonk.rs, UPSTREAM; the keys come from keygen_vk / keygen_pk at benches/shot.rs:59-61,
@@ -490,7 +492,9 @@ int bzh_prove_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advi
  *                        the library's own bookkeeping of device memory held under a key: *key_bytes = allocations that live as
  *                        long as the key (always 0 for a bzh_vk; columns, cosets, hoisted and fe29 columns for a bzh_pk),
  *                        *workspace_bytes = the per-(key, ctx) workspaces calls have grown so far.  Either may be NULL.
- *   bzh_vk_free          BZH_E_ARG, leaving the key as it was, while a bzh_verify_batch_vk on it is still running.
+ *   bzh_vk_free          BZH_E_ARG, leaving the key as it was, while a bzh_verify_batch_vk on it has started (a call counts from
+ *                        its entry into the library, also while it waits for its ctx) and not returned.  Starting a call on a
+ *                        key after its bzh_vk_free has returned BZH_OK is the caller's error.
  *   bzh_verify_batch_vk  bzh_verify_batch with the key and the SRS apart.  srs: (g | u | w) with its window table; g_lagrange:
  *                        (g_lagrange | u | w) or NULL; the other arguments and results[] exactly as bzh_verify_batch; g0_u_w is
  *                        checked against `srs`.  With g_lagrange the instance columns are committed as upstream's commit_lagrange

@@ -39,6 +39,28 @@ def test_intt_and_coset_match_oracle(gpu_ctx, oracle_c, k):
     assert (back == a).all()
 
 
+def test_ntt_domain_tables_follow_their_context(gpu_ctx, oracle_c):
+    """The domain tables are cached per ctx and go with it: forward and inverse transforms at 2^4 (one pass) and 2^12 (two passes,
+    the smallest size with a direct twiddle table) through a context, which is then closed; the next contexts -- often at the
+    address the closed one had -- build their own tables and give the first one's outputs bit for bit, which are the oracle's."""
+    import bzh2
+    F = O.FP
+    jobs = []
+    for k in (4, 12):
+        a = rand_elems(np.random.default_rng(900 + k), 1 << k)
+        for inverse in (False, True):
+            jobs.append((a, F.omega(k), inverse, C.ntt(0, a, F.omega(k), inverse=inverse, threads=8)))
+    first = None
+    for it in range(3):
+        with bzh2.Context(0) as ctx:
+            got = [ctx.ntt(0, a, omega=w, inverse=inverse) for a, w, inverse, _ in jobs]
+            again = [ctx.ntt(0, a, omega=w, inverse=inverse) for a, w, inverse, _ in jobs]     # ... and from the cached tables
+        if first is None:
+            first = got
+        for j, (_, _, _, want) in enumerate(jobs):
+            assert (got[j] == first[j]).all() and (again[j] == first[j]).all() and (got[j] == want).all(), (it, j)
+
+
 def test_ntt_batched_and_montgomery(gpu_ctx, oracle_c):
     import bzh2
     F = O.FP

@@ -66,7 +66,10 @@ def test_module_swap_and_free_are_refused_while_another_ctx_proves_on_the_key(gp
     key untouched) while a bzh_prove_batch on the key is still running on another ctx -- a launch of the unloaded code or a
     kernel on a freed arena would fault the GPU.  Thread A proves a batch; the main thread keeps asking for both through its
     own ctx until A is done: every answer during the call is a refusal, A's proofs are the expected bytes, and both requests
-    succeed afterwards."""
+    succeed afterwards.  A call counts from its first line inside the library, before it waits for its ctx: with a second
+    prove_batch queued behind the first on the same ctx, the module swap is refused without a gap from the first call's run to
+    the second's return, and the free, asked for once the first has returned, is refused while the second runs.  (The free is
+    not asked for while the first still runs: see the comment at that case.)"""
     import time
     import bzh2
     from bzh2 import BzhError, circuits as Cm, native as N, params as Pm
@@ -79,22 +82,82 @@ def test_module_swap_and_free_are_refused_while_another_ctx_proves_on_the_key(gp
         adv, insts = lay.synthesize(circuits)
         seeds = [R.rng_stream("busy-%d" % b, 32) for b in range(16)]
         want = pk.prove_batch(adv, insts, None, seeds=seeds, ctx=other)      # warm: caches filled, workspace grown
-        state = {"running": False, "done": False, "proofs": None, "error": None}
 
-        def prove():
+        def start_prove():
+            state = {"done": False, "proofs": None, "error": None}
+
+            def prove():
+                try:
+                    state["proofs"] = pk.prove_batch(adv, insts, None, seeds=seeds, ctx=other)
+                except BaseException as e:  # noqa: BLE001
+                    state["error"] = e
+                finally:
+                    state["done"] = True
+            th = threading.Thread(target=prove)
+            th.start()
+            return th, state
+
+        def module_swap_refused():
+            """the idle key's answer to set_quotient_module(None) is harmless (back to the builtin kernel): the probe for 'a call is inside'"""
             try:
-                state["running"] = True
-                state["proofs"] = pk.prove_batch(adv, insts, None, seeds=seeds, ctx=other)
-            except BaseException as e:  # noqa: BLE001
-                state["error"] = e
-            finally:
-                state["done"] = True
-        th = threading.Thread(target=prove)
-        th.start()
-        while not state["running"]:
-            time.sleep(0)
-        time.sleep(0.002)      # let the call take the key (it runs for tens of milliseconds)
+                pk.set_quotient_module(None)
+                return False
+            except BzhError as e:
+                assert e.status == -1
+                return True
+
+        def wait_for_first_refusal(state):
+            deadline = time.monotonic() + 5.0
+            while time.monotonic() < deadline and not state["done"]:
+                if module_swap_refused():
+                    return True
+            return False
+
+        # A second call queued behind the first on the same ctx: inside the library, not yet running.  From the moment the first is
+        # known to be inside until the second has returned, the count of calls on the key must never reach zero -- not even at the
+        # hand-over of the ctx -- so the harmless probe is refused every time.  The free itself is asked for only after the first
+        # call has returned and a probe has shown the second one inside: a free asked for earlier could, were the library wrong or
+        # the second thread slow, go through before that thread has entered the library and pull the key from under it.
+        th1, st1 = start_prove()
+        inside = wait_for_first_refusal(st1)
+        th2, st2 = start_prove()
+        probes_refused, free_refused, error = 0, 0, None
+        while not st2["done"] and error is None:
+            if not module_swap_refused():
+                th2.join(timeout=0.01)    # allowed only once both calls have left the library: thread 2 ends right after (its
+                if th2.is_alive() or not st1["done"]:    # batch alone runs longer than this wait)
+                    error = AssertionError("no call was counted on the key while one ran and one was queued or running")
+                break
+            probes_refused += 1
+            if not st1["done"]:
+                continue
+            try:
+                pk.close()
+                th2.join(timeout=0.01)    # (the second call left the library between the probe and the free)
+                if th2.is_alive():
+                    error = AssertionError("free went through with the queued call inside")
+                break
+            except BzhError as e:
+                assert e.status == -1
+                free_refused += 1
+        th1.join()
+        th2.join()
+        assert inside, "no refusal within 5 s of starting a 16-proof call"
+        assert error is None and st1["error"] is None and st2["error"] is None, (error, st1["error"], st2["error"])
+        assert st1["proofs"] == want and st2["proofs"] == want
+        print("queued call: %d probes refused, %d frees refused" % (probes_refused, free_refused))
+        assert probes_refused >= 1 and free_refused >= 1, (probes_refused, free_refused)
+        if pk.handle is None:     # (that rare, allowed free: the rest needs a key)
+            pk = N.NativeProvingKey(gpu_ctx, lay.blob(), bzh2.CURVE_VESTA, params=prm)
+            assert pk.prove_batch(adv, insts, None, seeds=seeds, ctx=other) == want
+
+        th, state = start_prove()
+        seen = wait_for_first_refusal(state)      # the call has taken the key (it runs for tens of milliseconds)
+        if not seen:
+            th.join()
+        assert seen, "no refusal within 5 s of starting a 16-proof call"
         refused = {"module": 0, "free": 0}
+        refused["module"] += 1      # the one wait_for_first_refusal has just seen
         while not state["done"]:
             for what, call in (("module", lambda: pk.set_quotient_module(None)), ("free", pk.close)):
                 try:

@@ -294,6 +294,34 @@ def test_two_threads_share_one_vk_and_free_waits(gpu_ctx, srs5):
         vk.close()
 
 
+def test_context_churn_on_one_key(gpu_ctx, srs5):
+    """Eight contexts, one after the other, verify the same three proofs (one corrupted) on ONE bzh_vk and ONE bzh_pk and are
+    closed again.  A key files its per-ctx workspace under the ctx's serial number, so a new context never inherits the workspace
+    of a destroyed one whose address it got back: the results are the first iteration's every time, the verifying key owns no
+    device memory of its own throughout, and both keys can be closed once the contexts are gone."""
+    import bzh2
+    from bzh2 import native as N
+    pk, blob, insts, proofs = _prove(gpu_ctx, srs5, 1, 3)
+    bad = [proofs[0], proofs[1][:100] + b"\x01" + proofs[1][101:], proofs[2]]
+    vk = N.NativeVerifyingKey.from_pk(pk)
+    try:
+        first = None
+        for it in range(8):
+            ctx = bzh2.Context(0)
+            try:
+                got = [vk.verify_batch(ctx, srs5, insts, bad, g0_u_w=srs5.g0_u_w), pk.verify_batch(insts, bad, ctx=ctx)]
+            finally:
+                ctx.close()
+            if first is None:
+                first = got
+            assert got == first == [[True, False, True]] * 2, (it, got)
+            assert vk.device_bytes()[0] == 0 and vk.device_bytes()[1] > 0, it
+    finally:
+        vk.close()
+        pk.close()
+    assert vk.handle is None and pk.handle is None
+
+
 def test_no_key_columns_on_the_device(gpu_ctx, srs5):
     import bzh2
     from bzh2 import native as N
