@@ -769,6 +769,51 @@ class TranscriptBatch:
                     where)
         return v, st
 
+    def multiopen(self, bases: "Bases", k: int, polys, blinds, points, queries, rng_list, *, shared=None, shared_blinds=None,
+                  form: int = FORM_CANONICAL, mem: int = MEM_HOST, status=None, rng_stride: int | None = None, batch: int | None = None,
+                  npolys_own: int | None = None, npolys_shared: int = 0, npoints: int | None = None):
+        """the multiopen argument of `batch` proofs against this device-resident batch (bzh_multiopen_batch_device): x1, x2, the
+        commitment of f, x3, every q_s(x3), x4 and the opening of p at x3 go through the transcripts, with no host trip in between.
+        queries: (poly, point number) pairs; ids below the number of own polynomials are a proof's own, the rest `shared`.
+        MEM_HOST: polys (batch, npolys_own, n, 4) uint64 in `form`; blinds (batch, npolys_own, 4); points (batch, npoints, 4);
+        shared (npolys_shared, n, 4) and shared_blinds (npolys_shared, 4) or None; rng_list: one byte string of
+        64 * (n + 2 + 2k) draws per proof.  Returns the status bytes, (batch,) uint8: bit 0 -- two points of a set coincide in
+        that proof, bit 1 -- a zero round challenge in the opening.
+        MEM_DEVICE: every operand is a device pointer (int, 16-byte aligned; `status` any alignment, or None), rng_list the pointer
+        to the draws (proof b at + b * rng_stride); npolys_own and npoints are required, npolys_shared defaults to 0.  Enqueues
+        only, returns None."""
+        L = load()
+        vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+        L.bzh_multiopen_batch_device.argtypes = [vp, vp, sz, ctypes.c_uint, vp, sz, vp, sz, vp, vp, vp, sz, vp, sz, ci, ci, vp, sz, vp, vp]
+        ctxh = self.ctx.handle if self.ctx is not None else None
+        bh = bases.handle if bases is not None else None
+        where = "bzh_multiopen_batch_device"
+        q = _query_array(queries)
+        if mem == MEM_DEVICE:
+            ptr = lambda v: ctypes.c_void_p(int(v)) if v else None  # noqa: E731
+            self._check(L.bzh_multiopen_batch_device(ctxh, bh, self.batch if batch is None else batch, k, ptr(polys), npolys_own or 0,
+                                                     ptr(shared), npolys_shared, ptr(blinds), ptr(shared_blinds), ptr(points), npoints or 0,
+                                                     _vp(q), len(q), form, mem, ptr(rng_list), rng_stride or 0, self.h, ptr(status)), where)
+            return None
+        B, n = len(rng_list), 1 << k
+        p = np.ascontiguousarray(np.asarray(polys, dtype=np.uint64).reshape(B, -1, n, 4))
+        own = p.shape[1]
+        bl = np.ascontiguousarray(np.asarray(blinds, dtype=np.uint64).reshape(B, own, 4))
+        pt = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(B, -1, 4))
+        sh = sb = None
+        nsh = 0
+        if shared is not None:
+            sh = np.ascontiguousarray(np.asarray(shared, dtype=np.uint64).reshape(-1, n, 4))
+            nsh = sh.shape[0]
+            sb = np.ascontiguousarray(np.asarray(shared_blinds, dtype=np.uint64).reshape(nsh, 4))
+        stride = len(rng_list[0])
+        assert all(len(r) == stride for r in rng_list)
+        raw = np.frombuffer(b"".join(rng_list), dtype=np.uint8)
+        st = np.zeros(B, dtype=np.uint8)
+        self._check(L.bzh_multiopen_batch_device(ctxh, bh, B, k, _vp(p), own, _vp(sh) if nsh else None, nsh, _vp(bl), _vp(sb) if nsh else None,
+                                                 _vp(pt), pt.shape[1], _vp(q), len(q), form, mem, _vp(raw), stride, self.h, _vp(st)), where)
+        return st
+
     def close(self):
         if self.h is not None:
             load().bzh_transcript_batch_free(self.h)
@@ -783,6 +828,37 @@ class TranscriptBatch:
 
 # ---- IPA opening --------------------------------------------------------------------------------
 EXPORTS += ["bzh_ipa_open", "bzh_ipa_open_batch", "bzh_ipa_open_batch_device", "bzh_ipa_verify"]
+EXPORTS += ["bzh_multiopen_plan", "bzh_multiopen_batch_device"]
+MULTIOPEN_MAX_POINTS = 8
+
+
+def _query_array(queries) -> np.ndarray:
+    """(poly, point number) pairs as the bzh_open_query array the library reads"""
+    return np.ascontiguousarray(np.asarray(list(queries), dtype=np.uint32).reshape(-1, 2))
+
+
+def multiopen_plan(queries, npolys: int, npoints: int):
+    """upstream's construct_intermediate_sets on (poly, point number) pairs (bzh_multiopen_plan, host only): returns
+    (point_sets, groups, set_of_poly) -- point_sets[s]: the point numbers of set s, ascending; groups[s]: its polynomials in
+    first-seen order; set_of_poly[p]: the set of polynomial p, or None if it is never queried."""
+    L = load()
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    L.bzh_multiopen_plan.argtypes = [vp, sz, sz, sz, vp, vp, vp, vp, ctypes.POINTER(sz)]
+    q = _query_array(queries)
+    room = max(npolys, 1)
+    set_of, order, sizes = (np.zeros(room, dtype=np.uint32) for _ in range(3))
+    pts = np.zeros((room, MULTIOPEN_MAX_POINTS), dtype=np.uint32)
+    nsets = sz(0)
+    rc = L.bzh_multiopen_plan(_vp(q), len(q), npolys, npoints, _vp(set_of), _vp(order), _vp(sizes), _vp(pts), ctypes.byref(nsets))
+    if rc != OK:
+        raise BzhError(rc, "bzh_multiopen_plan")
+    ns = nsets.value
+    point_sets = [[int(x) for x in pts[s, :sizes[s]]] for s in range(ns)]
+    groups = [[] for _ in range(ns)]
+    for pid in order[:npolys]:
+        if pid != 0xffffffff:
+            groups[int(set_of[pid])].append(int(pid))
+    return point_sets, groups, [None if x == 0xffffffff else int(x) for x in set_of[:npolys]]
 EXPORTS += ["bzh_pk_create", "bzh_pk_free", "bzh_pk_set_lagrange", "bzh_pk_quotient_stats", "bzh_pk_quotient_source", "bzh_pk_set_quotient_module", "bzh_pk_info", "bzh_prove_batch", "bzh_prove_batch_seeded", "bzh_rng_expand", "bzh_verify_batch",
             "bzh_vk_digest", "bzh_pk_vk_repr"]
 EXPORTS += ["bzh_vk_create", "bzh_vk_from_pk", "bzh_vk_write", "bzh_vk_read", "bzh_vk_info", "bzh_vk_vk_repr", "bzh_vk_device_bytes",

@@ -928,6 +928,80 @@ int bzh_ipa_open_batch_device(bzh_ctx* ctx, const bzh_bases* bases, const uint64
     return BZH_OK;
 }
 
+int bzh_multiopen_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, unsigned k, const uint64_t* polys, size_t npolys_own,
+                               const uint64_t* shared, size_t npolys_shared, const uint64_t* blinds, const uint64_t* shared_blinds,
+                               const uint64_t* points, size_t npoints, const bzh_open_query* queries, size_t nqueries, int form, int mem,
+                               const uint8_t* rng, size_t rng_stride, bzh_transcript_batch* transcripts, uint8_t* status) {
+    if (!ctx || !bases || !transcripts || !polys || !blinds || !points || !queries || !rng || !valid_form(form) || !valid_mem(mem))
+        return BZH_E_ARG;
+    if (!npolys_own || (npolys_shared && (!shared || !shared_blinds)) || !batch || batch > 65535 || k > 31) return BZH_E_ARG;
+    const size_t n = (size_t)1 << k, npolys = npolys_own + npolys_shared, nrand = n + 2 + 2 * (size_t)k;
+    if (rng_stride < 64 * nrand) return BZH_E_ARG;
+    MoPlan plan;
+    plan.npolys_own = npolys_own, plan.npolys_shared = npolys_shared, plan.npoints = npoints;
+    plan.set_of_poly.resize(npolys), plan.group_order.resize(npolys), plan.set_sizes.resize(npolys);
+    plan.set_points.resize(npolys * BZH_MULTIOPEN_MAX_POINTS);
+    BZH_TRY(bzh_multiopen_plan(queries, nqueries, npolys, npoints, plan.set_of_poly.data(), plan.group_order.data(), plan.set_sizes.data(),
+                               plan.set_points.data(), &plan.nsets));
+    for (size_t s = 0; s < plan.nsets; s++)
+        if (plan.set_sizes[s] >= n) return BZH_E_ARG;   // nothing is left of n coefficients after n divisions
+    const TbInfo ti = tb_info(transcripts);
+    if (ti.ctx != ctx || ti.batch != batch) return BZH_E_ARG;   // (a host-resident batch has no ctx)
+    if (bases->n != n + 2 || bases->device != ctx->device || ti.curve != bases->curve) return BZH_E_ARG;
+    const uintptr_t all = (uintptr_t)polys | (uintptr_t)shared | (uintptr_t)blinds | (uintptr_t)shared_blinds | (uintptr_t)points | (uintptr_t)rng;
+    if (mem == BZH_MEM_DEVICE && (all & 15)) return BZH_E_ARG;
+    if (ti.proof_len + 32 + 32 * plan.nsets + 32 * (1 + 2 * (size_t)k) + 64 > ti.proof_cap) return BZH_E_RANGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int field = 0;
+    BZH_TRY(with_curve(bases->curve, [&](auto c) {
+        field = CurveInfo<decltype(c)>::scalar_field;
+        return BZH_OK;
+    }));
+    const bool host = mem == BZH_MEM_HOST, canonical = form == BZH_FORM_CANONICAL;
+    const size_t st_bytes = (batch + 15) & ~(size_t)15, own = batch * npolys_own * n, shr = npolys_shared * n;
+    // the staging workspace holds, side by side: the polynomials' Montgomery copy (host or canonical operands), the small host
+    // operands, and the call's own scratch
+    Stager s{ctx, field, form};
+    BZH_TRY(s.begin(((host || canonical) ? (own + shr) * 32 + 128 : 0) +
+                    (host ? (batch * (npolys_own + npoints) + npolys_shared) * 32 + batch * nrand * 64 + st_bytes + 5 * 64 : 0) +
+                    multiopen_scratch_bytes(plan, batch, n) + 64));
+    const uint32_t *d_polys = (const uint32_t*)polys, *d_shared = (const uint32_t*)shared;
+    auto montgomery_copy = [&](const uint64_t* src, size_t elems, const uint32_t** dev) -> int {
+        uint32_t* d = nullptr;
+        if (host) {
+            BZH_TRY(s.in(src, elems, &d));
+        } else {
+            d = s.carve(elems * 32);
+            BZH_HIP_TRY(ctx, hipMemcpyAsync(d, src, elems * 32, hipMemcpyDeviceToDevice, ctx->stream));
+            BZH_TRY(field_convert(ctx, field, d, elems, 1));
+        }
+        *dev = d;
+        return BZH_OK;
+    };
+    if (host || canonical) {
+        BZH_TRY(montgomery_copy(polys, own, &d_polys));
+        if (shr) BZH_TRY(montgomery_copy(shared, shr, &d_shared));
+    }
+    if (!host)
+        return multiopen_device(ctx, bases, batch, k, plan, d_polys, d_shared, (const uint32_t*)blinds, (const uint32_t*)shared_blinds,
+                                (const uint32_t*)points, form, rng, rng_stride, transcripts, status, s.carve(0));
+    uint32_t *d_blinds = s.carve(batch * npolys_own * 32), *d_sblinds = s.carve(npolys_shared * 32), *d_points = s.carve(batch * npoints * 32);
+    uint8_t* d_rng = (uint8_t*)s.carve(batch * nrand * 64);
+    uint8_t* d_st = (uint8_t*)s.carve(st_bytes);
+    BZH_TRY(h2d_small(ctx, d_blinds, blinds, batch * npolys_own * 32));
+    BZH_TRY(h2d_small(ctx, d_sblinds, shared_blinds, npolys_shared * 32));
+    BZH_TRY(h2d_small(ctx, d_points, points, batch * npoints * 32));
+    for (size_t b = 0; b < batch; b++) BZH_TRY(h2d_small(ctx, d_rng + b * nrand * 64, rng + b * rng_stride, nrand * 64));
+    BZH_TRY(multiopen_device(ctx, bases, batch, k, plan, d_polys, d_shared, d_blinds, d_sblinds, d_points, form, d_rng, nrand * 64, transcripts,
+                             d_st, s.carve(0)));
+    std::vector<uint8_t> st(st_bytes);
+    BZH_TRY(d2h_async(ctx, st.data(), d_st, st_bytes));
+    BZH_TRY(d2h_finish(ctx));
+    if (status) memcpy(status, st.data(), batch);
+    return BZH_OK;
+}
+
 int bzh_ipa_open(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* poly, int form, int mem, const uint64_t* blind,
                  const uint64_t* x3, const uint8_t* rng, size_t rng_len, bzh_transcript* transcript, uint64_t* out_v) {
     return bzh_ipa_open_batch(ctx, bases, poly, form, mem, 1, blind, x3, rng, rng_len, &transcript, out_v);

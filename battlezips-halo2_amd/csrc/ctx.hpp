@@ -357,6 +357,22 @@ int ipa_open(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size
 int ipa_open_device(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint32_t* d_blinds,
                     const uint32_t* d_x3s, int form, const uint8_t* d_rng, size_t rng_stride, bzh_transcript_batch* tb,
                     uint32_t* d_out_v, uint8_t* d_status);
+// the blinded commitment the opening makes for S, for `batch` polynomials of n = bases->n - 2 Montgomery coefficients: scalars
+// [poly_b, 0, blind_b] (d_scalars: batch x (n + 2) scratch) against g || u || w, the Jacobian sums into d_out_xyz.  Enqueues only.
+int ipa_commit_blinded(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint32_t* d_blinds,
+                       uint32_t* d_scalars, uint32_t* d_out_xyz);
+// multiopen.hip: bzh_multiopen_batch_device for a caller that holds ctx->mu and has made every argument check.  The grouping of
+// bzh_multiopen_plan comes in as MoPlan; every data pointer is device memory, 16-byte aligned; d_polys (batch x npolys_own x n) and
+// d_shared (npolys_shared x n) Montgomery; blinds and points in `form`; d_scratch: multiopen_scratch_bytes() bytes that no callee
+// takes (WS_STAGE).  Enqueues only.
+struct MoPlan {
+    size_t npolys_own = 0, npolys_shared = 0, npoints = 0, nsets = 0;
+    std::vector<uint32_t> set_of_poly, group_order, set_sizes, set_points;   // as bzh_multiopen_plan fills them
+};
+size_t multiopen_scratch_bytes(const MoPlan& plan, size_t batch, size_t n);
+int multiopen_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, unsigned k, const MoPlan& plan, const uint32_t* d_polys,
+                     const uint32_t* d_shared, const uint32_t* d_blinds, const uint32_t* d_shared_blinds, const uint32_t* d_points, int form,
+                     const uint8_t* d_rng, size_t rng_stride, bzh_transcript_batch* tb, uint8_t* d_status, void* d_scratch);
 int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                const uint8_t* proof, size_t proof_len, bzh_transcript* tr, const uint64_t* g0_u_w_xy);
 int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,

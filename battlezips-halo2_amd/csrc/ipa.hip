@@ -89,13 +89,13 @@ __global__ void k_sub_at0_batch(uint32_t* __restrict__ v, size_t stride, const u
 
 // commit scalars of S: out[b] = [s_poly_b (n) | 0 | s_blind_b]
 template <class P>
-__global__ void __launch_bounds__(256) k_ipa_commit_scalars(const uint32_t* __restrict__ spoly, const uint32_t* __restrict__ rands,
-                                                              size_t n, size_t nrand, uint32_t* __restrict__ out) {
+__global__ void __launch_bounds__(256) k_ipa_commit_scalars(const uint32_t* __restrict__ spoly, const uint32_t* __restrict__ blinds,
+                                                              size_t n, size_t blind_stride, uint32_t* __restrict__ out) {
     const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x, b = blockIdx.y;
     if (g >= n + 2) return;
     Fe<P> v = fe_zero<P>();
     if (g < n) v = fe_load<P>(spoly + (b * n + g) * 8);
-    else if (g == n + 1) v = fe_load<P>(rands + (b * nrand + n) * 8);
+    else if (g == n + 1) v = fe_load<P>(blinds + b * blind_stride * 8);
     fe_store(out + (b * (n + 2) + g) * 8, v);
 }
 
@@ -589,7 +589,7 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
     BZH_TRY(poly_eval(ctx, field, d_spoly, n, B, d_hc, kHc, d_dv));
     hipLaunchKernelGGL((k_sub_at0_batch<SF>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, d_spoly, n, d_dv, B);
     // S = commit(s, s_blind): scalars [s..., 0, s_blind]
-    hipLaunchKernelGGL((k_ipa_commit_scalars<SF>), grid2(n + 2), dim3(g256), 0, st, d_spoly, d_rand, n, nrand, d_commit);
+    hipLaunchKernelGGL((k_ipa_commit_scalars<SF>), grid2(n + 2), dim3(g256), 0, st, d_spoly, d_rand + n * 8, n, nrand, d_commit);
     BZH_HIP_TRY(ctx, hipGetLastError());
     drv.msm_begin(ctx);
     BZH_TRY(msm_run(ctx, bases, d_commit, n + 2, B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
@@ -946,6 +946,18 @@ int ipa_open_device(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_poly
         IpaDeviceDriver<C> drv{tb, d_blinds, d_x3s, d_rng, rng_stride, d_out_v, d_status, form};
         return ipa_open_t<C>(ctx, bases, d_polys, batch, drv);
     });
+}
+int ipa_commit_blinded(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint32_t* d_blinds,
+                       uint32_t* d_scalars, uint32_t* d_out_xyz) {
+    const size_t n = bases->n - 2;
+    BZH_TRY(with_curve(bases->curve, [&](auto c) {
+        using SF = typename CurveInfo<decltype(c)>::SF;
+        hipLaunchKernelGGL((k_ipa_commit_scalars<SF>), dim3((unsigned)((n + 2 + 255) / 256), (unsigned)batch), dim3(256), 0, ctx->stream, d_polys,
+                           d_blinds, n, (size_t)1, d_scalars);
+        return BZH_OK;
+    }));
+    BZH_HIP_TRY(ctx, hipGetLastError());
+    return msm_run(ctx, bases, d_scalars, n + 2, batch, BZH_FORM_MONTGOMERY, d_out_xyz);
 }
 int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                const uint8_t* proof, size_t proof_len, bzh_transcript* tr, const uint64_t* g0_u_w_xy) {

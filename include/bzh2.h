@@ -318,6 +318,57 @@ struct bzh_transcript_batch;
 int bzh_ipa_open_batch_device(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* polys, int form, int mem, size_t batch,
                               const uint64_t* blinds, const uint64_t* x3s, const uint8_t* rng, size_t rng_stride,
                               struct bzh_transcript_batch* transcripts, uint64_t* out_v, uint8_t* status);
+/* poly::multiopen::prover::create_proof against a device-resident bzh_transcript_batch -- csrc/multiopen.hip,
+ * csrc/multiopen_scalars.hpp: every opening of a proof folded into one polynomial and one point, and that one opened by
+ * bzh_ipa_open_batch_device's rounds -- the multiopen() phase of bzh_prove_batch as a leaf, with its challenges in HBM.
+ *
+ * bzh_multiopen_plan is upstream's construct_intermediate_sets, pure host code (no ctx, no device).  A query says "open
+ * polynomial `poly` at point number `point`".  Polynomials are taken in first-seen order, a repeated (poly, point) pair counts
+ * once, a polynomial's set is the set of its point numbers, and sets are numbered in the order their first polynomial appears.
+ * Grouping is by point NUMBER, not by value: the caller gives equal values one number (two numbers with one value in the same
+ * set are the coincident points of status bit 0 below).  set_of_poly[p]: the set of polynomial p, 0xffffffff if never queried;
+ * group_order: the queried polynomials set by set, first-seen order inside a set (0xffffffff from their count on); set_sizes[s]:
+ * points of set s; set_points: row s (BZH_MULTIOPEN_MAX_POINTS entries) holds the point numbers of set s in ascending order,
+ * padded with 0xffffffff -- the order inside a set does not reach the proof bytes.  set_sizes and set_points have room for npolys
+ * sets.  BZH_E_ARG: a NULL pointer, a poly or point number out of range, nqueries == 0, a set of more than
+ * BZH_MULTIOPEN_MAX_POINTS points.
+ *
+ * bzh_multiopen_batch_device: n = 2^k coefficients per polynomial; `bases` is the SRS as the IPA entry points take it
+ * (g || u || w, n + 2 points); polynomial ids below npolys_own are proof b's own (polys[b][id], blinds[b][id]), the rest are
+ * shared by every proof (shared[id - npolys_own], shared_blinds[..]; both may be NULL only if npolys_shared == 0); points[b][j]
+ * is point number j of proof b.  `form` and `mem` apply to every data pointer except `queries` (host), as in
+ * bzh_ipa_open_batch_device: with BZH_MEM_DEVICE they are 16-byte-aligned device pointers (status: any alignment) and the call
+ * only enqueues; with BZH_MEM_HOST everything is staged up once at the start and status read back once at the end.
+ * Messages, per proof, in upstream's order: squeeze x1, x2; q_s = Horner in x1 over the polynomials of set s in group order
+ * (q_blind_s likewise over their blinds); r_s = the interpolant through (point, q_s(point)) over the set's points;
+ * f_s = (q_s - r_s) / prod (X - point), zero-padded to n; f = Horner in x2 over f_0, ..; WRITE the commitment of f under f_blind;
+ * squeeze x3; WRITE q_s(x3) for every s; squeeze x4; p = Horner in x4 over (f, q_0, ..), p_blind likewise; then the opening
+ * of p at x3: S, (L_j, R_j) for j < k, c, f as bzh_ipa_open_batch_device writes them.
+ * rng: the 64-byte draws of proof b at rng + b * rng_stride; the first is f_blind, the opening takes the n + 1 + 2k after it,
+ * so rng_stride >= 64 * (n + 2 + 2k).  The proof grows by 32 + 32 * nsets + 32 * (1 + 2k) + 64 bytes.
+ * status (may be NULL), one byte per proof: bit 0 -- two points of one set coincide in that proof (an interpolation denominator
+ * is zero; its inverse is taken as 0 and the proof's bytes mean nothing); bit 1 -- what bzh_ipa_open_batch_device reports, a
+ * zero round challenge.  A flagged proof disturbs no other proof, and the call returns BZH_OK.
+ * Between its first launch and its last the call copies no point, scalar or challenge to the host, does no host field or curve
+ * arithmetic and adds no stream synchronisation of its own; what bzh_msm itself waits for, and a workspace (the ctx's, or the
+ * batch's normalisation scratch) that grows on first use, stay as they are.  Its scratch -- q, the division's two buffers and
+ * the f_s at nsets x batch x n elements each, f and p -- is the ctx's staging workspace.
+ * BZH_E_ARG, the batch left as it was: a NULL ctx, bases, transcripts or required data pointer; a host-resident batch; a batch
+ * of another ctx, curve or size; batch == 0 or > 65535; unknown form or mem; a misaligned device pointer; rng_stride too small;
+ * bases that do not hold exactly n + 2 points (n + 2 larger than the table included); a set of n or more points; no own
+ * polynomial; anything bzh_multiopen_plan refuses.  BZH_E_RANGE, nothing absorbed: proof_cap
+ * cannot take the bytes above.  Every check that needs no device comes before the first use of ctx. */
+typedef struct {
+    uint32_t poly;
+    uint32_t point;
+} bzh_open_query;
+#define BZH_MULTIOPEN_MAX_POINTS 8
+int bzh_multiopen_plan(const bzh_open_query* queries, size_t nqueries, size_t npolys, size_t npoints, uint32_t* set_of_poly,
+                       uint32_t* group_order, uint32_t* set_sizes, uint32_t* set_points, size_t* nsets);
+int bzh_multiopen_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, unsigned k, const uint64_t* polys, size_t npolys_own,
+                               const uint64_t* shared, size_t npolys_shared, const uint64_t* blinds, const uint64_t* shared_blinds,
+                               const uint64_t* points, size_t npoints, const bzh_open_query* queries, size_t nqueries, int form, int mem,
+                               const uint8_t* rng, size_t rng_stride, struct bzh_transcript_batch* transcripts, uint8_t* status);
 int bzh_ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                    const uint8_t* proof, size_t proof_len, bzh_transcript* transcript, const uint64_t* g0_u_w);
 
