@@ -814,6 +814,54 @@ class TranscriptBatch:
                                                  _vp(pt), pt.shape[1], _vp(q), len(q), form, mem, _vp(raw), stride, self.h, _vp(st)), where)
         return st
 
+    def evaluations(self, k: int, polys, queries, *, shared=None, h_pieces=None, h_blinds=None, npieces: int = 0, h_stride: int | None = None,
+                    form: int = FORM_CANONICAL, mem: int = MEM_HOST, out_points=None, out_evals=None, out_h=None, out_h_blind=None,
+                    batch: int | None = None, npolys_own: int | None = None, npolys_shared: int = 0):
+        """the evaluation phase of `batch` proofs against this device-resident batch (bzh_evaluations_batch_device): x is squeezed,
+        every query's value poly(x * omega^rotation) written in the order given, and h(X) = sum_i x^(n i) piece_i built, with no
+        host trip in between.  queries: (poly, rotation) pairs; ids below the number of own polynomials are a proof's own, the
+        rest `shared`.  The outputs chain into multiopen(): points is its `points` operand, h and h_blind one more own polynomial.
+        MEM_HOST: polys (batch, npolys_own, n, 4) uint64 in `form`; shared (npolys_shared, n, 4) or None; with npieces > 0,
+        h_pieces (batch, h_stride, 4) -- piece i of a proof at elements [i * n, (i + 1) * n) of its row, h_stride >= npieces * n --
+        and h_blinds (batch, npieces, 4).  Returns (points, evals, h, h_blind): (batch, nrotations, 4), (batch, nqueries, 4),
+        (batch, n, 4) and (batch, 4) uint64 in `form`, the rotations numbered as evaluations_plan numbers them; h and h_blind are
+        None without pieces.
+        MEM_DEVICE: every operand and output is a device pointer (int, 16-byte aligned); npolys_own is required, and so are
+        h_stride and the two h outputs with npieces > 0; out_evals may be None.  Enqueues only, returns None."""
+        L = load()
+        vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+        L.bzh_evaluations_batch_device.argtypes = [vp, sz, ctypes.c_uint, vp, sz, vp, sz, vp, sz, vp, sz, sz, vp, ci, ci, vp, vp, vp, vp, vp]
+        ctxh = self.ctx.handle if self.ctx is not None else None
+        where = "bzh_evaluations_batch_device"
+        q = _eval_query_array(queries)
+        if mem == MEM_DEVICE:
+            ptr = lambda v: ctypes.c_void_p(int(v)) if v else None  # noqa: E731
+            self._check(L.bzh_evaluations_batch_device(ctxh, self.batch if batch is None else batch, k, ptr(polys), npolys_own or 0, ptr(shared),
+                                                       npolys_shared, _vp(q), len(q), ptr(h_pieces), npieces, h_stride or 0, ptr(h_blinds), form,
+                                                       mem, self.h, ptr(out_points), ptr(out_evals), ptr(out_h), ptr(out_h_blind)), where)
+            return None
+        n = 1 << k
+        p = np.ascontiguousarray(np.asarray(polys, dtype=np.uint64))
+        B = p.shape[0]
+        p = p.reshape(B, -1, n, 4)
+        sh, nsh = None, 0
+        if shared is not None:
+            sh = np.ascontiguousarray(np.asarray(shared, dtype=np.uint64).reshape(-1, n, 4))
+            nsh = sh.shape[0]
+        hp = hb = h = hbl = None
+        stride = 0
+        if npieces:
+            hp = np.ascontiguousarray(np.asarray(h_pieces, dtype=np.uint64).reshape(B, -1, 4))
+            stride = hp.shape[1] if h_stride is None else h_stride
+            hb = np.ascontiguousarray(np.asarray(h_blinds, dtype=np.uint64).reshape(B, npieces, 4))
+            h, hbl = np.zeros((B, n, 4), dtype=np.uint64), np.zeros((B, 4), dtype=np.uint64)
+        nrot = len({int(r) for r in q["rotation"]})
+        pts, ev = np.zeros((B, max(nrot, 1), 4), dtype=np.uint64), np.zeros((B, max(len(q), 1), 4), dtype=np.uint64)
+        opt = lambda a: _vp(a) if a is not None else None  # noqa: E731
+        self._check(L.bzh_evaluations_batch_device(ctxh, B, k, _vp(p), p.shape[1], opt(sh), nsh, _vp(q), len(q), opt(hp), npieces, stride, opt(hb),
+                                                   form, mem, self.h, _vp(pts), _vp(ev), opt(h), opt(hbl)), where)
+        return pts[:, :nrot], ev[:, :len(q)], h, hbl
+
     def close(self):
         if self.h is not None:
             load().bzh_transcript_batch_free(self.h)
@@ -859,6 +907,36 @@ def multiopen_plan(queries, npolys: int, npoints: int):
         if pid != 0xffffffff:
             groups[int(set_of[pid])].append(int(pid))
     return point_sets, groups, [None if x == 0xffffffff else int(x) for x in set_of[:npolys]]
+
+
+EXPORTS += ["bzh_evaluations_plan", "bzh_evaluations_batch_device"]
+EVAL_MAX_ROTATIONS = 8
+_EVAL_QUERY = np.dtype([("poly", np.uint32), ("rotation", np.int32)])
+
+
+def _eval_query_array(queries) -> np.ndarray:
+    """(poly, rotation) pairs as the bzh_eval_query array the library reads"""
+    return np.array([(int(p), int(r)) for p, r in queries], dtype=_EVAL_QUERY)
+
+
+def evaluations_plan(queries, npolys: int):
+    """what the evaluation phase derives from its (poly, rotation) queries (bzh_evaluations_plan, host only): returns
+    (rotations, point_of_query, poly_order, rot_count) -- the distinct rotations in first-seen order; per query the index of its
+    rotation in that list; the queried polynomials in first-seen order; per polynomial id the number of its distinct rotations
+    (0: never queried)."""
+    L = load()
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    L.bzh_evaluations_plan.argtypes = [vp, sz, sz, vp, ctypes.POINTER(sz), vp, vp, vp]
+    q = _eval_query_array(queries)
+    rots = np.zeros(max(len(q), 1), dtype=np.int32)
+    point = np.zeros(max(len(q), 1), dtype=np.uint32)
+    order, count = (np.zeros(max(npolys, 1), dtype=np.uint32) for _ in range(2))
+    nrot = sz(0)
+    rc = L.bzh_evaluations_plan(_vp(q), len(q), npolys, _vp(rots), ctypes.byref(nrot), _vp(point), _vp(order), _vp(count))
+    if rc != OK:
+        raise BzhError(rc, "bzh_evaluations_plan")
+    return ([int(r) for r in rots[:nrot.value]], [int(j) for j in point[:len(q)]], [int(i) for i in order[:npolys] if i != 0xffffffff],
+            [int(c) for c in count[:npolys]])
 EXPORTS += ["bzh_pk_create", "bzh_pk_free", "bzh_pk_set_lagrange", "bzh_pk_quotient_stats", "bzh_pk_quotient_source", "bzh_pk_set_quotient_module", "bzh_pk_info", "bzh_prove_batch", "bzh_prove_batch_seeded", "bzh_rng_expand", "bzh_verify_batch",
             "bzh_vk_digest", "bzh_pk_vk_repr"]
 EXPORTS += ["bzh_vk_create", "bzh_vk_from_pk", "bzh_vk_write", "bzh_vk_read", "bzh_vk_info", "bzh_vk_vk_repr", "bzh_vk_device_bytes",

@@ -4,6 +4,8 @@
 
 namespace bzh {
 
+static constexpr int kVecThreads = 256;   // the workgroup of the vector primitives (polyops.hip, evaluations.hip)
+
 // ---------------------------------------------------------------------------
 // block-wide sum of one field element per thread (LDS tree), result in thread 0
 // ---------------------------------------------------------------------------

@@ -1002,6 +1002,96 @@ int bzh_multiopen_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batc
     return BZH_OK;
 }
 
+int bzh_evaluations_batch_device(bzh_ctx* ctx, size_t batch, unsigned k, const uint64_t* polys, size_t npolys_own, const uint64_t* shared,
+                                 size_t npolys_shared, const bzh_eval_query* queries, size_t nqueries, const uint64_t* h_pieces,
+                                 size_t npieces, size_t h_stride, const uint64_t* h_blinds, int form, int mem,
+                                 bzh_transcript_batch* transcripts, uint64_t* out_points, uint64_t* out_evals, uint64_t* out_h,
+                                 uint64_t* out_h_blind) {
+    if (!ctx || !transcripts || !polys || !queries || !out_points || !valid_form(form) || !valid_mem(mem)) return BZH_E_ARG;
+    if (!npolys_own || (npolys_shared && !shared) || !batch || batch > 65535 || k > 32) return BZH_E_ARG;
+    if (npieces && (!h_pieces || !h_blinds || !out_h || !out_h_blind)) return BZH_E_ARG;
+    const size_t n = (size_t)1 << k, npolys = npolys_own + npolys_shared;
+    if (npieces && (npieces > ((size_t)1 << 20) || h_stride < npieces * n)) return BZH_E_ARG;
+    if (!nqueries) return BZH_E_ARG;
+    EvPlan plan;
+    plan.npolys_own = npolys_own, plan.npolys_shared = npolys_shared, plan.nqueries = nqueries;
+    plan.rotations.resize(nqueries), plan.point_of_query.resize(nqueries), plan.poly_order.resize(npolys), plan.rot_count.resize(npolys);
+    BZH_TRY(bzh_evaluations_plan(queries, nqueries, npolys, plan.rotations.data(), &plan.nrot, plan.point_of_query.data(),
+                                 plan.poly_order.data(), plan.rot_count.data()));
+    plan.rotations.resize(plan.nrot);
+    plan.poly_of_query.resize(nqueries);
+    for (size_t q = 0; q < nqueries; q++) plan.poly_of_query[q] = queries[q].poly;
+    const TbInfo ti = tb_info(transcripts);
+    if (ti.ctx != ctx || ti.batch != batch) return BZH_E_ARG;   // (a host-resident batch has no ctx)
+    int field = 0;
+    BZH_TRY(with_curve(ti.curve, [&](auto c) {
+        field = CurveInfo<decltype(c)>::scalar_field;
+        return BZH_OK;
+    }));
+    if (k > field_two_adicity(field)) return BZH_E_ARG;
+    if (!npieces) h_pieces = h_blinds = nullptr, out_h = out_h_blind = nullptr;
+    const uintptr_t all = (uintptr_t)polys | (uintptr_t)shared | (uintptr_t)h_pieces | (uintptr_t)h_blinds | (uintptr_t)out_points |
+                          (uintptr_t)out_evals | (uintptr_t)out_h | (uintptr_t)out_h_blind;
+    if (mem == BZH_MEM_DEVICE && (all & 15)) return BZH_E_ARG;
+    if (ti.proof_len + 32 * nqueries > ti.proof_cap) return BZH_E_RANGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool host = mem == BZH_MEM_HOST, canonical = form == BZH_FORM_CANONICAL;
+    const size_t own = batch * npolys_own * n, shr = npolys_shared * n, hrow = npieces * n, nrot = plan.nrot;
+    // the staging workspace holds, side by side: the polynomials' and the pieces' Montgomery copy (host or canonical operands), the
+    // host call's blinds and outputs, and the call's own scratch
+    Stager s{ctx, field, form};
+    BZH_TRY(s.begin(((host || canonical) ? (own + shr + batch * hrow) * 32 + 3 * 64 : 0) +
+                    (host ? batch * (npieces + nrot + nqueries + n + 1) * 32 + 5 * 64 : 0) + evaluations_scratch_bytes(plan, batch, npieces) + 64));
+    const uint32_t *d_polys = (const uint32_t*)polys, *d_shared = (const uint32_t*)shared, *d_h = (const uint32_t*)h_pieces;
+    size_t d_h_stride = h_stride;
+    // rows of `row` elements, `stride` apart at the caller's, side by side in the workspace and in Montgomery form
+    auto montgomery_copy = [&](const uint64_t* src, size_t rows, size_t row, size_t stride, const uint32_t** dev) -> int {
+        uint32_t* d = s.carve(rows * row * 32);
+        if (stride == row) row *= rows, stride = row, rows = 1;   // one piece
+        if (host) {
+            for (size_t r = 0; r < rows; r++) BZH_TRY(h2d_small(ctx, d + r * row * 8, src + r * stride * 4, row * 32));
+        } else if (rows == 1) {
+            BZH_HIP_TRY(ctx, hipMemcpyAsync(d, src, row * 32, hipMemcpyDeviceToDevice, ctx->stream));
+        } else {
+            BZH_HIP_TRY(ctx, hipMemcpy2DAsync(d, row * 32, src, stride * 32, row * 32, rows, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        *dev = d;
+        return BZH_OK;
+    };
+    if (host || canonical) {
+        BZH_TRY(montgomery_copy(polys, batch, npolys_own * n, npolys_own * n, &d_polys));
+        if (shr) BZH_TRY(montgomery_copy(shared, 1, shr, shr, &d_shared));
+        if (npieces) BZH_TRY(montgomery_copy(h_pieces, batch, hrow, h_stride, &d_h));
+        d_h_stride = hrow;
+        if (canonical) {   // the three copies lie side by side, 64-byte aligned: one conversion each
+            BZH_TRY(field_convert(ctx, field, (uint32_t*)d_polys, own, 1));
+            if (shr) BZH_TRY(field_convert(ctx, field, (uint32_t*)d_shared, shr, 1));
+            if (npieces) BZH_TRY(field_convert(ctx, field, (uint32_t*)d_h, batch * hrow, 1));
+        }
+    }
+    if (!host) {
+        BZH_TRY(evaluations_device(ctx, ti.curve, batch, k, plan, d_polys, d_shared, d_h, npieces, d_h_stride, (const uint32_t*)h_blinds, form,
+                                   transcripts, (uint32_t*)out_points, (uint32_t*)out_evals, (uint32_t*)out_h, (uint32_t*)out_h_blind,
+                                   s.carve(0)));
+        if (npieces && canonical) BZH_TRY(field_convert(ctx, field, (uint32_t*)out_h, batch * n, 0));
+        return BZH_OK;
+    }
+    uint32_t *d_hbl = s.carve(batch * npieces * 32), *d_pts = s.carve(batch * nrot * 32), *d_ev = s.carve(batch * nqueries * 32);
+    uint32_t *d_oh = s.carve(npieces ? batch * n * 32 : 0), *d_ohb = s.carve(batch * 32);
+    if (npieces) BZH_TRY(h2d_small(ctx, d_hbl, h_blinds, batch * npieces * 32));
+    BZH_TRY(evaluations_device(ctx, ti.curve, batch, k, plan, d_polys, d_shared, d_h, npieces, d_h_stride, d_hbl, form, transcripts, d_pts, d_ev,
+                               d_oh, d_ohb, s.carve(0)));
+    BZH_TRY(d2h_async(ctx, out_points, d_pts, batch * nrot * 32));
+    if (out_evals) BZH_TRY(d2h_async(ctx, out_evals, d_ev, batch * nqueries * 32));
+    if (npieces) {
+        if (canonical) BZH_TRY(field_convert(ctx, field, d_oh, batch * n, 0));
+        BZH_TRY(d2h_async(ctx, out_h, d_oh, batch * n * 32));
+        BZH_TRY(d2h_async(ctx, out_h_blind, d_ohb, batch * 32));
+    }
+    return d2h_finish(ctx);
+}
+
 int bzh_ipa_open(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* poly, int form, int mem, const uint64_t* blind,
                  const uint64_t* x3, const uint8_t* rng, size_t rng_len, bzh_transcript* transcript, uint64_t* out_v) {
     return bzh_ipa_open_batch(ctx, bases, poly, form, mem, 1, blind, x3, rng, rng_len, &transcript, out_v);

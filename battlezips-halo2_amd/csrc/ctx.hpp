@@ -369,10 +369,36 @@ struct MoPlan {
     size_t npolys_own = 0, npolys_shared = 0, npoints = 0, nsets = 0;
     std::vector<uint32_t> set_of_poly, group_order, set_sizes, set_points;   // as bzh_multiopen_plan fills them
 };
+// one Horner term of k_mo_combine, and one source of k_ev_multipoint: coefficient i of proof b at p + (b * stride + i) elements;
+// stride 0: the polynomial is shared by every proof
+struct MoSrc {
+    const uint32_t* p;
+    uint64_t stride;
+};
 size_t multiopen_scratch_bytes(const MoPlan& plan, size_t batch, size_t n);
 int multiopen_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, unsigned k, const MoPlan& plan, const uint32_t* d_polys,
                      const uint32_t* d_shared, const uint32_t* d_blinds, const uint32_t* d_shared_blinds, const uint32_t* d_points, int form,
                      const uint8_t* d_rng, size_t rng_stride, bzh_transcript_batch* tb, uint8_t* d_status, void* d_scratch);
+// k_mo_combine for another caller (evaluations.hip's h(X)): out[z][b][i] = Horner in d_ch[b] over the sources d_first[z] ..
+// d_first[z + 1) of d_srcs, z < lists, n coefficients each, list z at d_out + z * batch * n elements; device pointers, Montgomery
+// form.  Enqueues only.
+int mo_combine(bzh_ctx* ctx, int field, const MoSrc* d_srcs, const uint32_t* d_first, const uint32_t* d_ch, size_t n, size_t batch,
+               size_t lists, uint32_t* d_out);
+// evaluations.hip: bzh_evaluations_batch_device for a caller that holds ctx->mu and has made every argument check.  What
+// bzh_evaluations_plan says about the queries comes in as EvPlan; every data pointer is device memory, 16-byte aligned; d_polys
+// (batch x npolys_own x n), d_shared (npolys_shared x n), the pieces (piece i of proof b at d_h + (b * h_stride + i * n) elements)
+// and d_out_h (batch x n) Montgomery; d_h_blinds, d_out_points (batch x nrot), d_out_evals (batch x nqueries, or null) and
+// d_out_h_blind in `form`; d_scratch: evaluations_scratch_bytes() bytes that no callee takes (WS_STAGE).  Enqueues only.
+struct EvPlan {
+    size_t npolys_own = 0, npolys_shared = 0, nqueries = 0, nrot = 0;
+    std::vector<int32_t> rotations;                              // the nrot distinct rotations, first-seen order
+    std::vector<uint32_t> poly_of_query, point_of_query;         // per query: its polynomial, its index into rotations
+    std::vector<uint32_t> poly_order, rot_count;                 // as bzh_evaluations_plan fills them
+};
+size_t evaluations_scratch_bytes(const EvPlan& plan, size_t batch, size_t npieces);
+int evaluations_device(bzh_ctx* ctx, int curve, size_t batch, unsigned k, const EvPlan& plan, const uint32_t* d_polys, const uint32_t* d_shared,
+                       const uint32_t* d_h, size_t npieces, size_t h_stride, const uint32_t* d_h_blinds, int form, bzh_transcript_batch* tb,
+                       uint32_t* d_out_points, uint32_t* d_out_evals, uint32_t* d_out_h, uint32_t* d_out_h_blind, void* d_scratch);
 int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                const uint8_t* proof, size_t proof_len, bzh_transcript* tr, const uint64_t* g0_u_w_xy);
 int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,

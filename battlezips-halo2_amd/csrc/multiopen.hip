@@ -28,11 +28,7 @@ static_assert(bzh::kMoMaxPoints == BZH_MULTIOPEN_MAX_POINTS, "lane bodies and he
 
 namespace bzh {
 
-// one Horner term: coefficient i of proof b at p + (b * stride + i) elements; stride 0: the polynomial is shared by every proof
-struct MoSrc {
-    const uint32_t* p;
-    uint64_t stride;
-};
+// (one Horner term, MoSrc: ctx.hpp)
 struct MoSteps {
     uint32_t at[kMoMaxPoints];   // entries of the point / evaluation tables before step t
 };
@@ -316,6 +312,16 @@ int multiopen_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, unsigne
     return with_curve(bases->curve, [&](auto c) {
         return multiopen_t<decltype(c)>(ctx, bases, batch, k, plan, d_polys, d_shared, d_blinds, d_shared_blinds, d_points, form, d_rng,
                                         rng_stride, tb, d_status, d_scratch);
+    });
+}
+
+int mo_combine(bzh_ctx* ctx, int field, const MoSrc* d_srcs, const uint32_t* d_first, const uint32_t* d_ch, size_t n, size_t batch,
+               size_t lists, uint32_t* d_out) {
+    return with_field(field, [&](auto p) {
+        hipLaunchKernelGGL((k_mo_combine<decltype(p)>), dim3((unsigned)((n + kMoBlock - 1) / kMoBlock), (unsigned)batch, (unsigned)lists),
+                           dim3(kMoBlock), 0, ctx->stream, d_srcs, d_first, d_ch, n, batch, (const uint32_t*)nullptr, d_out, batch * n);
+        BZH_HIP_TRY(ctx, hipGetLastError());
+        return BZH_OK;
     });
 }
 

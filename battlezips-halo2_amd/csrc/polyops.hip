@@ -17,8 +17,6 @@
 
 namespace bzh {
 
-static constexpr int kVecThreads = 256;
-
 // ---------------------------------------------------------------------------
 // batch inversion: thread t owns elements t, t+T, t+2T, ... (coalesced); Montgomery's
 // trick over its chain with one Fermat inversion per thread.  tmp holds the running

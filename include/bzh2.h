@@ -369,6 +369,54 @@ int bzh_multiopen_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batc
                                const uint64_t* shared, size_t npolys_shared, const uint64_t* blinds, const uint64_t* shared_blinds,
                                const uint64_t* points, size_t npoints, const bzh_open_query* queries, size_t nqueries, int form, int mem,
                                const uint8_t* rng, size_t rng_stride, struct bzh_transcript_batch* transcripts, uint8_t* status);
+/* The evaluation phase of plonk::create_proof against a device-resident bzh_transcript_batch -- csrc/evaluations.hip,
+ * csrc/evaluations_scalars.hpp: the step between the quotient commitments and the multiopen argument, the evaluations() and
+ * h_poly() phases of bzh_prove_batch as a leaf, with x in HBM.  Its out_points is the `points` operand of
+ * bzh_multiopen_batch_device, and its out_h / out_h_blind one more own polynomial and blind of that call, so the arguments after
+ * the quotient commitments (evaluations, multiopen, opening) run back to back on a device batch.
+ *
+ * bzh_evaluations_plan is pure host code (no ctx, no device).  A query says "write `poly` at x * omega^rotation"; any int32
+ * rotation is taken.  rotations / *nrotations: the distinct rotations in first-seen order (room for nqueries); point_of_query[q]:
+ * the index of query q's rotation in `rotations`; poly_order: the queried polynomials in first-seen order, 0xffffffff from their
+ * count on, and rot_count[p]: the distinct rotations of polynomial p, 0 if it is never queried (room for npolys each).
+ * BZH_E_ARG, nothing written: a NULL pointer, a poly id out of range, nqueries == 0, a polynomial at more than
+ * BZH_EVAL_MAX_ROTATIONS distinct rotations.
+ *
+ * bzh_evaluations_batch_device: the field is the scalar field of the batch's curve, n = 2^k coefficients per polynomial, omega
+ * the 2^k-th root bzh_field_omega returns (a negative rotation uses its inverse).  Polynomial ids below npolys_own are proof b's
+ * own (polys[b][id]), the rest are shared by every proof (shared[id - npolys_own]; may be NULL only if npolys_shared == 0).  Piece
+ * i of proof b lies at h_pieces + (b * h_stride + i * n) elements -- a prover's batch x extended-size quotient buffer goes in as it
+ * is -- and h_blinds[b][i] is its blind.  `form` and `mem` apply to every data pointer except `queries` (host), as in the two calls
+ * above: with BZH_MEM_DEVICE they are 16-byte-aligned device pointers and the call only enqueues; with BZH_MEM_HOST the operands
+ * are staged up once at the start and the outputs read back once at the end.
+ * Messages, per proof, in upstream's order: squeeze x; for each query in the order given WRITE poly(x * omega^rotation) -- a
+ * repeated query is evaluated and written again.  The proof grows by 32 * nqueries bytes.
+ * Outputs, in `form`: out_points[b][j] = x_b * omega^rotations[j], j as bzh_evaluations_plan numbers the rotations;
+ * out_evals[b][q] (may be NULL); with npieces > 0, out_h[b] = sum_i x_b^(n i) * piece_i (n coefficients) and out_h_blind[b] the
+ * same sum over h_blinds -- h_pieces, h_blinds, out_h and out_h_blind are required iff npieces > 0.  The transcripts and the
+ * outputs are the only things written.
+ * Between its first launch and its last the call copies no scalar or challenge to the host, does no host field arithmetic on
+ * anything that depends on x and adds no stream synchronisation of its own; omega^rotation, which depends on (field, k,
+ * rotation) alone, is computed on the host and uploaded before the first launch.  A polynomial is read once per proof however
+ * many rotations it is queried at (twice above 5), in place: there is no gathered copy, and the scratch -- x, x^n, the values
+ * per (proof, query) and the small tables, in the ctx's staging workspace -- holds no buffer of n elements per query.
+ * BZH_E_ARG, the batch left as it was and nothing written: a NULL ctx, transcripts or required data pointer; a host-resident
+ * batch; a batch of another ctx or size; batch == 0 or > 65535; k larger than the field's two-adicity; nqueries == 0; no own
+ * polynomial; h_stride < npieces * n; unknown form or mem; a misaligned device pointer; anything bzh_evaluations_plan refuses.
+ * BZH_E_RANGE, nothing absorbed and x not squeezed: proof_cap cannot take 32 * nqueries more bytes.  Every check that needs no
+ * device comes before the first use of ctx. */
+typedef struct {
+    uint32_t poly;
+    int32_t rotation;
+} bzh_eval_query;
+#define BZH_EVAL_MAX_ROTATIONS 8
+int bzh_evaluations_plan(const bzh_eval_query* queries, size_t nqueries, size_t npolys, int32_t* rotations, size_t* nrotations,
+                         uint32_t* point_of_query, uint32_t* poly_order, uint32_t* rot_count);
+int bzh_evaluations_batch_device(bzh_ctx* ctx, size_t batch, unsigned k, const uint64_t* polys, size_t npolys_own, const uint64_t* shared,
+                                 size_t npolys_shared, const bzh_eval_query* queries, size_t nqueries, const uint64_t* h_pieces,
+                                 size_t npieces, size_t h_stride, const uint64_t* h_blinds, int form, int mem,
+                                 struct bzh_transcript_batch* transcripts, uint64_t* out_points, uint64_t* out_evals, uint64_t* out_h,
+                                 uint64_t* out_h_blind);
 int bzh_ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                    const uint8_t* proof, size_t proof_len, bzh_transcript* transcript, const uint64_t* g0_u_w);
 
