@@ -862,6 +862,53 @@ class TranscriptBatch:
                                                    form, mem, self.h, _vp(pts), _vp(ev), opt(h), opt(hbl)), where)
         return pts[:, :nrot], ev[:, :len(q)], h, hbl
 
+    def vanishing(self, pk, advice_polys, instance_polys, lookup_polys, z_polys, theta, beta, gamma, rng_list, *, form: int = FORM_CANONICAL,
+                  mem: int = MEM_HOST, out_random=None, out_random_blind=None, out_h=None, out_h_blinds=None, status=None,
+                  rng_stride: int | None = None, batch: int | None = None, shape=None):
+        """the vanishing argument of `batch` proofs against this device-resident batch (bzh_vanishing_batch_device): the commitment
+        of the random polynomial is written, y squeezed, the quotient evaluated in the flavour `pk` (a NativeProvingKey) has
+        selected, and the commitments of its pieces written, with no host trip in between.  The outputs chain into evaluations():
+        h is its h_pieces with h_stride = the extended size, h_blinds its h_blinds, random one more own polynomial.
+        MEM_HOST: advice_polys (batch, num_advice, n, 4), instance_polys (batch, num_instance, n, 4), lookup_polys
+        (batch, lookups, 2, n, 4) and z_polys (batch, nz, n, 4) uint64 coefficients in `form` (None where the count is 0); theta,
+        beta, gamma (batch, 4); rng_list: one byte string of 64 * (n + 1 + npieces) draws per proof.  Returns (random,
+        random_blind, h, h_blinds, status): (batch, n, 4), (batch, 4), (batch, en, 4), (batch, npieces, 4) uint64 in `form` and
+        (batch,) uint8 -- bit 0: a quotient coefficient at or above npieces * n is non-zero.  `shape`: the first element of
+        vanishing_plan(), which sizes the outputs; None: pk.vanishing_plan()[0], computed for this call.
+        MEM_DEVICE: every operand and output is a device pointer (int, 16-byte aligned; `status` any alignment, or None),
+        rng_list the pointer to the draws (proof b at + b * rng_stride).  Enqueues only, returns None."""
+        L = load()
+        vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+        L.bzh_vanishing_batch_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, sz, vp, vp, vp, vp, vp, vp]
+        ctxh = self.ctx.handle if self.ctx is not None else None
+        pkh = pk.handle if hasattr(pk, "handle") else pk
+        where = "bzh_vanishing_batch_device"
+        if mem == MEM_DEVICE:
+            ptr = lambda v: ctypes.c_void_p(int(v)) if v else None  # noqa: E731
+            self._check(L.bzh_vanishing_batch_device(ctxh, pkh, self.batch if batch is None else batch, ptr(advice_polys), ptr(instance_polys),
+                                                     ptr(lookup_polys), ptr(z_polys), ptr(theta), ptr(beta), ptr(gamma), form, mem, ptr(rng_list),
+                                                     rng_stride or 0, self.h, ptr(out_random), ptr(out_random_blind), ptr(out_h),
+                                                     ptr(out_h_blinds), ptr(status)), where)
+            return None
+        B = len(rng_list)
+        if shape is None:
+            if not hasattr(pk, "vanishing_plan"):
+                raise TypeError("TranscriptBatch.vanishing: `shape` is required when pk is a bare handle")
+            shape = pk.vanishing_plan()[0]
+        n, en, _, _, _, _, npieces, _ = shape
+        arr = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.uint64))  # noqa: E731
+        opt = lambda a: _vp(a) if a is not None and a.size else None  # noqa: E731
+        ops = [arr(a) for a in (advice_polys, instance_polys, lookup_polys, z_polys, theta, beta, gamma)]
+        stride = len(rng_list[0])
+        assert all(len(r) == stride for r in rng_list)
+        raw = np.frombuffer(b"".join(rng_list), dtype=np.uint8)
+        rp, rb = np.zeros((B, n, 4), dtype=np.uint64), np.zeros((B, 4), dtype=np.uint64)
+        h, hb = np.zeros((B, en, 4), dtype=np.uint64), np.zeros((B, npieces, 4), dtype=np.uint64)
+        st = np.zeros(B, dtype=np.uint8)
+        self._check(L.bzh_vanishing_batch_device(ctxh, pkh, B, *[opt(a) for a in ops], form, mem, _vp(raw), stride, self.h, _vp(rp), _vp(rb),
+                                                 _vp(h), _vp(hb), _vp(st)), where)
+        return rp, rb, h, hb, st
+
     def close(self):
         if self.h is not None:
             load().bzh_transcript_batch_free(self.h)
@@ -937,6 +984,37 @@ def evaluations_plan(queries, npolys: int):
         raise BzhError(rc, "bzh_evaluations_plan")
     return ([int(r) for r in rots[:nrot.value]], [int(j) for j in point[:len(q)]], [int(i) for i in order[:npolys] if i != 0xffffffff],
             [int(c) for c in count[:npolys]])
+
+
+EXPORTS += ["bzh_vanishing_plan", "bzh_vanishing_batch_device"]
+_VANISHING_CONST = np.dtype([("challenge", np.int32), ("exponent", np.uint32), ("value", np.uint32, 8)])
+
+
+def vanishing_plan(curve: int, circuit_blob: bytes):
+    """what the vanishing argument derives from a circuit (bzh_vanishing_plan, host only): returns (shape, consts) -- shape:
+    (n, extended size, num_advice, num_instance, nz, lookups, npieces, draws per proof); consts: one (challenge, exponent, value)
+    per entry of the quotient program's constant table, challenge -1 for a literal, else 0 .. 3 for theta, beta, gamma, y, the
+    entry meaning value * challenge^exponent, value a Montgomery-form int."""
+    L = load()
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    L.bzh_vanishing_plan.argtypes = [ctypes.c_int, ctypes.c_char_p, sz, vp, vp, sz, ctypes.POINTER(sz)]
+    L.bzh_quotient_program_for_circuit.argtypes = [ctypes.c_int, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), vp, sz, ctypes.POINTER(sz),
+                                                   ctypes.POINTER(ctypes.c_uint32)]
+    blob = bytes(circuit_blob)
+    nops, nc = sz(0), sz(0)
+    rc = L.bzh_quotient_program_for_circuit(curve, blob, len(blob), None, 0, ctypes.byref(nops), None, 0, ctypes.byref(nc), None)
+    if rc != OK:
+        raise BzhError(rc, "bzh_vanishing_plan")
+    shape = np.zeros(8, dtype=np.uint32)
+    consts = np.zeros(max(nc.value, 1), dtype=_VANISHING_CONST)
+    got = sz(0)
+    rc = L.bzh_vanishing_plan(curve, blob, len(blob), _vp(shape), _vp(consts), nc.value, ctypes.byref(got))
+    if rc != OK:
+        raise BzhError(rc, "bzh_vanishing_plan")
+    value = lambda w: sum(int(x) << (32 * i) for i, x in enumerate(w))  # noqa: E731
+    return tuple(int(x) for x in shape), [(int(c["challenge"]), int(c["exponent"]), value(c["value"])) for c in consts[:got.value]]
+
+
 EXPORTS += ["bzh_pk_create", "bzh_pk_free", "bzh_pk_set_lagrange", "bzh_pk_quotient_stats", "bzh_pk_quotient_source", "bzh_pk_set_quotient_module", "bzh_pk_info", "bzh_prove_batch", "bzh_prove_batch_seeded", "bzh_rng_expand", "bzh_verify_batch",
             "bzh_vk_digest", "bzh_pk_vk_repr"]
 EXPORTS += ["bzh_vk_create", "bzh_vk_from_pk", "bzh_vk_write", "bzh_vk_read", "bzh_vk_info", "bzh_vk_vk_repr", "bzh_vk_device_bytes",

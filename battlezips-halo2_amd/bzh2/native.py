@@ -142,6 +142,7 @@ class NativeProvingKey:
                                                           np.concatenate([int_to_limbs(wp[0]), int_to_limbs(wp[1])])]))
         # a circuit built by the C++ front end (bzh2.circuits.CircuitLayout.blob()) arrives already serialised
         blob = bytes(circuit) if isinstance(circuit, (bytes, bytearray)) else serialize_circuit(circuit, self.p, vk_repr)
+        self.blob = blob
         L = _bind()
         h = _VP()
         ctx._check(L.bzh_pk_create(ctx.handle, self.bases.handle, blob, len(blob), ctypes.byref(h)), "bzh_pk_create")
@@ -158,6 +159,11 @@ class NativeProvingKey:
         out, ph = (ctypes.c_uint8 * 32)(), ctypes.c_int()
         self.ctx._check(_bind().bzh_pk_vk_repr(self.handle, out, ctypes.byref(ph)), "bzh_pk_vk_repr")
         return int.from_bytes(bytes(out), "little"), bool(ph.value)
+
+    def vanishing_plan(self):
+        """(shape, consts) of bzh2.vanishing_plan for this key's circuit: what TranscriptBatch.vanishing takes as `shape`"""
+        from . import vanishing_plan
+        return vanishing_plan(self.curve, self.blob)
 
     def quotient_stats(self) -> dict:
         L = _bind()

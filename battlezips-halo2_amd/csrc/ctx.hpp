@@ -399,6 +399,16 @@ size_t evaluations_scratch_bytes(const EvPlan& plan, size_t batch, size_t npiece
 int evaluations_device(bzh_ctx* ctx, int curve, size_t batch, unsigned k, const EvPlan& plan, const uint32_t* d_polys, const uint32_t* d_shared,
                        const uint32_t* d_h, size_t npieces, size_t h_stride, const uint32_t* d_h_blinds, int form, bzh_transcript_batch* tb,
                        uint32_t* d_out_points, uint32_t* d_out_evals, uint32_t* d_out_h, uint32_t* d_out_h_blind, void* d_scratch);
+// vanishing.hip: the two kernels of bzh_vanishing_batch_device (the call itself reads the key: csrc/vanishing_device.hpp); device
+// pointers, 16-byte aligned unless said otherwise; enqueue only.
+// vanishing_consts: d_table[b][i] = value_i * challenge_b^exponent_i over the nconsts descriptors at d_descs (bzh_vanishing_const);
+// d_theta / d_beta / d_gamma batch elements each in `form`, d_y Montgomery; a constant takes 8 saturated words, or with planes29
+// the unsaturated quotient kernel's 12-word slot.  vanishing_degree: bit 0 of d_status[b] (any alignment, may be null) and of
+// d_sticky[b] is set when an element [first, pitch) of row b of d_h (rows of `pitch` elements) is non-zero; first >= pitch
+// launches nothing.
+int vanishing_consts(bzh_ctx* ctx, int field, const void* d_descs, size_t nconsts, size_t batch, const uint32_t* d_theta,
+                     const uint32_t* d_beta, const uint32_t* d_gamma, const uint32_t* d_y, int form, bool planes29, uint32_t* d_table);
+int vanishing_degree(bzh_ctx* ctx, const uint32_t* d_h, size_t first, size_t pitch, size_t batch, uint8_t* d_status, uint8_t* d_sticky);
 int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                const uint8_t* proof, size_t proof_len, bzh_transcript* tr, const uint64_t* g0_u_w_xy);
 int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
@@ -437,6 +447,7 @@ int tb_absorb_locked(bzh_transcript_batch* tb, int kind, const void* d_base, siz
 int tb_write_jacobian_locked(bzh_transcript_batch* tb, const void* d_xyz, size_t count, size_t stride, int form);
 int tb_squeeze_locked(bzh_transcript_batch* tb, int form, uint32_t* d_out);
 const uint8_t* tb_status_device(const bzh_transcript_batch* tb);
+uint8_t* tb_status_device_mut(bzh_transcript_batch* tb);   // for a kernel of the caller's that marks a transcript (vanishing.hip)
 TbInfo tb_info(const bzh_transcript_batch* tb);
 // verify_pass.hip: the kernels of the verifier's device pass (BZH_VERIFY_PASS_DEVICE); device pointers, enqueue only
 struct VerifyPassArgs {

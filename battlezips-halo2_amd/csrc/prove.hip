@@ -42,6 +42,7 @@
 #include "curve.cuh"
 #include "fe29.cuh"
 #include "host_field.hpp"
+#include "vanishing_scalars.hpp"   // (bzh_vanishing_const as the lane body reads it)
 #include "vm2_isa.hpp"
 
 // the table of quotient kernels generated at build time (quotient_builtin.hip); absent (null) in the generator's own link
@@ -56,6 +57,7 @@ extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __at
 #include "verifying_key.hpp"     // likewise around bzh_vk; its byte format and host-only entry points
 #include "device_columns.hpp"     // columns on the device, their commitments: shared by prover, verifier and keygen_vk
 #include "prover.hpp"
+#include "vanishing_device.hpp"   // phase 5 of the prover as a leaf on device-resident transcripts
 #include "verifier.hpp"
 
 // pk.get_vk(): the commitments to the fixed and permutation polynomials (blind 1), computed once per key
@@ -580,6 +582,64 @@ int bzh_prove_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advi
 int bzh_prove_batch_seeded(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice, int form, int mem, const uint64_t* instances,
                            size_t instance_rows, const uint8_t* seeds, uint8_t* proofs, size_t proof_stride, size_t* proof_lens) {
     return prove_batch_entry(ctx, pk, batch, advice, form, mem, instances, instance_rows, seeds, 0, proofs, proof_stride, proof_lens);
+}
+
+int bzh_vanishing_plan(int curve, const uint8_t* circuit, size_t circuit_len, uint32_t shape8[8], bzh_vanishing_const* consts,
+                       size_t consts_cap, size_t* nconsts) {
+    if (!circuit || !shape8 || !consts || !nconsts) return BZH_E_ARG;
+    bzh_pk pk;
+    std::vector<bzh::VnConst> descs;
+    BZH_TRY(bzh::with_pasta_curve(curve, [&](auto c) {
+        using SF = typename bzh::CurveInfo<decltype(c)>::SF;
+        bzh::ParsedKey<SF> po;
+        BZH_TRY(bzh::pk_parse_t<decltype(c)>(circuit, circuit_len, pk, po));
+        return bzh::vanishing_consts_plan<SF>(pk, descs);
+    }));
+    if (consts_cap < descs.size()) return BZH_E_ARG;
+    const uint32_t shape[8] = {(uint32_t)pk.n,  (uint32_t)pk.en, (uint32_t)pk.na,      (uint32_t)pk.ni, (uint32_t)(pk.nsets + pk.nl),
+                               (uint32_t)pk.nl, (uint32_t)pk.npieces, (uint32_t)(pk.n + 1 + (size_t)pk.npieces)};
+    memcpy(shape8, shape, sizeof(shape));
+    if (!descs.empty()) memcpy(consts, descs.data(), descs.size() * sizeof(bzh::VnConst));
+    *nconsts = descs.size();
+    return BZH_OK;
+}
+
+int bzh_vanishing_batch_device(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice_polys, const uint64_t* instance_polys,
+                               const uint64_t* lookup_polys, const uint64_t* z_polys, const uint64_t* theta, const uint64_t* beta,
+                               const uint64_t* gamma, int form, int mem, const uint8_t* rng, size_t rng_stride,
+                               bzh_transcript_batch* transcripts, uint64_t* out_random, uint64_t* out_random_blind, uint64_t* out_h,
+                               uint64_t* out_h_blinds, uint8_t* status) {
+    // what reads neither the key nor the device
+    if (!ctx || !pk || !transcripts || !rng || !theta || !beta || !gamma || !out_random || !out_random_blind || !out_h || !out_h_blinds)
+        return BZH_E_ARG;
+    if (!batch || batch > 65535 || (form != BZH_FORM_CANONICAL && form != BZH_FORM_MONTGOMERY) || (mem != BZH_MEM_HOST && mem != BZH_MEM_DEVICE))
+        return BZH_E_ARG;
+    const bzh::TbInfo ti = bzh::tb_info(transcripts);
+    if (!ti.ctx) return BZH_E_ARG;   // a host-resident batch
+    bzh::KeyRuntime::Call in_flight(pk->rt);   // registered before the wait for ctx->mu, like every other call on a key
+    // what reads the key
+    const size_t n = pk->n, npieces = (size_t)pk->npieces, nz = (size_t)(pk->nsets + pk->nl);
+    if (pk->device != ctx->device || ti.ctx != ctx || ti.curve != pk->curve || ti.batch != batch) return BZH_E_ARG;
+    if ((pk->na && !advice_polys) || (pk->ni && !instance_polys) || (pk->nl && !lookup_polys) || (nz && !z_polys)) return BZH_E_ARG;
+    // (batch * npieces: ipa_commit_blinded puts the number of commitments into grid.y, and the pieces of a batch are one launch)
+    if (rng_stride < 64 * (n + 1 + npieces) || batch * npieces > 65535) return BZH_E_ARG;
+    const uintptr_t all = (uintptr_t)advice_polys | (uintptr_t)instance_polys | (uintptr_t)lookup_polys | (uintptr_t)z_polys | (uintptr_t)theta |
+                          (uintptr_t)beta | (uintptr_t)gamma | (uintptr_t)rng | (uintptr_t)out_random | (uintptr_t)out_random_blind |
+                          (uintptr_t)out_h | (uintptr_t)out_h_blinds;
+    if (mem == BZH_MEM_DEVICE && (all & 15)) return BZH_E_ARG;
+    if (!pk->q_ok || pk->en % 128) return BZH_E_RANGE;   // no VM v2 program, or a domain below its workgroup: the VM v1 fold is not offered
+    if (ti.proof_len + 32 * (1 + npieces) > ti.proof_cap) return BZH_E_RANGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = bzh::with_pasta_curve(pk->curve, [&](auto c) {
+        return bzh::vanishing_device_t<decltype(c)>(ctx, pk, batch, advice_polys, instance_polys, lookup_polys, z_polys, theta, beta, gamma, form,
+                                                    mem, rng, rng_stride, transcripts, out_random, out_random_blind, out_h, out_h_blinds, status);
+    });
+    if (rc && !ctx->pending_d2h.empty()) {   // a host call that failed between its read-backs and their end: they must not land later
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->pending_d2h.clear();
+    }
+    return rc;
 }
 
 int bzh_rng_expand(const uint8_t* seed, uint64_t first_draw, size_t draws, uint8_t* out) {

@@ -104,14 +104,16 @@ struct Prover : DeviceColumns<C> {
         char* dev = (char*)arena.alloc(total);
         if (!dev) return BZH_E_OOM;
         char* slot = nullptr;
-        BZH_TRY(h2d_stage(ctx, total, &slot));
-        memcpy(slot, cv, cv_bytes);
-        memcpy(slot + o_prog, ops, op_bytes);
+        // (cv == null: the constants are written on the device -- vanishing_device.hpp --, their room is left alone)
+        const size_t from = cv ? 0 : o_prog;
+        BZH_TRY(h2d_stage(ctx, total - from, &slot));
+        if (cv) memcpy(slot, cv, cv_bytes);
+        memcpy(slot + (o_prog - from), ops, op_bytes);
         if (ncols) {
-            memcpy(slot + o_ptrs, ptrs, ncols * 8);
-            memcpy(slot + o_strides, strides, ncols * 8);
+            memcpy(slot + (o_ptrs - from), ptrs, ncols * 8);
+            memcpy(slot + (o_strides - from), strides, ncols * 8);
         }
-        BZH_TRY(h2d_commit(ctx, dev, slot, total));
+        BZH_TRY(h2d_commit(ctx, dev + from, slot, total - from));
         out.consts = (uint32_t*)dev;
         out.prog = dev + o_prog;
         out.ptrs = dev + o_ptrs;
@@ -273,8 +275,25 @@ struct Prover : DeviceColumns<C> {
         const Fe29<SF> w = fe29_from_sat_reduced(v);
         memcpy(dst, w.l, 36);
     }
+    // run_quotient is two halves.  The first builds the program's arguments in device memory: the constant table from env (host
+    // transcripts), or only its room (cv == null: vanishing_device.hpp fills it on the device from challenges in HBM).  The
+    // second, launch_quotient, picks the flavour and launches; both callers share it.
+    bool quotient_fits(size_t size) const { return pk.q_ok && size % 128 == 0 && size == pk.en; }
+    size_t quotient_const_words() const { return q29 ? 12 : 8; }
+    int quotient_args(const Cols& reg, const void* cv, size_t cv_bytes, ProgramArgs& pa) {
+        const Program2& pg = pk.qprog;   // (the unsaturated kernel's launch carries no instructions: only the interpreter reads them)
+        return upload_program(cv, cv_bytes, pg.ops.data(), q29 ? 0 : pg.ops.size() * sizeof(ExprOp2), reg.ptr.data(), reg.stride.data(),
+                              reg.ptr.size(), pa);
+    }
     int run_quotient(const Cols& reg, size_t size, uint32_t* d_out) {
-        if (!pk.q_ok || size % 128 || size != pk.en) return BZH_E_RANGE;
+        if (!quotient_fits(size)) return BZH_E_RANGE;
+        std::vector<uint32_t> cv;
+        BZH_TRY(fill_consts(pk.qprog.consts, B, quotient_const_words(), q29 ? put_fe29 : put_saturated, cv));
+        ProgramArgs pa;
+        BZH_TRY(quotient_args(reg, cv.data(), cv.size() * 4, pa));
+        return launch_quotient(reg, size, pa, d_out);
+    }
+    int launch_quotient(const Cols& reg, size_t size, const ProgramArgs& pa, uint32_t* d_out) {
         hipFunction_t q_fn = nullptr;
         bzh_quotient_launch_fn q_builtin = nullptr;
         if (q29) {
@@ -286,10 +305,6 @@ struct Prover : DeviceColumns<C> {
         }
         const Program2& pg = pk.qprog;
         const size_t nc = pg.consts.size(), ncols = reg.ptr.size();
-        std::vector<uint32_t> cv;
-        BZH_TRY(fill_consts(pg.consts, B, q29 ? 12 : 8, q29 ? put_fe29 : put_saturated, cv));
-        ProgramArgs pa;   // (the unsaturated kernel's launch carries no instructions: only the interpreter reads them)
-        BZH_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), q29 ? 0 : pg.ops.size() * sizeof(ExprOp2), reg.ptr.data(), reg.stride.data(), ncols, pa));
         const uint32_t* const* d_ptrs = (const uint32_t* const*)pa.ptrs;
         const size_t* d_strides = (const size_t*)pa.strides;
         const uint32_t* d_consts = pa.consts;

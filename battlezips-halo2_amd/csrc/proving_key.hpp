@@ -125,6 +125,7 @@ struct QuotientPtrs {
     const uint32_t* inst = nullptr;   // ni
     const uint32_t* z = nullptr;      // nsets + nl grand products
     std::vector<const uint32_t*> lk;  // per lookup: A' | S'
+    size_t lk_cols = 2;               // columns between consecutive proofs of one lookup's pair (2: a buffer per lookup)
 };
 // The key's columns as fe29 planes (pk.key29), where each block begins, in columns of 9 en words:
 // fixed cosets | sigma cosets | l0, l_last, l_blind, X, 1/(X^n - 1) | hoisted columns
@@ -156,8 +157,8 @@ static void quotient_registry(const bzh_pk& pk, const QuotientPtrs& q, bool plan
     for (int i = 0; i < nsets; i++) reg.add(key(K_PZ, i), at(q.z, (size_t)i * en), (size_t)nz * su);
     for (int i = 0; i < nl; i++) {
         const uint32_t* c = (size_t)i < q.lk.size() ? q.lk[i] : nullptr;
-        reg.add(key(K_LA, i), c, 2 * su);
-        reg.add(key(K_LS, i), at(c, en), 2 * su);
+        reg.add(key(K_LA, i), c, q.lk_cols * su);
+        reg.add(key(K_LS, i), at(c, en), q.lk_cols * su);
         reg.add(key(K_LZ, i), at(q.z, (size_t)(nsets + i) * en), (size_t)nz * su);
     }
     static const int misc[5] = {M_L0, M_LLAST, M_LBLIND, M_X, M_TINV};

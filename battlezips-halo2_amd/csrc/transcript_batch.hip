@@ -274,6 +274,7 @@ int tb_squeeze_locked(bzh_transcript_batch* tb, int form, uint32_t* d_out) {
     return BZH_OK;
 }
 const uint8_t* tb_status_device(const bzh_transcript_batch* tb) { return tb->S.status; }
+uint8_t* tb_status_device_mut(bzh_transcript_batch* tb) { return tb->S.status; }
 
 }  // namespace bzh
 

@@ -417,6 +417,66 @@ int bzh_evaluations_batch_device(bzh_ctx* ctx, size_t batch, unsigned k, const u
                                  size_t npieces, size_t h_stride, const uint64_t* h_blinds, int form, int mem,
                                  struct bzh_transcript_batch* transcripts, uint64_t* out_points, uint64_t* out_evals, uint64_t* out_h,
                                  uint64_t* out_h_blind);
+/* The vanishing argument of plonk::create_proof against a device-resident bzh_transcript_batch -- csrc/vanishing_device.hpp,
+ * csrc/vanishing.hip, csrc/vanishing_scalars.hpp: the step between the grand products and the evaluations, the vanishing() phase
+ * of bzh_prove_batch as a leaf, with theta, beta, gamma and y in HBM.  Its out_h goes into bzh_evaluations_batch_device as
+ * h_pieces with h_stride = the extended size, its out_h_blinds as h_blinds and its out_random as one more own polynomial, so the
+ * arguments from the random polynomial's commitment on (vanishing, evaluations, multiopen, opening) run back to back on a device
+ * batch.  Its speed has not been measured.
+ *
+ * bzh_vanishing_plan is pure host code (no ctx, no device), like bzh_quotient_program_for_circuit.  shape8: n, the extended size
+ * en, num_advice, num_instance, nz (permutation sets + lookups), the number of lookups, npieces, and the draws per proof
+ * (n + 1 + npieces).  consts / *nconsts: one bzh_vanishing_const per entry of the circuit's VM v2 constant table, in the table's
+ * order (consts_cap counts entries).  A literal (challenge -1) carries its value; a symbol means value * challenge^exponent in
+ * Montgomery form: theta, beta, gamma, y are (0 .. 3, 1, one), y^m is (3, m, one) with m <= 64, and beta * delta^j -- the
+ * permutation argument's column j -- is (1, 1, delta^j); delta^j depends on the key alone and is computed here.  BZH_E_RANGE if
+ * the circuit does not fit VM v2.  BZH_E_ARG, nothing written: a NULL pointer, a blob that does not parse, consts_cap below the
+ * number of constants.
+ *
+ * bzh_vanishing_batch_device takes its operands in the prover's own layouts, n = 2^k coefficients each: advice_polys[b][i][n],
+ * instance_polys[b][i][n], lookup_polys[b][l][2][n] (the permuted input, then the permuted table) and z_polys[b][nz][n] (the
+ * permutation sets' grand products, then the lookups'); an operand whose count is 0 may be NULL.  theta, beta, gamma: one element
+ * per proof each, as bzh_transcript_batch_squeeze writes them.  `form` and `mem` apply to every data pointer, as in the three
+ * calls above: with BZH_MEM_DEVICE they are 16-byte-aligned device pointers (`status` any alignment) and the call only enqueues;
+ * with BZH_MEM_HOST the operands are staged up once at the start and the outputs read back once at the end.  rng: proof b's
+ * 64-byte draws at rng + b * rng_stride, in upstream's order -- the n coefficients of the random polynomial, its blind, the
+ * npieces piece blinds --, so rng_stride >= 64 * (n + 1 + npieces).
+ * Messages, per proof, in upstream's order: WRITE the commitment of the random polynomial; squeeze y; WRITE the commitment of each
+ * piece h[i * n .. (i + 1) * n), i < npieces, under its blind.  The proof grows by 32 * (1 + npieces) bytes; x is not squeezed.
+ * Outputs, in `form`: out_random[b][n] and out_random_blind[b]; out_h[b][en], the quotient's coefficients, all en of them;
+ * out_h_blinds[b][npieces]; status (may be NULL), one byte per proof: bit 0 is set when a coefficient at or above npieces * n is
+ * non-zero -- the witness does not satisfy the circuit.  Such a proof still gets its messages, built from the low coefficients,
+ * disturbs no other proof, and the call returns BZH_OK; the bit is also ORed into the batch's sticky status byte.  A circuit
+ * whose pieces fill the extended domain (npieces * n == en: degree 3, 5, 9 ..) has no such coefficient and never sets the bit.
+ * The quotient runs in the flavour the key has selected (bzh_pk_quotient_select), with the launches of bzh_prove_batch, from a
+ * constant table that one launch builds on the device out of the challenges; the plan's descriptors are uploaded before the
+ * first launch.  Between its first launch and its last the call copies nothing that depends on a challenge to the host, does no
+ * host field or curve arithmetic on such a value and adds no stream synchronisation of its own.  The scratch -- the extended
+ * cosets of every column, the commitments' scalar rows -- is the key's workspace for this ctx, as in bzh_prove_batch, and the
+ * call counts as running on the key like every other call on it (bzh_pk_free).  A BZH_MEM_DEVICE call returns with its work
+ * queued on that workspace.  The workspace grows during a key's first call of a shape on a ctx and is merged into one block at
+ * the start of the next call on that key and ctx, which therefore waits once for the stream, before its own first launch; the
+ * calls after it wait for nothing.
+ * BZH_E_ARG, the batch left as it was and nothing written: a NULL ctx, pk, transcripts, rng, challenge, output or required
+ * operand pointer; a host-resident batch; a batch of another ctx, curve or size; a key on another device than ctx; batch == 0
+ * or > 65535, or batch * npieces > 65535 (the piece commitments of a batch are one launch with one row of its grid per
+ * commitment: at most 8191 proofs for Shot and Board, whose npieces is 8); unknown form or mem; a misaligned device pointer; rng_stride too small.  BZH_E_RANGE, nothing absorbed: proof_cap
+ * cannot take 32 * (1 + npieces) more bytes; the key's circuit does not fit VM v2 or its extended size is no multiple of 128
+ * (the VM v1 fold is not offered here).  Every check that reads neither the key nor the device comes first, then those that read
+ * the key; all of them come before the first use of ctx. */
+typedef struct {
+    int32_t challenge; /* -1 literal, 0 theta, 1 beta, 2 gamma, 3 y */
+    uint32_t exponent;
+    uint32_t value[8]; /* Montgomery */
+} bzh_vanishing_const;
+int bzh_vanishing_plan(int curve, const uint8_t* circuit, size_t circuit_len, uint32_t shape8[8], bzh_vanishing_const* consts,
+                       size_t consts_cap, size_t* nconsts);
+struct bzh_pk; /* (a proving key: the next section) */
+int bzh_vanishing_batch_device(bzh_ctx* ctx, struct bzh_pk* pk, size_t batch, const uint64_t* advice_polys, const uint64_t* instance_polys,
+                               const uint64_t* lookup_polys, const uint64_t* z_polys, const uint64_t* theta, const uint64_t* beta,
+                               const uint64_t* gamma, int form, int mem, const uint8_t* rng, size_t rng_stride,
+                               struct bzh_transcript_batch* transcripts, uint64_t* out_random, uint64_t* out_random_blind,
+                               uint64_t* out_h, uint64_t* out_h_blinds, uint8_t* status);
 int bzh_ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                    const uint8_t* proof, size_t proof_len, bzh_transcript* transcript, const uint64_t* g0_u_w);
 
