@@ -562,7 +562,10 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
     uint32_t* s_cur = take(B * n * 8);
     uint32_t* s_nxt = take(B * n * 8);
     uint32_t* d_lr = take(B * 2 * (n + 4) * 8);
-    const bool paired = bases->pre_c != 0 && k >= 1;  // window table: L_j and R_j of a proof share one dense vector
+    // window table: L_j and R_j of a proof share one dense vector (msm_run_paired).  Its 16-bit digits hold bucket + class * M below
+    // 2^15, so a table of width c = 15 (M = 2^14; bzh_bases_precompute accepts it) takes the two-vector rounds instead.  A tail
+    // table has c <= 13: once collapsed, the rounds always pair.
+    auto pairs = [](const bzh_bases* t) { return t->pre_c != 0 && t->pre_c <= 14; };
     uint32_t* d_commit = take(B * (n + 2) * 8);
     uint32_t* d_tail_table = jstar ? take(B * (tail_m + 2) * (size_t)tail_nwin * 16) : nullptr;
     uint32_t* d_tail_table29 = jstar ? take(B * (tail_m + 2) * (size_t)tail_nwin * 20) : nullptr;
@@ -619,13 +622,13 @@ static int ipa_open_t(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_po
         }
         const size_t m = n >> j, half = m >> 1, cnt = (size_t)1 << (j - j0);
         hipLaunchKernelGGL((k_ipa_inner2<SF>), dim3((unsigned)B, 2), dim3(256), 0, st, p_cur, b_cur, half, d_vlr);
-        if (paired) {
+        if (pairs(rb)) {
             hipLaunchKernelGGL((k_ipa_round_vectors_paired<SF>), grid2(rn + 1), dim3(g256), 0, st, p_cur, s_cur, rn, k - j, d_vlr, d_hc,
                                d_rand, nrand, n, j, d_lr);
             BZH_HIP_TRY(ctx, hipGetLastError());
             drv.msm_begin(ctx);
             BZH_TRY(msm_run_paired(ctx, rb, d_lr, rn, k - j, B, BZH_FORM_MONTGOMERY, (uint32_t*)d_out));
-        } else {
+        } else {   // (rb is the SRS here)
             hipLaunchKernelGGL((k_ipa_round_vectors<SF>), grid2(n + 1), dim3(g256), 0, st, p_cur, s_cur, n, k - j, d_vlr, d_hc,
                                d_rand, nrand, n, j, d_lr);
             BZH_HIP_TRY(ctx, hipGetLastError());

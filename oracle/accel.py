@@ -5,6 +5,8 @@ order, blinding rows, query grouping, constraint order -- stays in halo2_oracle.
 
 `with accelerated(threads):` swaps, for the duration of the block,
   Curve.msm_naive            -> orc_msm  (upstream best_multiexp, thread-chunked Pippenger)
+  Curve.mul                  -> orc_msm on one point (the big-int double-and-add inverts per addition: 40 ms a call, most of
+                                an opening's time once the MSMs are the C oracle's)
   Domain.lagrange_to_coeff / coeff_to_extended / extended_to_coeff -> orc_ntt (upstream best_fft)
   pasta.eval_polynomial      -> orc_eval_poly (Horner)
   pasta.fold_bases           -> orc_generator_collapse (parallel_generator_collapse)
@@ -66,11 +68,17 @@ def _quotient_evals(threads):
 def accelerated(threads: int = 8):
     C.lib()
     saved = (O.Curve.msm_naive, H.Domain.lagrange_to_coeff, H.Domain.coeff_to_extended, H.Domain.extended_to_coeff,
-             O.eval_polynomial, O.fold_bases, H.quotient_evals)
+             O.eval_polynomial, O.fold_bases, H.quotient_evals, O.Curve.mul)
 
     def msm(self, scalars, points):
         p = self.scalar.p
         return C.array_to_point(C.msm(_CID[self.name], C.ints_to_array([int(s) % p for s in scalars]), C.points_to_array(points), threads))
+
+    def mul(self, k, pt):
+        k %= self.scalar.p
+        if pt is None or k == 0:
+            return None
+        return C.array_to_point(C.msm(_CID[self.name], C.ints_to_array([k]), C.points_to_array([pt]), 1))
 
     def lagrange_to_coeff(self, v):
         return C.array_to_ints(C.ntt(_fid(self.F), C.ints_to_array(v), self.omega, inverse=True, threads=threads))
@@ -92,11 +100,11 @@ def accelerated(threads: int = 8):
         out = C.generator_collapse(_CID[curve.name], C.points_to_array(g), u, threads)
         return [C.array_to_point(out[i]) for i in range(out.shape[0])]
 
-    O.Curve.msm_naive = msm
+    O.Curve.msm_naive, O.Curve.mul = msm, mul
     H.Domain.lagrange_to_coeff, H.Domain.coeff_to_extended, H.Domain.extended_to_coeff = lagrange_to_coeff, coeff_to_extended, extended_to_coeff
     O.eval_polynomial, O.fold_bases, H.quotient_evals = eval_polynomial, fold_bases, _quotient_evals(threads)
     try:
         yield
     finally:
         (O.Curve.msm_naive, H.Domain.lagrange_to_coeff, H.Domain.coeff_to_extended, H.Domain.extended_to_coeff,
-         O.eval_polynomial, O.fold_bases, H.quotient_evals) = saved
+         O.eval_polynomial, O.fold_bases, H.quotient_evals, O.Curve.mul) = saved
