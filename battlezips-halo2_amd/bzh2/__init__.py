@@ -909,6 +909,52 @@ class TranscriptBatch:
                                                  _vp(h), _vp(hb), _vp(st)), where)
         return rp, rb, h, hb, st
 
+    def grand_products(self, pk, advice, instance, lookup_compressed, lookup_permuted, beta, gamma, rng_list, *, form: int = FORM_CANONICAL,
+                       mem: int = MEM_HOST, out_z=None, out_z_polys=None, out_z_blinds=None, status=None, rng_stride: int | None = None,
+                       batch: int | None = None, shape=None, want_z: bool = True):
+        """the permutation and lookup grand products of `batch` proofs against this device-resident batch
+        (bzh_grand_products_batch_device): every product is built from beta and gamma where they lie, and its commitment written,
+        with no host trip in between.  The outputs chain into vanishing(): z_polys is its z_polys operand.
+        MEM_HOST: advice (batch, num_advice, n, 4) and instance (batch, num_instance, n, 4) uint64 evaluations over the domain in
+        `form`, blinding rows in place; lookup_compressed and lookup_permuted (batch, lookups, 2, n, 4) (None where the count is
+        0); beta, gamma (batch, 4); rng_list: one byte string of 64 * nz * (bf + 1) draws per proof.  Returns (z, z_polys,
+        z_blinds, status): (batch, nz, n, 4) twice (z is None with want_z false) and (batch, nz, 4) uint64 in `form`, and
+        (batch,) uint8 -- 1: a product of that proof does not close.  `shape`: grand_products_plan(), which sizes the outputs;
+        None: pk.grand_products_plan(), computed for this call.
+        MEM_DEVICE: every operand and output is a device pointer (int, 16-byte aligned; `status` any alignment, or None; out_z may
+        be None), rng_list the pointer to the draws (proof b at + b * rng_stride).  Enqueues only, returns None."""
+        L = load()
+        vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+        L.bzh_grand_products_batch_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, ci, ci, vp, sz, vp, vp, vp, vp, vp]
+        ctxh = self.ctx.handle if self.ctx is not None else None
+        pkh = pk.handle if hasattr(pk, "handle") else pk
+        where = "bzh_grand_products_batch_device"
+        if mem == MEM_DEVICE:
+            ptr = lambda v: ctypes.c_void_p(int(v)) if v else None  # noqa: E731
+            self._check(L.bzh_grand_products_batch_device(ctxh, pkh, self.batch if batch is None else batch, ptr(advice), ptr(instance),
+                                                          ptr(lookup_compressed), ptr(lookup_permuted), ptr(beta), ptr(gamma), form, mem,
+                                                          ptr(rng_list), rng_stride or 0, self.h, ptr(out_z), ptr(out_z_polys),
+                                                          ptr(out_z_blinds), ptr(status)), where)
+            return None
+        B = len(rng_list)
+        if shape is None:
+            if not hasattr(pk, "grand_products_plan"):
+                raise TypeError("TranscriptBatch.grand_products: `shape` is required when pk is a bare handle")
+            shape = pk.grand_products_plan()
+        n, nz = shape[0], shape[5]
+        arr = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.uint64))  # noqa: E731
+        opt = lambda a: _vp(a) if a is not None and a.size else None  # noqa: E731
+        ops = [arr(a) for a in (advice, instance, lookup_compressed, lookup_permuted, beta, gamma)]
+        stride = len(rng_list[0])
+        assert all(len(r) == stride for r in rng_list)
+        raw = np.frombuffer(b"".join(rng_list), dtype=np.uint8)
+        z = np.zeros((B, nz, n, 4), dtype=np.uint64) if want_z else None
+        zp, zb = np.zeros((B, nz, n, 4), dtype=np.uint64), np.zeros((B, nz, 4), dtype=np.uint64)
+        st = np.zeros(B, dtype=np.uint8)
+        self._check(L.bzh_grand_products_batch_device(ctxh, pkh, B, *[opt(a) for a in ops], form, mem, _vp(raw), stride, self.h,
+                                                      _vp(z) if want_z else None, _vp(zp), _vp(zb), _vp(st)), where)
+        return z, zp, zb, st
+
     def close(self):
         if self.h is not None:
             load().bzh_transcript_batch_free(self.h)
@@ -1013,6 +1059,22 @@ def vanishing_plan(curve: int, circuit_blob: bytes):
         raise BzhError(rc, "bzh_vanishing_plan")
     value = lambda w: sum(int(x) << (32 * i) for i, x in enumerate(w))  # noqa: E731
     return tuple(int(x) for x in shape), [(int(c["challenge"]), int(c["exponent"]), value(c["value"])) for c in consts[:got.value]]
+
+
+EXPORTS += ["bzh_grand_products_plan", "bzh_grand_products_batch_device"]
+
+
+def grand_products_plan(curve: int, circuit_blob: bytes):
+    """what the grand products derive from a circuit (bzh_grand_products_plan, host only): (n, usable rows, blinding factors,
+    permutation sets, lookups, nz = sets + lookups, columns per set, draws per proof = nz * (blinding factors + 1))"""
+    L = load()
+    L.bzh_grand_products_plan.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
+    blob = bytes(circuit_blob)
+    shape = np.zeros(8, dtype=np.uint32)
+    rc = L.bzh_grand_products_plan(curve, blob, len(blob), _vp(shape))
+    if rc != OK:
+        raise BzhError(rc, "bzh_grand_products_plan")
+    return tuple(int(x) for x in shape)
 
 
 EXPORTS += ["bzh_pk_create", "bzh_pk_free", "bzh_pk_set_lagrange", "bzh_pk_quotient_stats", "bzh_pk_quotient_source", "bzh_pk_set_quotient_module", "bzh_pk_info", "bzh_prove_batch", "bzh_prove_batch_seeded", "bzh_rng_expand", "bzh_verify_batch",

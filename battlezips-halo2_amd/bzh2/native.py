@@ -165,6 +165,11 @@ class NativeProvingKey:
         from . import vanishing_plan
         return vanishing_plan(self.curve, self.blob)
 
+    def grand_products_plan(self):
+        """the shape of bzh2.grand_products_plan for this key's circuit: what TranscriptBatch.grand_products takes as `shape`"""
+        from . import grand_products_plan
+        return grand_products_plan(self.curve, self.blob)
+
     def quotient_stats(self) -> dict:
         L = _bind()
         L.bzh_pk_quotient_stats.argtypes = [_VP] + [ctypes.POINTER(ctypes.c_uint32)] * 4

@@ -409,6 +409,18 @@ int evaluations_device(bzh_ctx* ctx, int curve, size_t batch, unsigned k, const 
 int vanishing_consts(bzh_ctx* ctx, int field, const void* d_descs, size_t nconsts, size_t batch, const uint32_t* d_theta,
                      const uint32_t* d_beta, const uint32_t* d_gamma, const uint32_t* d_y, int form, bool planes29, uint32_t* d_table);
 int vanishing_degree(bzh_ctx* ctx, const uint32_t* d_h, size_t first, size_t pitch, size_t batch, uint8_t* d_status, uint8_t* d_sticky);
+// products.hip: the two kernels of bzh_grand_products_batch_device (the call itself reads the key: csrc/products_device.hpp); device
+// pointers, 16-byte aligned unless said otherwise, Montgomery unless said otherwise; enqueue only.
+// products_factors: the numerator d_num[p][b][row] and denominator d_den[p][b][row] of every grand product's factors, nsets
+// permutation sets and then nl lookups, from the column table d_cols (GpCol) / d_prods (GpProd, one per product) of
+// products_scalars.hpp; d_beta / d_gamma batch elements each in `form`.  products_finish: d_raw is that buffer after the inversion,
+// the product and the exclusive scan; d_drawn[b][p][bf + 1] the reduced draws (the bf blinding rows, then the blind);
+// d_z[b][p][row] = raw * the set's carry, the draws in rows n - bf .. n - 1; d_blinds[b][p]; d_status[b] (any alignment, may be
+// null) = bit 0: a product of proof b does not close, ORed into d_sticky[b].
+int products_factors(bzh_ctx* ctx, int field, const void* d_cols, const void* d_prods, size_t nsets, size_t nl, size_t n, size_t batch,
+                     const uint32_t* d_beta, const uint32_t* d_gamma, int form, uint32_t* d_num, uint32_t* d_den);
+int products_finish(bzh_ctx* ctx, int field, const uint32_t* d_raw, const uint32_t* d_drawn, size_t n, size_t usable, size_t bf, size_t nsets,
+                    size_t nl, size_t batch, uint32_t* d_z, uint32_t* d_blinds, uint8_t* d_status, uint8_t* d_sticky);
 int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                const uint8_t* proof, size_t proof_len, bzh_transcript* tr, const uint64_t* g0_u_w_xy);
 int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,

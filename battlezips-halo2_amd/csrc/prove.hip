@@ -43,6 +43,7 @@
 #include "fe29.cuh"
 #include "host_field.hpp"
 #include "vanishing_scalars.hpp"   // (bzh_vanishing_const as the lane body reads it)
+#include "products_scalars.hpp"    // (the column table as k_gp_factors reads it)
 #include "vm2_isa.hpp"
 
 // the table of quotient kernels generated at build time (quotient_builtin.hip); absent (null) in the generator's own link
@@ -58,6 +59,7 @@ extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __at
 #include "device_columns.hpp"     // columns on the device, their commitments: shared by prover, verifier and keygen_vk
 #include "prover.hpp"
 #include "vanishing_device.hpp"   // phase 5 of the prover as a leaf on device-resident transcripts
+#include "products_device.hpp"    // phase 4 likewise
 #include "verifier.hpp"
 
 // pk.get_vk(): the commitments to the fixed and permutation polynomials (blind 1), computed once per key
@@ -634,6 +636,56 @@ int bzh_vanishing_batch_device(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uin
     const int rc = bzh::with_pasta_curve(pk->curve, [&](auto c) {
         return bzh::vanishing_device_t<decltype(c)>(ctx, pk, batch, advice_polys, instance_polys, lookup_polys, z_polys, theta, beta, gamma, form,
                                                     mem, rng, rng_stride, transcripts, out_random, out_random_blind, out_h, out_h_blinds, status);
+    });
+    if (rc && !ctx->pending_d2h.empty()) {   // a host call that failed between its read-backs and their end: they must not land later
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->pending_d2h.clear();
+    }
+    return rc;
+}
+
+int bzh_grand_products_plan(int curve, const uint8_t* circuit, size_t circuit_len, uint32_t shape8[8]) {
+    if (!circuit || !shape8) return BZH_E_ARG;
+    bzh_pk pk;
+    BZH_TRY(bzh::with_pasta_curve(curve, [&](auto c) {
+        bzh::ParsedKey<typename bzh::CurveInfo<decltype(c)>::SF> po;
+        return bzh::pk_parse_t<decltype(c)>(circuit, circuit_len, pk, po);
+    }));
+    const uint32_t nz = (uint32_t)(pk.nsets + pk.nl);
+    const uint32_t shape[8] = {(uint32_t)pk.n, (uint32_t)pk.usable, (uint32_t)pk.bf, (uint32_t)pk.nsets, (uint32_t)pk.nl, nz, (uint32_t)pk.chunk_len,
+                               nz * (uint32_t)(pk.bf + 1)};
+    memcpy(shape8, shape, sizeof(shape));
+    return BZH_OK;
+}
+
+int bzh_grand_products_batch_device(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice, const uint64_t* instance,
+                                    const uint64_t* lookup_compressed, const uint64_t* lookup_permuted, const uint64_t* beta,
+                                    const uint64_t* gamma, int form, int mem, const uint8_t* rng, size_t rng_stride,
+                                    bzh_transcript_batch* transcripts, uint64_t* out_z, uint64_t* out_z_polys, uint64_t* out_z_blinds,
+                                    uint8_t* status) {
+    // what reads neither the key nor the device
+    if (!ctx || !pk || !transcripts || !rng || !beta || !gamma || !out_z_polys || !out_z_blinds) return BZH_E_ARG;
+    if (!batch || batch > 65535 || (form != BZH_FORM_CANONICAL && form != BZH_FORM_MONTGOMERY) || (mem != BZH_MEM_HOST && mem != BZH_MEM_DEVICE))
+        return BZH_E_ARG;
+    const bzh::TbInfo ti = bzh::tb_info(transcripts);
+    if (!ti.ctx) return BZH_E_ARG;   // a host-resident batch
+    bzh::KeyRuntime::Call in_flight(pk->rt);   // registered before the wait for ctx->mu, like every other call on a key
+    // what reads the key
+    const size_t nz = (size_t)(pk->nsets + pk->nl);
+    if (pk->device != ctx->device || ti.ctx != ctx || ti.curve != pk->curve || ti.batch != batch) return BZH_E_ARG;
+    if ((pk->na && !advice) || (pk->ni && !instance) || (pk->nl && (!lookup_compressed || !lookup_permuted))) return BZH_E_ARG;
+    // (batch * nz: ipa_commit_blinded puts the number of commitments into grid.y, and the commitments of a batch are one launch)
+    if (rng_stride < 64 * nz * (size_t)(pk->bf + 1) || batch * nz > 65535) return BZH_E_ARG;
+    const uintptr_t all = (uintptr_t)advice | (uintptr_t)instance | (uintptr_t)lookup_compressed | (uintptr_t)lookup_permuted | (uintptr_t)beta |
+                          (uintptr_t)gamma | (uintptr_t)rng | (uintptr_t)out_z | (uintptr_t)out_z_polys | (uintptr_t)out_z_blinds;
+    if (mem == BZH_MEM_DEVICE && (all & 15)) return BZH_E_ARG;
+    if (!nz) return BZH_OK;   // no permutation and no lookup: nothing to write
+    if (ti.proof_len + 32 * nz > ti.proof_cap) return BZH_E_RANGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = bzh::with_pasta_curve(pk->curve, [&](auto c) {
+        return bzh::products_device_t<decltype(c)>(ctx, pk, batch, advice, instance, lookup_compressed, lookup_permuted, beta, gamma, form, mem, rng,
+                                                   rng_stride, transcripts, out_z, out_z_polys, out_z_blinds, status);
     });
     if (rc && !ctx->pending_d2h.empty()) {   // a host call that failed between its read-backs and their end: they must not land later
         (void)hipStreamSynchronize(ctx->stream);

@@ -46,6 +46,42 @@ static int vanishing_consts_plan(const bzh_pk& pk, std::vector<VnConst>& out) {
 }
 static_assert(SY_THETA == 0 && SY_BETA == 1 && SY_GAMMA == 2 && SY_Y == 3, "bzh_vanishing_const numbers the challenges like the symbols");
 
+// Two steps every leaf on the key's arena shares (vanishing_device_t below, products_device.hpp).
+// the first `nd` 64-byte draws of every proof (proof b at rng + b * rng_stride: host memory, or device memory with `host` false),
+// reduced into drawn[b][nd]: one upload or one strided device copy of the batch's bytes, none when they already lie dense
+template <class C>
+static int leaf_draws(Prover<C>& pv, bool host, const uint8_t* rng, size_t rng_stride, size_t nd, uint32_t* drawn) {
+    bzh_ctx* ctx = pv.ctx;
+    const size_t B = pv.B;
+    const uint8_t* raw = rng;
+    if (host) {
+        char* stage = nullptr;
+        uint8_t* d = (uint8_t*)pv.arena.alloc(B * nd * 64);
+        if (!d) return BZH_E_OOM;
+        BZH_TRY(h2d_stage(ctx, B * nd * 64, &stage));
+        for (size_t b = 0; b < B; b++) memcpy(stage + b * nd * 64, rng + b * rng_stride, nd * 64);
+        BZH_TRY(h2d_commit(ctx, d, stage, B * nd * 64));
+        raw = d;
+    } else if (rng_stride != nd * 64) {
+        uint8_t* d = (uint8_t*)pv.arena.alloc(B * nd * 64);
+        if (!d) return BZH_E_OOM;
+        BZH_HIP_TRY(ctx, hipMemcpy2DAsync(d, nd * 64, rng, rng_stride, nd * 64, B, hipMemcpyDeviceToDevice, pv.st));
+        raw = d;
+    }
+    return random_field(ctx, pv.field, (const uint32_t*)raw, B * nd, drawn);
+}
+// `count` polynomials of n coefficients under their blinds in device memory, into the transcripts: `per_proof` points each
+template <class C>
+static int leaf_commit_write(Prover<C>& pv, bzh_transcript_batch* tb, const uint32_t* polys, const uint32_t* blinds, size_t count,
+                             size_t per_proof) {
+    ArenaScope scope(pv.arena);   // (dead once enqueued: everything that reuses the memory is queued behind it on the one stream)
+    uint32_t* scalars = pv.dalloc(count * (pv.n + 2));
+    uint32_t* xyz = pv.dalloc(count * 3);
+    if (!scalars || !xyz) return BZH_E_OOM;
+    BZH_TRY(ipa_commit_blinded(pv.ctx, pv.pk.srs, polys, count, blinds, scalars, xyz));
+    return tb_write_jacobian_locked(tb, xyz, per_proof, per_proof, BZH_FORM_MONTGOMERY);
+}
+
 // the call, for a caller that holds ctx->mu and has made every argument check
 template <class C>
 static int vanishing_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t* advice_polys, const uint64_t* instance_polys,
@@ -115,35 +151,12 @@ static int vanishing_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t
     if (!rp || !rb || !h || !hb || (host && !d_st) || !d_y || !drawn) return BZH_E_OOM;
 
     // the draws: one upload of the batch's bytes, reduced, then scattered into the random polynomial, its blind, the piece blinds
-    {
-        const uint8_t* raw = rng;
-        if (host) {
-            char* stage = nullptr;
-            uint8_t* d = (uint8_t*)arena.alloc(B * nd * 64);
-            if (!d) return BZH_E_OOM;
-            BZH_TRY(h2d_stage(ctx, B * nd * 64, &stage));
-            for (size_t b = 0; b < B; b++) memcpy(stage + b * nd * 64, rng + b * rng_stride, nd * 64);
-            BZH_TRY(h2d_commit(ctx, d, stage, B * nd * 64));
-            raw = d;
-        } else if (rng_stride != nd * 64) {
-            uint8_t* d = (uint8_t*)arena.alloc(B * nd * 64);
-            if (!d) return BZH_E_OOM;
-            BZH_HIP_TRY(ctx, hipMemcpy2DAsync(d, nd * 64, rng, rng_stride, nd * 64, B, hipMemcpyDeviceToDevice, st));
-            raw = d;
-        }
-        BZH_TRY(random_field(ctx, field, (const uint32_t*)raw, B * nd, drawn));
-        BZH_TRY(pv.copy2d(rp, n, drawn, nd, n, B));
-        BZH_TRY(pv.copy2d(rb, 1, drawn + n * 8, nd, 1, B));
-        BZH_TRY(pv.copy2d(hb, npieces, drawn + (n + 1) * 8, nd, npieces, B));
-    }
-    // `count` polynomials of n coefficients under their blinds, into the transcripts: `per_proof` points each
+    BZH_TRY(leaf_draws(pv, host, rng, rng_stride, nd, drawn));
+    BZH_TRY(pv.copy2d(rp, n, drawn, nd, n, B));
+    BZH_TRY(pv.copy2d(rb, 1, drawn + n * 8, nd, 1, B));
+    BZH_TRY(pv.copy2d(hb, npieces, drawn + (n + 1) * 8, nd, npieces, B));
     auto commit_write = [&](const uint32_t* polys, const uint32_t* blinds, size_t count, size_t per_proof) -> int {
-        ArenaScope scope(arena);   // (dead once enqueued: everything that reuses the memory is queued behind it on the one stream)
-        uint32_t* scalars = pv.dalloc(count * (n + 2));
-        uint32_t* xyz = pv.dalloc(count * 3);
-        if (!scalars || !xyz) return BZH_E_OOM;
-        BZH_TRY(ipa_commit_blinded(ctx, pk->srs, polys, count, blinds, scalars, xyz));
-        return tb_write_jacobian_locked(tb, xyz, per_proof, per_proof, BZH_FORM_MONTGOMERY);
+        return leaf_commit_write(pv, tb, polys, blinds, count, per_proof);
     };
     BZH_TRY(commit_write(rp, rb, B, 1));
     BZH_TRY(tb_squeeze_locked(tb, BZH_FORM_MONTGOMERY, d_y));

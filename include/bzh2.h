@@ -477,6 +477,54 @@ int bzh_vanishing_batch_device(bzh_ctx* ctx, struct bzh_pk* pk, size_t batch, co
                                const uint64_t* gamma, int form, int mem, const uint8_t* rng, size_t rng_stride,
                                struct bzh_transcript_batch* transcripts, uint64_t* out_random, uint64_t* out_random_blind,
                                uint64_t* out_h, uint64_t* out_h_blinds, uint8_t* status);
+/* The permutation and lookup grand products of plonk::create_proof against a device-resident bzh_transcript_batch --
+ * csrc/products_device.hpp, csrc/products.hip, csrc/products_scalars.hpp: the step between the squeeze of beta and gamma and the
+ * vanishing argument, the grand_products() phase of bzh_prove_batch as a leaf, with beta and gamma in HBM.  Its out_z_polys is
+ * the z_polys operand of bzh_vanishing_batch_device and its out_z_blinds goes into the multiopen's blind table, so the arguments
+ * from the grand products on (grand products, vanishing, evaluations, multiopen, opening) run back to back on a device batch.
+ *
+ * bzh_grand_products_plan is pure host code (no ctx, no device).  shape8: n, the usable rows, the blinding factors bf, the
+ * permutation sets nsets, the lookups nl, nz = nsets + nl, the columns per permutation set chunk_len, and the draws per proof
+ * nz * (bf + 1).  BZH_E_ARG, nothing written: a NULL pointer, an unknown curve, a blob that does not parse.
+ *
+ * bzh_grand_products_batch_device takes the witness over the domain, n = 2^k rows each, blinding rows in place: advice[b][na][n],
+ * instance[b][ni][n], lookup_compressed[b][l][2][n] (the compressed input a_c, then the compressed table s_c) and
+ * lookup_permuted[b][l][2][n] (the permuted pair a, s with their blinding rows); an operand whose count is 0 may be NULL.  The
+ * fixed columns, sigma and the identity rows delta^j omega^r are the key's.  beta, gamma: one element per proof each, as
+ * bzh_transcript_batch_squeeze writes them.  `form` and `mem` apply to every data pointer, as in the four calls above: with
+ * BZH_MEM_DEVICE they are 16-byte-aligned device pointers (`status` any alignment) and the call only enqueues; with BZH_MEM_HOST
+ * the operands are staged up once at the start and the outputs read back once at the end.  rng: proof b's 64-byte draws at
+ * rng + b * rng_stride, in upstream's order -- per product, permutation sets first and then lookups, the bf blinding rows
+ * n - bf .. n - 1 and then the blind --, so rng_stride >= 64 * nz * (bf + 1).
+ * Messages, per proof: WRITE the nz commitments in product order, the coefficients committed under the drawn blinds.  The proof
+ * grows by 32 * nz bytes; nothing is squeezed.
+ * Outputs, in `form`: out_z[b][nz][n] (may be NULL), the products over the domain; out_z_polys[b][nz][n], their coefficients;
+ * out_z_blinds[b][nz]; status (may be NULL), one byte per proof: 1 when the last permutation set's z[usable] is not 1 or a
+ * lookup product's z[usable] is not 1 -- a copy constraint or a lookup of that witness does not hold --, else 0.  Such a proof
+ * still gets its messages, disturbs no other proof, and the call returns BZH_OK; the bit is also ORed into the batch's sticky
+ * status byte.  A zero denominator is left zero by the batch inversion, as upstream's batch_invert leaves it: that product is 0
+ * from the next row on, in that proof alone.
+ * One launch (k_gp_factors) writes the numerator and the denominator of every product's factors, reading the columns in place
+ * through a table built from the key and uploaded before the first launch; the inversion, the product and the scan are those of
+ * bzh_prove_batch; one launch (k_gp_finish) chains the permutation sets -- set i is its own scanned product times the z[usable]
+ * of the sets before it --, places the blinding rows and the blinds and sets the status.  Between its first launch and its last
+ * the call copies nothing that depends on a challenge to the host, does no host field arithmetic on such a value, adds no stream
+ * synchronisation of its own and runs no expression program.  The scratch is the key's workspace for this ctx, under the rule
+ * bzh_vanishing_batch_device states: a BZH_MEM_DEVICE call returns with its work queued on it, and the call that merges the
+ * workspace's blocks waits once for the stream before its own first launch.  A key with nz == 0 returns BZH_OK with nothing
+ * written.  Its speed against the host path: DESIGN.md section 7.
+ * BZH_E_ARG, the batch left as it was and nothing written: a NULL ctx, pk, transcripts, rng, beta, gamma, out_z_polys,
+ * out_z_blinds or required operand pointer; a host-resident batch; a batch of another ctx, curve or size; a key on another device
+ * than ctx; batch == 0 or > 65535, or batch * nz > 65535 (the commitments of a batch are one launch with one row of its grid per
+ * commitment); unknown form or mem; a misaligned device pointer; rng_stride too small.  BZH_E_RANGE, nothing absorbed: proof_cap
+ * cannot take 32 * nz more bytes.  Every check that reads neither the key nor the device comes first, then those that read the
+ * key; all of them come before the first use of ctx. */
+int bzh_grand_products_plan(int curve, const uint8_t* circuit, size_t circuit_len, uint32_t shape8[8]);
+int bzh_grand_products_batch_device(bzh_ctx* ctx, struct bzh_pk* pk, size_t batch, const uint64_t* advice, const uint64_t* instance,
+                                    const uint64_t* lookup_compressed, const uint64_t* lookup_permuted, const uint64_t* beta,
+                                    const uint64_t* gamma, int form, int mem, const uint8_t* rng, size_t rng_stride,
+                                    struct bzh_transcript_batch* transcripts, uint64_t* out_z, uint64_t* out_z_polys, uint64_t* out_z_blinds,
+                                    uint8_t* status);
 int bzh_ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                    const uint8_t* proof, size_t proof_len, bzh_transcript* transcript, const uint64_t* g0_u_w);
 
