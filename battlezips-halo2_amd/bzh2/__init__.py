@@ -955,6 +955,62 @@ class TranscriptBatch:
                                                       _vp(z) if want_z else None, _vp(zp), _vp(zb), _vp(st)), where)
         return z, zp, zb, st
 
+    COMMITMENTS_OUT = ("advice", "instance", "lookup_compressed", "lookup_permuted", "advice_polys", "instance_polys", "lookup_polys",
+                       "advice_blinds", "lookup_blinds", "theta", "beta", "gamma")
+
+    def commitments(self, pk, advice, instances, rng_list, *, form: int = FORM_CANONICAL, mem: int = MEM_HOST, out=None, status=None,
+                    instance_rows: int | None = None, rng_stride: int | None = None, batch: int | None = None, shape=None):
+        """the witness commitments of `batch` proofs against this device-resident batch (bzh_commitments_batch_device): the instance
+        commitments are absorbed, the advice commitments written, theta squeezed, the lookups compressed with theta where it lies,
+        permuted and committed, beta and gamma squeezed, with no host trip in between.  The key's vk_repr is not absorbed here:
+        common_scalars it first.  The outputs chain into grand_products() and vanishing().
+        MEM_HOST: advice (batch, num_advice, n, 4) and instances (batch, num_instance, instance_rows, 4) uint64 in `form` (None
+        where the count is 0); rng_list: one byte string of 64 * nd draws per proof.  Returns (outputs, status): a dict of uint64
+        arrays in `form` by the names of COMMITMENTS_OUT -- advice (batch, na, n, 4), instance (batch, ni, n, 4),
+        lookup_compressed, lookup_permuted and lookup_polys (batch, nl, 2, n, 4), advice_polys, instance_polys, advice_blinds
+        (batch, na, 4), lookup_blinds (batch, nl, 2, 4), theta, beta, gamma (batch, 4) -- and (batch,) uint8 -- bit 0: a lookup
+        input of that proof is not in its table.  `shape`: commitments_plan(), which sizes the outputs; None:
+        pk.commitments_plan(), computed for this call.
+        MEM_DEVICE: advice, instances and rng_list are device pointers (ints, 16-byte aligned; proof b's draws at + b *
+        rng_stride), `out` a dict of device pointers by the names of COMMITMENTS_OUT (a missing name is NULL), `status` a device
+        pointer of any alignment or None, instance_rows the rows per instance column.  Enqueues only, returns None."""
+        L = load()
+        vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+        L.bzh_commitments_batch_device.argtypes = [vp, vp, sz, vp, vp, sz, ci, ci, vp, sz, vp, vp, vp]
+        ctxh = self.ctx.handle if self.ctx is not None else None
+        pkh = pk.handle if hasattr(pk, "handle") else pk
+        where = "bzh_commitments_batch_device"
+        if mem == MEM_DEVICE:
+            ptr = lambda v: ctypes.c_void_p(int(v)) if v else None  # noqa: E731
+            o = (ctypes.c_void_p * 12)(*[ptr((out or {}).get(name)) for name in self.COMMITMENTS_OUT])
+            self._check(L.bzh_commitments_batch_device(ctxh, pkh, self.batch if batch is None else batch, ptr(advice), ptr(instances),
+                                                       instance_rows or 0, form, mem, ptr(rng_list), rng_stride or 0, self.h,
+                                                       ctypes.cast(o, vp) if out is not None else None, ptr(status)), where)
+            return None
+        B = len(rng_list)
+        if shape is None:
+            if not hasattr(pk, "commitments_plan"):
+                raise TypeError("TranscriptBatch.commitments: `shape` is required when pk is a bare handle")
+            shape = pk.commitments_plan()
+        n, _, _, na, ni, nl = shape[:6]
+        arr = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.uint64))  # noqa: E731
+        opt = lambda a: _vp(a) if a is not None and a.size else None  # noqa: E731
+        adv, inst = arr(advice), arr(instances)
+        if instance_rows is None:
+            instance_rows = inst.reshape(B, ni, -1, 4).shape[2] if inst is not None and inst.size else 0
+        stride = len(rng_list[0])
+        assert all(len(r) == stride for r in rng_list)
+        raw = np.frombuffer(b"".join(rng_list), dtype=np.uint8)
+        dims = {"advice": (na, n), "instance": (ni, n), "lookup_compressed": (nl, 2, n), "lookup_permuted": (nl, 2, n), "advice_polys": (na, n),
+                "instance_polys": (ni, n), "lookup_polys": (nl, 2, n), "advice_blinds": (na,), "lookup_blinds": (nl, 2), "theta": (), "beta": (),
+                "gamma": ()}
+        res = {name: np.zeros((B,) + dims[name] + (4,), dtype=np.uint64) for name in self.COMMITMENTS_OUT}
+        o = (ctypes.c_void_p * 12)(*[opt(res[name]) for name in self.COMMITMENTS_OUT])
+        st = np.zeros(B, dtype=np.uint8)
+        self._check(L.bzh_commitments_batch_device(ctxh, pkh, B, opt(adv), opt(inst), instance_rows, form, mem, _vp(raw), stride, self.h,
+                                                   ctypes.cast(o, vp), _vp(st)), where)
+        return res, st
+
     def close(self):
         if self.h is not None:
             load().bzh_transcript_batch_free(self.h)
@@ -1074,6 +1130,23 @@ def grand_products_plan(curve: int, circuit_blob: bytes):
     rc = L.bzh_grand_products_plan(curve, blob, len(blob), _vp(shape))
     if rc != OK:
         raise BzhError(rc, "bzh_grand_products_plan")
+    return tuple(int(x) for x in shape)
+
+
+EXPORTS += ["bzh_commitments_plan", "bzh_commitments_batch_device"]
+
+
+def commitments_plan(curve: int, circuit_blob: bytes):
+    """what the witness commitments derive from a circuit (bzh_commitments_plan, host only): (n, usable rows, blinding factors bf,
+    num_advice na, num_instance ni, lookups nl, draws per proof = na * (bf + 1) + na + nl * (2 * (bf + 1) + 2), proof bytes
+    appended = 32 * (na + 2 * nl))"""
+    L = load()
+    L.bzh_commitments_plan.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
+    blob = bytes(circuit_blob)
+    shape = np.zeros(8, dtype=np.uint32)
+    rc = L.bzh_commitments_plan(curve, blob, len(blob), _vp(shape))
+    if rc != OK:
+        raise BzhError(rc, "bzh_commitments_plan")
     return tuple(int(x) for x in shape)
 
 

@@ -170,6 +170,11 @@ class NativeProvingKey:
         from . import grand_products_plan
         return grand_products_plan(self.curve, self.blob)
 
+    def commitments_plan(self):
+        """the shape of bzh2.commitments_plan for this key's circuit: what TranscriptBatch.commitments takes as `shape`"""
+        from . import commitments_plan
+        return commitments_plan(self.curve, self.blob)
+
     def quotient_stats(self) -> dict:
         L = _bind()
         L.bzh_pk_quotient_stats.argtypes = [_VP] + [ctypes.POINTER(ctypes.c_uint32)] * 4

@@ -421,6 +421,25 @@ int products_factors(bzh_ctx* ctx, int field, const void* d_cols, const void* d_
                      const uint32_t* d_beta, const uint32_t* d_gamma, int form, uint32_t* d_num, uint32_t* d_den);
 int products_finish(bzh_ctx* ctx, int field, const uint32_t* d_raw, const uint32_t* d_drawn, size_t n, size_t usable, size_t bf, size_t nsets,
                     size_t nl, size_t batch, uint32_t* d_z, uint32_t* d_blinds, uint8_t* d_status, uint8_t* d_sticky);
+// commitments.hip: the four kernels of bzh_commitments_batch_device (the call itself reads the key: csrc/commitments_device.hpp);
+// device pointers, 16-byte aligned unless said otherwise, Montgomery unless said otherwise; enqueue only.
+// commitments_place: d_out_adv[b][na][n] = the caller's d_advice[b][na][n] (in `form`) below `usable`, from there on the drawn
+// blinding rows d_drawn[b][c * (n - usable) ..] (d_drawn: batch rows of nd elements); d_out_blinds[b][na] = the na draws after
+// them; d_out_inst[b][ni][n] = d_instances[b][ni][inst_rows] (in `form`; not read when inst_rows is 0) and zeros.
+// commitments_consts: every entry of the CmConst list at d_descs (commitments_scalars.hpp) into its program's table, theta
+// (batch elements) in `form`.  commitments_lookup_finish: per pair b * nl + l the 2 (n - usable) drawn rows from
+// d_drawn[b][first + l * (2 (n - usable) + 2) ..] into rows usable .. n - 1 of d_permuted[pair][2][n], the two draws after them
+// into d_blinds[pair][2]; d_status[b] (any alignment, may be null) = bit 0: one of d_words[b * nl ..][nl] is non-zero, ORed into
+// d_sticky[b].  commitments_scalar_rows: d_scalars[v] = (d_evals[v][n] | 0 | d_blinds[v] [| 0]), cols = n + 2 or n + 3.
+int commitments_place(bzh_ctx* ctx, int field, const uint32_t* d_advice, const uint32_t* d_instances, size_t inst_rows,
+                      const uint32_t* d_drawn, size_t nd, size_t n, size_t usable, size_t na, size_t ni, size_t batch, int form,
+                      uint32_t* d_out_adv, uint32_t* d_out_inst, uint32_t* d_out_blinds);
+int commitments_consts(bzh_ctx* ctx, int field, const void* d_descs, size_t ndescs, size_t batch, const uint32_t* d_theta, int form);
+int commitments_lookup_finish(bzh_ctx* ctx, int field, const uint32_t* d_drawn, size_t nd, size_t first, size_t n, size_t usable, size_t nl,
+                              size_t batch, const int32_t* d_words, uint32_t* d_permuted, uint32_t* d_blinds, uint8_t* d_status,
+                              uint8_t* d_sticky);
+int commitments_scalar_rows(bzh_ctx* ctx, int field, const uint32_t* d_evals, const uint32_t* d_blinds, size_t n, size_t cols, size_t count,
+                            uint32_t* d_scalars);
 int ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                const uint8_t* proof, size_t proof_len, bzh_transcript* tr, const uint64_t* g0_u_w_xy);
 int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
@@ -446,8 +465,8 @@ int h2c_generators_run(bzh_ctx* ctx, uint32_t first, size_t count, uint32_t* d_o
 // kind 0 / 1: common / write points (d_pre: a BZH_POINT_* byte per point at [b * stride + i], or null), kind 2 / 3: common / write
 // scalars; item i of transcript b lies at d_base + (b * stride + i) items -- stride 0 gives every transcript the same items.  A
 // write appends to the proofs without a capacity check: the caller has made it (tb_info).  tb_write_jacobian_locked is
-// bzh_transcript_batch_write_jacobian for device operands.  tb_squeeze_locked writes batch x 32 bytes.  tb_free_locked waits for
-// the stream.
+// bzh_transcript_batch_write_jacobian for device operands; with kind 0 the normalised points are absorbed as COMMON points and
+// nothing goes into the proofs.  tb_squeeze_locked writes batch x 32 bytes.  tb_free_locked waits for the stream.
 struct TbInfo {
     bzh_ctx* ctx;   // null: host-resident
     int curve;
@@ -456,7 +475,7 @@ struct TbInfo {
 int tb_new_locked(bzh_ctx* ctx, int curve, size_t batch, bzh_transcript_batch** out);
 void tb_free_locked(bzh_transcript_batch* tb);
 int tb_absorb_locked(bzh_transcript_batch* tb, int kind, const void* d_base, size_t count, size_t stride, int form, const uint8_t* d_pre);
-int tb_write_jacobian_locked(bzh_transcript_batch* tb, const void* d_xyz, size_t count, size_t stride, int form);
+int tb_write_jacobian_locked(bzh_transcript_batch* tb, const void* d_xyz, size_t count, size_t stride, int form, int kind = 1);
 int tb_squeeze_locked(bzh_transcript_batch* tb, int form, uint32_t* d_out);
 const uint8_t* tb_status_device(const bzh_transcript_batch* tb);
 uint8_t* tb_status_device_mut(bzh_transcript_batch* tb);   // for a kernel of the caller's that marks a transcript (vanishing.hip)

@@ -44,6 +44,7 @@
 #include "host_field.hpp"
 #include "vanishing_scalars.hpp"   // (bzh_vanishing_const as the lane body reads it)
 #include "products_scalars.hpp"    // (the column table as k_gp_factors reads it)
+#include "commitments_scalars.hpp" // (the constant descriptors as k_cm_consts reads them)
 #include "vm2_isa.hpp"
 
 // the table of quotient kernels generated at build time (quotient_builtin.hip); absent (null) in the generator's own link
@@ -60,6 +61,7 @@ extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __at
 #include "prover.hpp"
 #include "vanishing_device.hpp"   // phase 5 of the prover as a leaf on device-resident transcripts
 #include "products_device.hpp"    // phase 4 likewise
+#include "commitments_device.hpp" // phases 1 to 3 likewise
 #include "verifier.hpp"
 
 // pk.get_vk(): the commitments to the fixed and permutation polynomials (blind 1), computed once per key
@@ -686,6 +688,60 @@ int bzh_grand_products_batch_device(bzh_ctx* ctx, bzh_pk* pk, size_t batch, cons
     const int rc = bzh::with_pasta_curve(pk->curve, [&](auto c) {
         return bzh::products_device_t<decltype(c)>(ctx, pk, batch, advice, instance, lookup_compressed, lookup_permuted, beta, gamma, form, mem, rng,
                                                    rng_stride, transcripts, out_z, out_z_polys, out_z_blinds, status);
+    });
+    if (rc && !ctx->pending_d2h.empty()) {   // a host call that failed between its read-backs and their end: they must not land later
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->pending_d2h.clear();
+    }
+    return rc;
+}
+
+int bzh_commitments_plan(int curve, const uint8_t* circuit, size_t circuit_len, uint32_t shape8[8]) {
+    if (!circuit || !shape8) return BZH_E_ARG;
+    bzh_pk pk;
+    BZH_TRY(bzh::with_pasta_curve(curve, [&](auto c) {
+        bzh::ParsedKey<typename bzh::CurveInfo<decltype(c)>::SF> po;
+        return bzh::pk_parse_t<decltype(c)>(circuit, circuit_len, pk, po);
+    }));
+    const uint32_t shape[8] = {(uint32_t)pk.n,  (uint32_t)pk.usable, (uint32_t)pk.bf, (uint32_t)pk.na, (uint32_t)pk.ni,
+                               (uint32_t)pk.nl, (uint32_t)bzh::commitments_draws(pk), 32u * (uint32_t)(pk.na + 2 * pk.nl)};
+    memcpy(shape8, shape, sizeof(shape));
+    return BZH_OK;
+}
+
+int bzh_commitments_batch_device(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice, const uint64_t* instances,
+                                 size_t instance_rows, int form, int mem, const uint8_t* rng, size_t rng_stride,
+                                 bzh_transcript_batch* transcripts, const bzh_commitments_out* out, uint8_t* status) {
+    // what reads neither the key nor the device
+    if (!ctx || !pk || !transcripts || !rng || !out || !out->theta || !out->beta || !out->gamma) return BZH_E_ARG;
+    if (!batch || batch > 65535 || (form != BZH_FORM_CANONICAL && form != BZH_FORM_MONTGOMERY) || (mem != BZH_MEM_HOST && mem != BZH_MEM_DEVICE))
+        return BZH_E_ARG;
+    const bzh::TbInfo ti = bzh::tb_info(transcripts);
+    if (!ti.ctx) return BZH_E_ARG;   // a host-resident batch
+    bzh::KeyRuntime::Call in_flight(pk->rt);   // registered before the wait for ctx->mu, like every other call on a key
+    // what reads the key
+    const size_t na = (size_t)pk->na, ni = (size_t)pk->ni, nl = (size_t)pk->nl;
+    if (pk->device != ctx->device || ti.ctx != ctx || ti.curve != pk->curve || ti.batch != batch) return BZH_E_ARG;
+    // (instance_rows == 0: the instance columns are zero and `instances` is not read, NULL or not -- as in bzh_prove_batch)
+    if ((na && !advice) || (ni && instance_rows && !instances) || instance_rows > pk->usable) return BZH_E_ARG;
+    if ((na && (!out->advice || !out->advice_polys || !out->advice_blinds)) || (ni && (!out->instance || !out->instance_polys)) ||
+        (nl && (!out->lookup_compressed || !out->lookup_permuted || !out->lookup_polys || !out->lookup_blinds)))
+        return BZH_E_ARG;
+    // (one row of a launch's grid per commitment, and the commitments of a kind are one launch; batch * 2 nl <= 65535 also keeps
+    // the batch * nl pairs within the 32767 that one lookup_permute call takes)
+    if (rng_stride < 64 * bzh::commitments_draws(*pk) || batch * std::max({na, ni, 2 * nl}) > 65535) return BZH_E_ARG;
+    const uintptr_t all = (uintptr_t)advice | (uintptr_t)(instance_rows ? instances : nullptr) | (uintptr_t)rng | (uintptr_t)out->advice |
+                          (uintptr_t)out->instance | (uintptr_t)out->lookup_compressed | (uintptr_t)out->lookup_permuted |
+                          (uintptr_t)out->advice_polys | (uintptr_t)out->instance_polys | (uintptr_t)out->lookup_polys |
+                          (uintptr_t)out->advice_blinds | (uintptr_t)out->lookup_blinds | (uintptr_t)out->theta | (uintptr_t)out->beta |
+                          (uintptr_t)out->gamma;
+    if (mem == BZH_MEM_DEVICE && (all & 15)) return BZH_E_ARG;
+    if (ti.proof_len + 32 * (na + 2 * nl) > ti.proof_cap) return BZH_E_RANGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = bzh::with_pasta_curve(pk->curve, [&](auto c) {
+        return bzh::commitments_device_t<decltype(c)>(ctx, pk, batch, advice, instances, instance_rows, form, mem, rng, rng_stride, transcripts,
+                                                      *out, status);
     });
     if (rc && !ctx->pending_d2h.empty()) {   // a host call that failed between its read-backs and their end: they must not land later
         (void)hipStreamSynchronize(ctx->stream);

@@ -235,8 +235,22 @@ struct Prover : DeviceColumns<C> {
         return BZH_OK;
     }
     static void put_saturated(uint32_t* dst, const Fe<SF>& v) { memcpy(dst, v.l, 32); }
+    // run is two halves, like run_quotient.  The first finds or compiles the key's cached program and builds its arguments in
+    // device memory: the constant table from env (host transcripts), or only its room (consts_on_device:
+    // commitments_device.hpp fills it on the device from theta in HBM).  The second, run_launch, is the interpreter's launch.
+    struct RunProgram {
+        const Program* pg = nullptr;
+        ProgramArgs pa;
+        bool per_proof = false;   // a constant is a symbol: the table has one row per proof
+    };
     template <class Build>
     int run(uint64_t pkey, Build build, const Cols& reg, size_t size, uint32_t* d_out) {
+        RunProgram rp;
+        BZH_TRY(run_args(pkey, build, reg, false, rp));
+        return run_launch(rp, size, d_out);
+    }
+    template <class Build>
+    int run_args(uint64_t pkey, Build build, const Cols& reg, bool consts_on_device, RunProgram& rp) {
         const Program* pgp = nullptr;
         {
             std::lock_guard<std::mutex> lk(pk.rt.mu);   // map nodes are stable: the program outlives the lock
@@ -253,18 +267,20 @@ struct Prover : DeviceColumns<C> {
         }
         const Program& pg = *pgp;
         const size_t nc = pg.consts.size(), ncols = reg.ptr.size();
-        bool per_proof = false;
-        for (auto& c : pg.consts) per_proof |= c.sym >= 0;
+        rp.pg = pgp, rp.per_proof = false;
+        for (auto& c : pg.consts) rp.per_proof |= c.sym >= 0;
+        const size_t rows = rp.per_proof ? B : 1;
         std::vector<uint32_t> cv;
-        BZH_TRY(fill_consts(pg.consts, per_proof ? B : 1, 8, put_saturated, cv));
-        ProgramArgs pa;
-        BZH_TRY(upload_program(cv.data(), cv.size() * 4, pg.ops.data(), pg.ops.size() * sizeof(bzh_expr_op), reg.ptr.data(), reg.stride.data(), ncols, pa));
-        uint32_t* d_consts = pa.consts;
-        char *d_prog = pa.prog, *d_ptrs = pa.ptrs, *d_strides = pa.strides;
+        if (!consts_on_device) BZH_TRY(fill_consts(pg.consts, rows, 8, put_saturated, cv));
+        return upload_program(consts_on_device ? nullptr : cv.data(), std::max<size_t>(rows * nc, 1) * 32, pg.ops.data(),
+                              pg.ops.size() * sizeof(bzh_expr_op), reg.ptr.data(), reg.stride.data(), ncols, rp.pa);
+    }
+    int run_launch(const RunProgram& rp, size_t size, uint32_t* d_out) {
+        const Program& pg = *rp.pg;
         int nslots = pg.result_slot + 1;
         for (auto& o : pg.ops) nslots = std::max(nslots, (int)o.dst + 1);  // operands only read slots written before
-        return expr_eval(ctx, field, d_prog, (int)pg.ops.size(), (const uint32_t* const*)d_ptrs, (const size_t*)d_strides, d_consts,
-                         per_proof ? nc : 0, size, pg.result_slot, B, nslots, d_out);
+        return expr_eval(ctx, field, rp.pa.prog, (int)pg.ops.size(), (const uint32_t* const*)rp.pa.ptrs, (const size_t*)rp.pa.strides,
+                         rp.pa.consts, rp.per_proof ? pg.consts.size() : 0, size, pg.result_slot, B, nslots, d_out);
     }
 
     // The quotient through VM v2 (the program compiled at bzh_pk_create), in one of four flavours: the builtin kernel in unsaturated
@@ -511,6 +527,14 @@ struct Prover : DeviceColumns<C> {
         return BZH_OK;
     }
 
+    // the compress expression of lookup li's input (side 0) or table (side 1) over lag_registry's columns: Horner in theta over
+    // its expressions -- the key's cached programs key(20 + side, li)
+    int compress_root(int li, int side, EPool& ep, Cols& reg) {
+        std::vector<int> terms;
+        for (int e : side ? pk.lookups[li].second : pk.lookups[li].first) terms.push_back(lower(pk, e, ep, reg, 1));
+        return ep.horner(terms, ep.sym(SY_THETA));
+    }
+
     // 3. lookups: compress, permute (device kernels or host sort: bzh_pk_lookup_select), blind and commit; then beta, gamma.
     // reads adv, inst, env[SY_THETA]; fills lk (all but the cosets), inst_cosets, adv_cosets, env[SY_BETA], env[SY_GAMMA]
     int lookups() {
@@ -530,14 +554,8 @@ struct Prover : DeviceColumns<C> {
             if (!d.a_c || !d.s_c || !d.as || !d.polys) return BZH_E_OOM;
             Cols reg;
             lag_registry(reg);
-            for (int side = 0; side < 2; side++) {
-                const std::vector<int>& es = side ? pk.lookups[li].second : pk.lookups[li].first;
-                BZH_TRY(run(key(20 + side, li), [&](EPool& ep) {
-                    std::vector<int> terms;
-                    for (int e : es) terms.push_back(lower(pk, e, ep, reg, 1));
-                    return ep.horner(terms, ep.sym(SY_THETA));
-                }, reg, n, side ? d.s_c : d.a_c));
-            }
+            for (int side = 0; side < 2; side++)
+                BZH_TRY(run(key(20 + side, li), [&](EPool& ep) { return compress_root(li, side, ep, reg); }, reg, n, side ? d.s_c : d.a_c));
             BZH_TRY(lk_device ? permute_on_device(d) : permute_on_host(d));
             BZH_TRY(blind_rows(d.as, usable, bf1, 2, n));
             d.blinds.resize(B * 2);

@@ -246,16 +246,18 @@ int tb_absorb_locked(bzh_transcript_batch* tb, int kind, const void* d_base, siz
     return BZH_OK;
 }
 // bzh_transcript_batch_write_jacobian's device half: bzh_batch_normalize's launch over the whole span the points lie in, into the
-// batch's own scratch (which grows on first use), then the write kernel
-int tb_write_jacobian_locked(bzh_transcript_batch* tb, const void* d_xyz, size_t count, size_t stride, int form) {
+// batch's own scratch (which grows on first use), then the write kernel (kind 1) or the common kernel (kind 0)
+int tb_write_jacobian_locked(bzh_transcript_batch* tb, const void* d_xyz, size_t count, size_t stride, int form, int kind) {
     if (!count) return BZH_OK;
+    if (kind != 0 && kind != 1) return BZH_E_ARG;
     bzh_ctx* ctx = tb->ctx;
     const size_t n = (tb->batch - 1) * stride + count;
     BZH_TRY(scratch_ensure(tb, n * 64 + n + 256));
     uint8_t* d_st = (uint8_t*)tb->d_scratch + n * 64;
     BZH_TRY(normalize_run(ctx, tb->curve, d_xyz, n, form, tb->d_scratch, nullptr, d_st));
-    BZH_TRY(absorb_launch<1>(tb, tb->d_scratch, count, stride, form, d_st));
-    advance(tb, count, 65, true);
+    if (kind) BZH_TRY(absorb_launch<1>(tb, tb->d_scratch, count, stride, form, d_st));
+    else BZH_TRY(absorb_launch<0>(tb, tb->d_scratch, count, stride, form, d_st));
+    advance(tb, count, 65, kind != 0);
     return BZH_OK;
 }
 TbInfo tb_info(const bzh_transcript_batch* tb) { return TbInfo{tb->ctx, tb->curve, tb->batch, tb->proof_cap, tb->proof_len}; }

@@ -70,16 +70,30 @@ static int leaf_draws(Prover<C>& pv, bool host, const uint8_t* rng, size_t rng_s
     }
     return random_field(ctx, pv.field, (const uint32_t*)raw, B * nd, drawn);
 }
-// `count` polynomials of n coefficients under their blinds in device memory, into the transcripts: `per_proof` points each
+// `count` polynomials of n coefficients under their blinds in device memory, into the transcripts: `per_proof` points each,
+// written (kind 1) or absorbed as common points (kind 0).  evals: the same columns over the domain; when the caller has them and
+// the key offers g_lagrange (bzh_pk_set_lagrange) they are committed in that basis, where witness columns are sparse
+// (DeviceColumns::commit) -- the same group elements, the same bytes
 template <class C>
 static int leaf_commit_write(Prover<C>& pv, bzh_transcript_batch* tb, const uint32_t* polys, const uint32_t* blinds, size_t count,
-                             size_t per_proof) {
+                             size_t per_proof, const uint32_t* evals = nullptr, int kind = 1) {
     ArenaScope scope(pv.arena);   // (dead once enqueued: everything that reuses the memory is queued behind it on the one stream)
-    uint32_t* scalars = pv.dalloc(count * (pv.n + 2));
+    const bzh_bases* lagrange = nullptr;
+    if (evals) {
+        std::lock_guard<std::mutex> lk(pv.pk.rt.mu);
+        lagrange = pv.pk.srs_lagrange;
+    }
+    const size_t cols = lagrange ? lagrange->n : pv.n + 2;
+    uint32_t* scalars = pv.dalloc(count * cols);
     uint32_t* xyz = pv.dalloc(count * 3);
     if (!scalars || !xyz) return BZH_E_OOM;
-    BZH_TRY(ipa_commit_blinded(pv.ctx, pv.pk.srs, polys, count, blinds, scalars, xyz));
-    return tb_write_jacobian_locked(tb, xyz, per_proof, per_proof, BZH_FORM_MONTGOMERY);
+    if (lagrange) {
+        BZH_TRY(commitments_scalar_rows(pv.ctx, pv.field, evals, blinds, pv.n, cols, count, scalars));
+        BZH_TRY(msm_run(pv.ctx, lagrange, scalars, cols, count, BZH_FORM_MONTGOMERY, xyz));
+    } else {
+        BZH_TRY(ipa_commit_blinded(pv.ctx, pv.pk.srs, polys, count, blinds, scalars, xyz));
+    }
+    return tb_write_jacobian_locked(tb, xyz, per_proof, per_proof, BZH_FORM_MONTGOMERY, kind);
 }
 
 // the call, for a caller that holds ctx->mu and has made every argument check

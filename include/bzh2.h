@@ -525,6 +525,71 @@ int bzh_grand_products_batch_device(bzh_ctx* ctx, struct bzh_pk* pk, size_t batc
                                     const uint64_t* gamma, int form, int mem, const uint8_t* rng, size_t rng_stride,
                                     struct bzh_transcript_batch* transcripts, uint64_t* out_z, uint64_t* out_z_polys, uint64_t* out_z_blinds,
                                     uint8_t* status);
+/* The witness commitments of plonk::create_proof against a device-resident bzh_transcript_batch -- csrc/commitments_device.hpp,
+ * csrc/commitments.hip, csrc/commitments_scalars.hpp: the instance and advice commitments, theta, the lookups' compressed and
+ * permuted columns with their commitments, beta and gamma; the commit_instances(), commit_advice() and lookups() phases of
+ * bzh_prove_batch as a leaf.  It is the head of the chain: its outputs are the operands of bzh_grand_products_batch_device and
+ * bzh_vanishing_batch_device, and theta, beta, gamma land where those calls read them, so a witness goes in here and whole
+ * proofs come out of the transcript batch after the opening with no challenge, scalar or point crossing to the host.
+ *
+ * bzh_commitments_plan is pure host code (no ctx, no device).  shape8: n, the usable rows, the blinding factors bf, num_advice na,
+ * num_instance ni, the lookups nl, the draws per proof nd = na * (bf + 1) + na + nl * (2 * (bf + 1) + 2), and the proof bytes
+ * appended, 32 * (na + 2 * nl).  BZH_E_ARG, nothing written: a NULL pointer, an unknown curve, a blob that does not parse.
+ *
+ * bzh_commitments_batch_device takes advice[b][na][n], the caller's witness over the domain, n = 2^k rows each -- its rows from
+ * `usable` on are ignored and overwritten in the output, as in bzh_prove_batch -- and instances[b][ni][instance_rows], which is
+ * padded with zeros to n; with instance_rows == 0 the instance columns are zero and `instances` is not read, NULL or not, as in
+ * bzh_prove_batch.  `form` and `mem` apply to every data pointer, as in the four calls above: with BZH_MEM_DEVICE they are
+ * 16-byte-aligned device pointers (`status` any alignment; `out` itself is a host struct) and the call only enqueues; with
+ * BZH_MEM_HOST the operands are staged up once at the start and the outputs read back once at the end.  rng: proof b's 64-byte
+ * draws at rng + b * rng_stride, in upstream's order -- the advice blinding rows usable .. n - 1, column by column; the na advice
+ * blinds; then per lookup the bf + 1 rows of the permuted input, the bf + 1 rows of the permuted table, the input's blind, the
+ * table's blind --, so rng_stride >= 64 * nd.
+ * Messages, per proof, in upstream's order: COMMON each instance commitment (blind one); WRITE each advice commitment; squeeze
+ * theta; per lookup WRITE the commitment of the permuted input and then of the permuted table; squeeze beta; squeeze gamma.  The
+ * proof grows by 32 * (na + 2 * nl) bytes.  The key's vk_repr is NOT absorbed here: the caller does that first, with
+ * bzh_transcript_batch_common_scalars, as for every batch.
+ * Outputs, in `form`, through the struct bzh_commitments_out; a member whose count is 0 may be NULL.  Over the domain, blinding rows in
+ * place: advice[b][na][n], instance[b][ni][n], lookup_compressed[b][nl][2][n] (a_c, then s_c), lookup_permuted[b][nl][2][n] --
+ * the four operands of bzh_grand_products_batch_device.  Coefficients: advice_polys, instance_polys, lookup_polys[b][nl][2][n] --
+ * operands of bzh_vanishing_batch_device.  Blinds: advice_blinds[b][na], lookup_blinds[b][nl][2].  Challenges: theta[b], beta[b],
+ * gamma[b], as bzh_transcript_batch_squeeze writes them.  status (may be NULL), one byte per proof: bit 0 is set when a lookup of
+ * that proof has an input that is not in its table (the device permutation's non-zero status word).  Such a proof still gets all
+ * its messages -- a failed pair keeps every index in bounds and writes a reduced element in every row --, disturbs no other
+ * proof, and the call returns BZH_OK; the bit is also ORed into the batch's sticky status byte.
+ * One launch (k_cm_place) writes the advice and instance columns from the caller's arrays and the drawn rows, converting from
+ * the caller's form in the same pass.  The lookups' compressed columns come from the key's cached expression programs, whose
+ * constant tables one launch (k_cm_consts) builds on the device from theta where it was squeezed; one device permutation call
+ * takes all batch * nl pairs; one launch (k_cm_lookup_finish) places their drawn rows and blinds and folds the status.  The
+ * commitments take their blinds from device memory and are made in the basis the key offers: the evaluations against g_lagrange
+ * when the key has that table (bzh_pk_set_lagrange), the coefficients against the SRS otherwise -- the same bytes.  Between its
+ * first launch and its last the call copies nothing that depends on a challenge or on the permutation's status to the host, does
+ * no host field or curve arithmetic on such a value and adds no stream synchronisation of its own; everything that depends on
+ * the key and the operand pointers alone -- expression programs, column registries, descriptor tables -- is uploaded before the
+ * first launch.  The scratch is the key's workspace for this ctx, under the rule bzh_vanishing_batch_device states: a
+ * BZH_MEM_DEVICE call returns with its work queued on it, and the call that merges the workspace's blocks waits once for the
+ * stream before its own first launch.  Its speed against the host path: DESIGN.md section 7.
+ * BZH_E_ARG, the batch left as it was and nothing written: a NULL ctx, pk, transcripts, rng, out, required operand or required
+ * output member; a host-resident batch; a batch of another ctx, curve or size; a key on another device than ctx; batch == 0 or
+ * > 65535, or batch * max(na, ni, 2 * nl) > 65535 (the commitments of a kind are one launch with one row of its grid per
+ * commitment); instance_rows > usable; unknown form or mem; a misaligned device pointer; rng_stride too small.  BZH_E_RANGE,
+ * nothing absorbed and nothing squeezed: proof_cap cannot take 32 * (na + 2 * nl) more bytes; a lookup whose expressions do not
+ * fit the expression interpreter.  That last refusal is decided when the call finds or compiles the key's cached programs, which
+ * is after ctx is taken and the workspace reset, with at most the uploads of the programs before it queued on the stream; every other check comes before the
+ * first use of ctx: first those that read neither the key nor the device, then those that read the key.  (The device
+ * permutation takes at most 32767 pairs a call; batch * 2 * nl <= 65535 keeps batch * nl within that, so the shape it would
+ * refuse is already BZH_E_ARG.)  The uploads that depend on the key and the operand pointers alone are the call's first work on
+ * the stream -- the small upload kernels that carry them included --; a BZH_MEM_HOST call's operands are staged up after them. */
+typedef struct {
+    uint64_t *advice, *instance, *lookup_compressed, *lookup_permuted; /* over the domain */
+    uint64_t *advice_polys, *instance_polys, *lookup_polys;            /* coefficients */
+    uint64_t *advice_blinds, *lookup_blinds;
+    uint64_t *theta, *beta, *gamma;
+} bzh_commitments_out;
+int bzh_commitments_plan(int curve, const uint8_t* circuit, size_t circuit_len, uint32_t shape8[8]);
+int bzh_commitments_batch_device(bzh_ctx* ctx, struct bzh_pk* pk, size_t batch, const uint64_t* advice, const uint64_t* instances,
+                                 size_t instance_rows, int form, int mem, const uint8_t* rng, size_t rng_stride,
+                                 struct bzh_transcript_batch* transcripts, const bzh_commitments_out* out, uint8_t* status);
 int bzh_ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitment_xy, const uint64_t* x3, const uint64_t* v,
                    const uint8_t* proof, size_t proof_len, bzh_transcript* transcript, const uint64_t* g0_u_w);
 
