@@ -1150,6 +1150,22 @@ def commitments_plan(curve: int, circuit_blob: bytes):
     return tuple(int(x) for x in shape)
 
 
+EXPORTS += ["bzh_prove_device_plan", "bzh_prove_batch_device", "bzh_prove_batch_device_seeded"]
+
+
+def prove_device_plan(curve: int, circuit_blob: bytes):
+    """(commitments draws, grand-products draws, vanishing draws, multiopen draws, their sum = rng_bytes / 64, proof bytes, nown, largest
+    batch) of bzh_prove_batch_device for a circuit blob (host only): the draws per proof of the four drawing leaves in chain order,
+    the polynomials of a proof that get opened, and 65535 // max(na, ni, 2 nl, nz, npieces)"""
+    L = load()
+    L.bzh_prove_device_plan.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
+    shape = np.zeros(8, dtype=np.uint32)
+    rc = L.bzh_prove_device_plan(curve, circuit_blob, len(circuit_blob), ctypes.c_void_p(shape.ctypes.data))
+    if rc:
+        raise BzhError(rc, "bzh_prove_device_plan")
+    return tuple(int(v) for v in shape)
+
+
 EXPORTS += ["bzh_pk_create", "bzh_pk_free", "bzh_pk_set_lagrange", "bzh_pk_quotient_stats", "bzh_pk_quotient_source", "bzh_pk_set_quotient_module", "bzh_pk_info", "bzh_prove_batch", "bzh_prove_batch_seeded", "bzh_rng_expand", "bzh_verify_batch",
             "bzh_vk_digest", "bzh_pk_vk_repr"]
 EXPORTS += ["bzh_vk_create", "bzh_vk_from_pk", "bzh_vk_write", "bzh_vk_read", "bzh_vk_info", "bzh_vk_vk_repr", "bzh_vk_device_bytes",

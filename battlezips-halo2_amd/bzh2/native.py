@@ -30,6 +30,10 @@ def _bind():
     L.bzh_prove_batch_seeded.argtypes = [_VP, _VP, ctypes.c_size_t, _VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t, ctypes.c_char_p,
                                          _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.bzh_rng_expand.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_size_t, _VP]
+    L.bzh_prove_batch_device.argtypes = [_VP, _VP, ctypes.c_size_t, _VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t, _VP,
+                                         ctypes.c_size_t, _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), _VP]
+    L.bzh_prove_batch_device_seeded.argtypes = [_VP, _VP, ctypes.c_size_t, _VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t,
+                                                ctypes.c_char_p, _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), _VP]
     L.bzh_pk_vk_repr.argtypes = [_VP, _VP, ctypes.POINTER(ctypes.c_int)]
     szp, u32p = ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32)
     L.bzh_vk_create.argtypes = [_VP, _VP, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_VP)]
@@ -174,6 +178,11 @@ class NativeProvingKey:
         """the shape of bzh2.commitments_plan for this key's circuit: what TranscriptBatch.commitments takes as `shape`"""
         from . import commitments_plan
         return commitments_plan(self.curve, self.blob)
+
+    def prove_device_plan(self):
+        """the shape of bzh2.prove_device_plan for this key's circuit: the leaves' draws, their sum, the proof bytes, nown, the largest batch"""
+        from . import prove_device_plan
+        return prove_device_plan(self.curve, self.blob)
 
     def quotient_stats(self) -> dict:
         L = _bind()
@@ -363,6 +372,50 @@ class NativeProvingKey:
                                    _VP(proofs.ctypes.data), self.max_proof_bytes, lens)
         ctx._check(rc, "bzh_prove_batch")
         return [bytes(proofs[b, :lens[b]]) for b in range(B)]
+
+    def prove_batch_device(self, advice, instances, rng_list=None, *, seeds=None, device_ptr: int | None = None,
+                           rng_device_ptr: int | None = None, ctx: Context | None = None, want_status: bool = True,
+                           batch: int | None = None, rng_stride: int | None = None, proof_stride: int | None = None):
+        """prove_batch as the chain of the device-resident leaves in one call (bzh_prove_batch_device / _seeded): the same
+        arguments, marshalled the same way, and (proofs, status) back -- status one byte per proof (bit 0 lookup, 1 grand product,
+        2 degree check, 3 multiopen / opening), or None with want_status=False, when a flagged proof fails the whole batch with
+        BZH_E_RANGE.  rng_device_ptr (with device_ptr): the draws already in device memory, rng_stride bytes apart (default
+        rng_bytes), `batch` proofs.  proof_stride: room per proof in the result buffer, default max_proof_bytes."""
+        L = _bind()
+        ctx = ctx or self.ctx
+        seeded = rng_list is None and rng_device_ptr is None
+        if seeded:
+            assert seeds is not None and all(len(sd) == 32 for sd in seeds)
+            rng_list = list(seeds)
+        if rng_device_ptr is not None:
+            B = batch if batch is not None else len(instances)
+            stride = self.rng_bytes if rng_stride is None else rng_stride
+            rng_p = _VP(rng_device_ptr)
+        else:
+            B = batch if batch is not None else len(rng_list)
+            stride = len(rng_list[0]) if rng_stride is None else rng_stride
+            assert all(len(r) == len(rng_list[0]) for r in rng_list)
+            raw = np.frombuffer(b"".join(rng_list), dtype=np.uint8)
+            rng_p = _VP(raw.ctypes.data)
+        inst, rows = self._instances(instances)
+        pstride = self.max_proof_bytes if proof_stride is None else proof_stride
+        proofs = np.zeros((B, max(pstride, 1)), dtype=np.uint8)
+        lens = (ctypes.c_size_t * max(B, 1))()
+        status = np.zeros(max(B, 1), dtype=np.uint8)
+        st_p = _VP(status.ctypes.data) if want_status else None
+        if device_ptr is not None:
+            adv_p, form, mem = _VP(device_ptr), FORM_MONTGOMERY, MEM_DEVICE
+        else:
+            a = np.ascontiguousarray(advice, dtype=np.uint64)
+            adv_p, form, mem = _VP(a.ctypes.data), FORM_CANONICAL, MEM_HOST
+        if seeded:
+            rc = L.bzh_prove_batch_device_seeded(ctx.handle, self.handle, B, adv_p, form, mem, _VP(inst.ctypes.data), rows, raw.tobytes(),
+                                                 _VP(proofs.ctypes.data), pstride, lens, st_p)
+        else:
+            rc = L.bzh_prove_batch_device(ctx.handle, self.handle, B, adv_p, form, mem, _VP(inst.ctypes.data), rows, rng_p, stride,
+                                          _VP(proofs.ctypes.data), pstride, lens, st_p)
+        ctx._check(rc, "bzh_prove_batch_device")
+        return [bytes(proofs[b, :lens[b]]) for b in range(B)], (status[:B].copy() if want_status else None)
 
 
 def _check(rc: int, where: str):

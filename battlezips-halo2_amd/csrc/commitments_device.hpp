@@ -29,12 +29,14 @@ static size_t commitments_draws(const KeyShape& ks) {
 template <class C>
 static int commitments_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t* advice, const uint64_t* instances, size_t inst_rows,
                                 int form, int mem, const uint8_t* rng, size_t rng_stride, bzh_transcript_batch* tb,
-                                const bzh_commitments_out& out, uint8_t* status) {
+                                const bzh_commitments_out& out, uint8_t* status, bool chained = false) {
     using SF = typename CurveInfo<C>::SF;
     Arena& arena = pk->rt.arena_for(ctx->serial, ctx->device);
-    // (the merged-block rule and its one wait: vanishing_device_t)
-    if (arena.blocks.size() > 1) BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    arena.reset();
+    // (the merged-block rule and its one wait, and `chained`: vanishing_device_t)
+    if (!chained) {
+        if (arena.blocks.size() > 1) BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        arena.reset();
+    }
     Prover<C> pv(ctx, *pk, B, arena);
     const bool host = mem == BZH_MEM_HOST, canonical = form == BZH_FORM_CANONICAL;
     const int field = pk->field;

@@ -379,6 +379,11 @@ size_t multiopen_scratch_bytes(const MoPlan& plan, size_t batch, size_t n);
 int multiopen_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, unsigned k, const MoPlan& plan, const uint32_t* d_polys,
                      const uint32_t* d_shared, const uint32_t* d_blinds, const uint32_t* d_shared_blinds, const uint32_t* d_points, int form,
                      const uint8_t* d_rng, size_t rng_stride, bzh_transcript_batch* tb, uint8_t* d_status, void* d_scratch);
+// the same with every polynomial where it lies: srcs (host memory) holds one MoSrc per polynomial id, own ids first; d_blinds stays
+// the dense [batch][npolys_own] row.  multiopen_device builds this table from its dense operands.
+int multiopen_device_srcs(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, unsigned k, const MoPlan& plan, const MoSrc* srcs,
+                          const uint32_t* d_blinds, const uint32_t* d_shared_blinds, const uint32_t* d_points, int form, const uint8_t* d_rng,
+                          size_t rng_stride, bzh_transcript_batch* tb, uint8_t* d_status, void* d_scratch);
 // k_mo_combine for another caller (evaluations.hip's h(X)): out[z][b][i] = Horner in d_ch[b] over the sources d_first[z] ..
 // d_first[z + 1) of d_srcs, z < lists, n coefficients each, list z at d_out + z * batch * n elements; device pointers, Montgomery
 // form.  Enqueues only.
@@ -399,6 +404,17 @@ size_t evaluations_scratch_bytes(const EvPlan& plan, size_t batch, size_t npiece
 int evaluations_device(bzh_ctx* ctx, int curve, size_t batch, unsigned k, const EvPlan& plan, const uint32_t* d_polys, const uint32_t* d_shared,
                        const uint32_t* d_h, size_t npieces, size_t h_stride, const uint32_t* d_h_blinds, int form, bzh_transcript_batch* tb,
                        uint32_t* d_out_points, uint32_t* d_out_evals, uint32_t* d_out_h, uint32_t* d_out_h_blind, void* d_scratch);
+// the same with every polynomial where it lies: srcs (host memory) holds one MoSrc per polynomial id, own ids first.
+// evaluations_device builds this table from its dense operands.
+int evaluations_device_srcs(bzh_ctx* ctx, int curve, size_t batch, unsigned k, const EvPlan& plan, const MoSrc* srcs, const uint32_t* d_h,
+                            size_t npieces, size_t h_stride, const uint32_t* d_h_blinds, int form, bzh_transcript_batch* tb,
+                            uint32_t* d_out_points, uint32_t* d_out_evals, uint32_t* d_out_h, uint32_t* d_out_h_blind, void* d_scratch);
+// prove_device.hip: the two lane kernels of bzh_prove_batch_device (the call itself reads the key: csrc/prove_device.hpp); device
+// pointers, enqueue only.  prove_device_blinds: d_out[b][nown] = the blind of every opened polynomial of proof b, gathered through
+// the `nsrc` entries of d_srcs (PdBlindSrc, prove_device_scalars.hpp; a null pointer stands for Montgomery 1).
+// prove_device_status: d_slot[b] = {the four leaves' bytes of proof b folded into bits 0 .. 3, proof_len} (two words per proof).
+int prove_device_blinds(bzh_ctx* ctx, int field, const void* d_srcs, size_t nsrc, size_t nown, size_t batch, uint32_t* d_out);
+int prove_device_status(bzh_ctx* ctx, const uint8_t* d_leaf, size_t leaf_stride, size_t batch, uint32_t proof_len, uint32_t* d_slot);
 // vanishing.hip: the two kernels of bzh_vanishing_batch_device (the call itself reads the key: csrc/vanishing_device.hpp); device
 // pointers, 16-byte aligned unless said otherwise; enqueue only.
 // vanishing_consts: d_table[b][i] = value_i * challenge_b^exponent_i over the nconsts descriptors at d_descs (bzh_vanishing_const);
@@ -472,7 +488,12 @@ struct TbInfo {
     int curve;
     size_t batch, proof_cap, proof_len;
 };
-int tb_new_locked(bzh_ctx* ctx, int curve, size_t batch, bzh_transcript_batch** out);
+// proof_cap: room per transcript for written messages (0: a verifier's batch, which writes none).  tb_reserve_points_locked sizes
+// the batch's normalise scratch for writes of up to `points` Jacobian points each, so that no later write has to grow it (growing
+// waits for the stream).  tb_proofs_device: the proofs in device memory, `*pstride` bytes apart.
+int tb_new_locked(bzh_ctx* ctx, int curve, size_t batch, bzh_transcript_batch** out, size_t proof_cap = 0);
+int tb_reserve_points_locked(bzh_transcript_batch* tb, size_t points);
+const uint8_t* tb_proofs_device(const bzh_transcript_batch* tb, size_t* pstride);
 void tb_free_locked(bzh_transcript_batch* tb);
 int tb_absorb_locked(bzh_transcript_batch* tb, int kind, const void* d_base, size_t count, size_t stride, int form, const uint8_t* d_pre);
 int tb_write_jacobian_locked(bzh_transcript_batch* tb, const void* d_xyz, size_t count, size_t stride, int form, int kind = 1);

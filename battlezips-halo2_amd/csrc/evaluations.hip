@@ -208,12 +208,11 @@ size_t evaluations_scratch_bytes(const EvPlan& plan, size_t batch, size_t npiece
 }
 
 template <class C>
-static int evaluations_t(bzh_ctx* ctx, size_t B, unsigned k, const EvPlan& plan, const uint32_t* d_polys, const uint32_t* d_shared,
-                         const uint32_t* d_h, size_t npieces, size_t h_stride, const uint32_t* d_h_blinds, int form, bzh_transcript_batch* tb,
+static int evaluations_t(bzh_ctx* ctx, size_t B, unsigned k, const EvPlan& plan, const MoSrc* srcs, const uint32_t* d_h, size_t npieces, size_t h_stride, const uint32_t* d_h_blinds, int form, bzh_transcript_batch* tb,
                          uint32_t* d_out_points, uint32_t* d_out_evals, uint32_t* d_out_h, uint32_t* d_out_h_blind, void* d_scratch) {
     using SF = typename CurveInfo<C>::SF;
     const int field = CurveInfo<C>::scalar_field;
-    const size_t n = (size_t)1 << k, nown = plan.npolys_own, nq = plan.nqueries, nrot = plan.nrot;
+    const size_t n = (size_t)1 << k, nq = plan.nqueries, nrot = plan.nrot;
     const int canonical = form == BZH_FORM_CANONICAL ? 1 : 0;
     hipStream_t st = ctx->stream;
     EvPasses passes(plan);
@@ -231,10 +230,7 @@ static int evaluations_t(bzh_ctx* ctx, size_t B, unsigned k, const EvPlan& plan,
         const int64_t m = (int64_t)n, e = (((int64_t)plan.rotations[j] % m) + m) % m;
         omegas[j] = h_pow_u64(omega, (uint64_t)e);
     }
-    for (size_t a = 0; a < passes.jobs.size(); a++) {
-        const size_t id = passes.poly[a];
-        passes.jobs[a].src = id < nown ? MoSrc{d_polys + id * n * 8, (uint64_t)(nown * n)} : MoSrc{d_shared + (id - nown) * n * 8, 0};
-    }
+    for (size_t a = 0; a < passes.jobs.size(); a++) passes.jobs[a].src = srcs[passes.poly[a]];
     std::vector<MoSrc> hsrcs;
     for (size_t i = npieces; i-- > 0;) hsrcs.push_back(MoSrc{d_h + i * n * 8, (uint64_t)h_stride});
     const uint32_t hfirst[2] = {0, (uint32_t)npieces};
@@ -281,9 +277,21 @@ static int evaluations_t(bzh_ctx* ctx, size_t B, unsigned k, const EvPlan& plan,
 int evaluations_device(bzh_ctx* ctx, int curve, size_t batch, unsigned k, const EvPlan& plan, const uint32_t* d_polys, const uint32_t* d_shared,
                        const uint32_t* d_h, size_t npieces, size_t h_stride, const uint32_t* d_h_blinds, int form, bzh_transcript_batch* tb,
                        uint32_t* d_out_points, uint32_t* d_out_evals, uint32_t* d_out_h, uint32_t* d_out_h_blind, void* d_scratch) {
+    // the dense operands as a source table: polynomial id of a proof at d_polys + id * n, npolys_own * n between proofs
+    const size_t n = (size_t)1 << k, nown = plan.npolys_own;
+    std::vector<MoSrc> srcs(nown + plan.npolys_shared);
+    for (size_t id = 0; id < srcs.size(); id++)
+        srcs[id] = id < nown ? MoSrc{d_polys + id * n * 8, (uint64_t)(nown * n)} : MoSrc{d_shared + (id - nown) * n * 8, 0};
+    return evaluations_device_srcs(ctx, curve, batch, k, plan, srcs.data(), d_h, npieces, h_stride, d_h_blinds, form, tb, d_out_points,
+                                   d_out_evals, d_out_h, d_out_h_blind, d_scratch);
+}
+
+int evaluations_device_srcs(bzh_ctx* ctx, int curve, size_t batch, unsigned k, const EvPlan& plan, const MoSrc* srcs, const uint32_t* d_h,
+                            size_t npieces, size_t h_stride, const uint32_t* d_h_blinds, int form, bzh_transcript_batch* tb,
+                            uint32_t* d_out_points, uint32_t* d_out_evals, uint32_t* d_out_h, uint32_t* d_out_h_blind, void* d_scratch) {
     return with_curve(curve, [&](auto c) {
-        return evaluations_t<decltype(c)>(ctx, batch, k, plan, d_polys, d_shared, d_h, npieces, h_stride, d_h_blinds, form, tb, d_out_points,
-                                          d_out_evals, d_out_h, d_out_h_blind, d_scratch);
+        return evaluations_t<decltype(c)>(ctx, batch, k, plan, srcs, d_h, npieces, h_stride, d_h_blinds, form, tb, d_out_points, d_out_evals,
+                                          d_out_h, d_out_h_blind, d_scratch);
     });
 }
 

@@ -3,7 +3,9 @@
 // For every (input, table) pair of a batch, over the first `usable` rows:
 //   A' = the input sorted ascending by canonical value;
 //   S'[i] = A'[i] where A'[i] starts a run of equal values; the table values not consumed that way go, ascending, to the
-//   repeated rows from the last repeated row backwards.  An input value without a table copy fails that pair (status word).
+//   repeated rows from the last repeated row backwards.  An input value without a table copy fails that pair (status word);
+//   its run start has no copy to take and is filled like a repeated row, so S' of a failed pair is still a permutation of the
+//   table (and A' of the input): the pair's grand product closes and what gives the pair away is its status word.
 // Equal keys are indistinguishable in the output, so VALUES are sorted, not indices.
 //
 // Pipeline (every launch covers the whole batch; nothing is read back to choose a path):
@@ -13,11 +15,12 @@
 //   general keys     k_lp_tile_sort: bitonic sort of 1024-key tiles in LDS (32 KB, words of a key 1024 apart), then
 //                    k_lp_merge passes: every element finds its slot by co-rank -- its index in its own run plus a lower
 //                    bound (left run) or an upper bound (right run) in the sibling run.  Any usable < 2^31.
-//   k_lp_mark        every run start marks the lower bound of its value in the sorted table as used (or fails the pair)
-//   k_lp_assign      one workgroup per pair, two prefix sums: the repeated row at offset e >= 1 of the run of value v has rank
-//                    q = (repeated rows before the run) + e - 1 (sum over the not-run-start flags); the j-th leftover (sum
-//                    over the not-used flags) lands on the repeated row of rank m - 1 - j, m = number of repeated rows.
-// A pair that fails keeps every index in bounds: surplus leftovers (rank >= m) are dropped.
+//   k_lp_mark        every run start marks the lower bound of its value in the sorted table as used (or fails the pair and marks
+//                    its own row as one without a copy)
+//   k_lp_assign      one workgroup per pair, two prefix sums: the rows to fill -- repeated rows and run starts without a copy --
+//                    are ranked in row order (sum over their flags); the j-th leftover (sum over the not-used flags) lands on
+//                    the row of rank m - 1 - j, m = number of rows to fill.
+// Leftovers and rows to fill are equally many, failed pair or not: usable - (run starts with a copy) of either.
 #include "ctx.hpp"
 #include "field.cuh"
 #include "host_field.hpp"
@@ -239,7 +242,7 @@ __global__ void __launch_bounds__(256) k_lp_merge(const uint32_t* __restrict__ s
 }
 
 __global__ void __launch_bounds__(256) k_lp_mark(const uint32_t* __restrict__ sorted, uint32_t usable, uint32_t* __restrict__ used,
-                                                 int32_t* __restrict__ status) {
+                                                 uint32_t* __restrict__ nocopy, int32_t* __restrict__ status) {
     const size_t pair = blockIdx.y;
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= usable) return;
@@ -249,7 +252,7 @@ __global__ void __launch_bounds__(256) k_lp_mark(const uint32_t* __restrict__ so
     if (i && lp_eq(k, lp_load(a + (size_t)(i - 1) * 8))) return;
     const uint32_t lb = lp_bound(t, usable, k, false);
     if (lb < usable && lp_eq(k, lp_load(t + (size_t)lb * 8))) used[pair * usable + lb] = 1;  // run starts differ: one writer each
-    else status[pair] = BZH_E_RANGE;
+    else status[pair] = BZH_E_RANGE, nocopy[pair * usable + i] = 1;   // (a row of the input: this thread's own)
 }
 
 template <class P>
@@ -263,31 +266,32 @@ static __device__ __forceinline__ void lp_emit(uint32_t* p, const LpKey& k, int 
 
 template <class P>
 __global__ void __launch_bounds__(kLpWide) k_lp_assign(const uint32_t* __restrict__ sorted, uint32_t usable, const uint32_t* __restrict__ used,
-                                                      uint32_t* __restrict__ row_of_rank, uint32_t* __restrict__ out_a,
+                                                      const uint32_t* __restrict__ nocopy, uint32_t* __restrict__ row_of_rank, uint32_t* __restrict__ out_a,
                                                       uint32_t* __restrict__ out_s, size_t out_stride, uint32_t rows, int mont) {
     __shared__ uint32_t wave_sums[kLpWide / 64];
     const size_t pair = blockIdx.x;
     const uint32_t* a = sorted + (2 * pair) * usable * 8;
     const uint32_t* t = a + (size_t)usable * 8;
     used += pair * usable;
+    nocopy += pair * usable;
     row_of_rank += pair * usable;
     out_a += pair * out_stride * 8;
     out_s += pair * out_stride * 8;
     const unsigned tid = threadIdx.x;
-    uint32_t m = 0;  // repeated rows so far
+    uint32_t m = 0;  // rows to fill so far
     for (uint32_t i0 = 0; i0 < usable; i0 += kLpWide) {
         const uint32_t i = i0 + tid;
         LpKey k;
-        uint32_t repeated = 0;
+        uint32_t fill = 0;  // a repeated row, or a run start whose value the table does not hold
         if (i < usable) {
             k = lp_load(a + (size_t)i * 8);
-            repeated = i && lp_eq(k, lp_load(a + (size_t)(i - 1) * 8));
+            fill = (i && lp_eq(k, lp_load(a + (size_t)(i - 1) * 8))) || nocopy[i];
         }
         uint32_t total;
-        const uint32_t q = m + lp_block_exscan(repeated, wave_sums, &total);
+        const uint32_t q = m + lp_block_exscan(fill, wave_sums, &total);
         if (i < usable) {
             lp_emit<P>(out_a + (size_t)i * 8, k, mont);
-            if (repeated) row_of_rank[q] = i;
+            if (fill) row_of_rank[q] = i;
             else lp_emit<P>(out_s + (size_t)i * 8, k, mont);
         }
         m += total;
@@ -300,7 +304,7 @@ __global__ void __launch_bounds__(kLpWide) k_lp_assign(const uint32_t* __restric
         const uint32_t free_ = i < usable && !used[i];
         uint32_t total;
         const uint32_t j = left + lp_block_exscan(free_, wave_sums, &total);
-        if (free_ && j < m)  // (a failed pair has more leftovers than repeated rows)
+        if (free_ && j < m)  // (always: as many leftovers as rows to fill)
             lp_emit<P>(out_s + (size_t)row_of_rank[m - 1 - j] * 8, lp_load(t + (size_t)i * 8), mont);
         left += total;
     }
@@ -318,7 +322,7 @@ inline size_t lp_al(size_t v) { return (v + 255) & ~(size_t)255; }
 }  // namespace
 
 size_t lookup_permute_ws_bytes(size_t usable, size_t batch) {
-    return 2 * lp_al(2 * batch * usable * 32) + 2 * lp_al(batch * usable * 4) + 2 * lp_al(batch * 4);
+    return 2 * lp_al(2 * batch * usable * 32) + 3 * lp_al(batch * usable * 4) + 2 * lp_al(batch * 4);
 }
 
 template <class P>
@@ -334,8 +338,10 @@ static int lookup_permute_t(bzh_ctx* ctx, const uint32_t* d_in, const uint32_t* 
     w += lp_al(2 * batch * usable * 32);
     uint32_t* row_of_rank = (uint32_t*)w;
     w += lp_al(batch * usable * 4);
-    char* zeroed = w;  // used | big | status: cleared in one piece
+    char* zeroed = w;  // used | nocopy | big | status: cleared in one piece
     uint32_t* used = (uint32_t*)w;
+    w += lp_al(batch * usable * 4);
+    uint32_t* nocopy = (uint32_t*)w;
     w += lp_al(batch * usable * 4);
     uint32_t* big = (uint32_t*)w;
     w += lp_al(batch * 4);
@@ -357,8 +363,8 @@ static int lookup_permute_t(bzh_ctx* ctx, const uint32_t* d_in, const uint32_t* 
         hipLaunchKernelGGL(k_lp_merge, per_elem, dim3(256), 0, st, cur, nxt, U, (uint32_t)width, big);
         cur = nxt;
     }
-    hipLaunchKernelGGL(k_lp_mark, dim3((unsigned)((usable + 255) / 256), (unsigned)batch), dim3(256), 0, st, buf1, U, used, status);
-    hipLaunchKernelGGL((k_lp_assign<P>), dim3((unsigned)batch), dim3(kLpWide), 0, st, buf1, U, used, row_of_rank, d_out_a, d_out_s, out_stride,
+    hipLaunchKernelGGL(k_lp_mark, dim3((unsigned)((usable + 255) / 256), (unsigned)batch), dim3(256), 0, st, buf1, U, used, nocopy, status);
+    hipLaunchKernelGGL((k_lp_assign<P>), dim3((unsigned)batch), dim3(kLpWide), 0, st, buf1, U, used, nocopy, row_of_rank, d_out_a, d_out_s, out_stride,
                        (uint32_t)rows, mont);
     BZH_HIP_TRY(ctx, hipGetLastError());
     *d_status = status;

@@ -181,8 +181,8 @@ size_t multiopen_scratch_bytes(const MoPlan& plan, size_t batch, size_t n) {
 }
 
 template <class C>
-static int multiopen_t(bzh_ctx* ctx, const bzh_bases* bases, size_t B, unsigned k, const MoPlan& plan, const uint32_t* d_polys,
-                       const uint32_t* d_shared, const uint32_t* d_blinds, const uint32_t* d_shared_blinds, const uint32_t* d_points, int form,
+static int multiopen_t(bzh_ctx* ctx, const bzh_bases* bases, size_t B, unsigned k, const MoPlan& plan, const MoSrc* poly_srcs,
+                       const uint32_t* d_blinds, const uint32_t* d_shared_blinds, const uint32_t* d_points, int form,
                        const uint8_t* d_rng, size_t rng_stride, bzh_transcript_batch* tb, uint8_t* d_status, void* d_scratch) {
     using SF = typename CurveInfo<C>::SF;
     const int field = CurveInfo<C>::scalar_field;
@@ -222,9 +222,7 @@ static int multiopen_t(bzh_ctx* ctx, const bzh_bases* bases, size_t B, unsigned 
     }
     std::vector<MoSrc> srcs;
     srcs.reserve(L.nsrcs);
-    auto src_of = [&](uint32_t id) {
-        return id < nown ? MoSrc{d_polys + (size_t)id * n * 8, (uint64_t)(nown * n)} : MoSrc{d_shared + (size_t)(id - nown) * n * 8, 0};
-    };
+    auto src_of = [&](uint32_t id) { return poly_srcs[id]; };
     for (size_t pos = 0; pos < nsets; pos++) {   // q, list z = position
         const size_t s = o.order[pos];
         for (uint32_t c = grp_first[s]; c < grp_first[s + 1]; c++) srcs.push_back(src_of(grp_ids[c]));
@@ -309,9 +307,21 @@ static int multiopen_t(bzh_ctx* ctx, const bzh_bases* bases, size_t B, unsigned 
 int multiopen_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, unsigned k, const MoPlan& plan, const uint32_t* d_polys,
                      const uint32_t* d_shared, const uint32_t* d_blinds, const uint32_t* d_shared_blinds, const uint32_t* d_points, int form,
                      const uint8_t* d_rng, size_t rng_stride, bzh_transcript_batch* tb, uint8_t* d_status, void* d_scratch) {
+    // the dense operands as a source table: polynomial id of a proof at d_polys + id * n, npolys_own * n between proofs
+    const size_t n = (size_t)1 << k, nown = plan.npolys_own;
+    std::vector<MoSrc> srcs(nown + plan.npolys_shared);
+    for (size_t id = 0; id < srcs.size(); id++)
+        srcs[id] = id < nown ? MoSrc{d_polys + id * n * 8, (uint64_t)(nown * n)} : MoSrc{d_shared + (id - nown) * n * 8, 0};
+    return multiopen_device_srcs(ctx, bases, batch, k, plan, srcs.data(), d_blinds, d_shared_blinds, d_points, form, d_rng, rng_stride, tb,
+                                 d_status, d_scratch);
+}
+
+int multiopen_device_srcs(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, unsigned k, const MoPlan& plan, const MoSrc* srcs,
+                          const uint32_t* d_blinds, const uint32_t* d_shared_blinds, const uint32_t* d_points, int form, const uint8_t* d_rng,
+                          size_t rng_stride, bzh_transcript_batch* tb, uint8_t* d_status, void* d_scratch) {
     return with_curve(bases->curve, [&](auto c) {
-        return multiopen_t<decltype(c)>(ctx, bases, batch, k, plan, d_polys, d_shared, d_blinds, d_shared_blinds, d_points, form, d_rng,
-                                        rng_stride, tb, d_status, d_scratch);
+        return multiopen_t<decltype(c)>(ctx, bases, batch, k, plan, srcs, d_blinds, d_shared_blinds, d_points, form, d_rng, rng_stride, tb,
+                                        d_status, d_scratch);
     });
 }
 

@@ -18,11 +18,13 @@ template <class C>
 static int products_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t* advice, const uint64_t* instance, const uint64_t* lookup_compressed,
                              const uint64_t* lookup_permuted, const uint64_t* beta, const uint64_t* gamma, int form, int mem, const uint8_t* rng,
                              size_t rng_stride, bzh_transcript_batch* tb, uint64_t* out_z, uint64_t* out_z_polys, uint64_t* out_z_blinds,
-                             uint8_t* status) {
+                             uint8_t* status, bool chained = false, bool commit_evals = false) {
     Arena& arena = pk->rt.arena_for(ctx->serial, ctx->device);
-    // (the merged-block rule and its one wait: vanishing_device_t)
-    if (arena.blocks.size() > 1) BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    arena.reset();
+    // (the merged-block rule and its one wait, and `chained`: vanishing_device_t)
+    if (!chained) {
+        if (arena.blocks.size() > 1) BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        arena.reset();
+    }
     Prover<C> pv(ctx, *pk, B, arena);
     const bool host = mem == BZH_MEM_HOST, canonical = form == BZH_FORM_CANONICAL;
     const int field = pk->field;
@@ -104,7 +106,9 @@ static int products_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t*
     BZH_TRY(products_finish(ctx, field, zt_all, drawn, n, pk->usable, bf, nsets, nl, B, zs, zb, d_st, tb_status_device_mut(tb)));
     if (zs != zp) BZH_TRY(pv.to_coeff(zp, zs, B * nz));
     else BZH_TRY(ntt_run(ctx, field, zp, pk->k, B * nz, pk->omega, nullptr, 1, BZH_FORM_MONTGOMERY));
-    BZH_TRY(leaf_commit_write(pv, tb, zp, zb, B * nz, nz));
+    // commit_evals (bzh_prove_batch_device, with out_z): the products over the domain go to leaf_commit_write as well, which commits
+    // them against g_lagrange when the key has that table -- the same points; this leaf's own entry passes none
+    BZH_TRY(leaf_commit_write(pv, tb, zp, zb, B * nz, nz, commit_evals && zs != zp ? zs : nullptr));
 
     // the outputs in the caller's form, and to the host
     if (canonical) {

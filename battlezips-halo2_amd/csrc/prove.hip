@@ -45,6 +45,7 @@
 #include "vanishing_scalars.hpp"   // (bzh_vanishing_const as the lane body reads it)
 #include "products_scalars.hpp"    // (the column table as k_gp_factors reads it)
 #include "commitments_scalars.hpp" // (the constant descriptors as k_cm_consts reads them)
+#include "prove_device_scalars.hpp" // (the blind sources as k_pd_blinds reads them)
 #include "vm2_isa.hpp"
 
 // the table of quotient kernels generated at build time (quotient_builtin.hip); absent (null) in the generator's own link
@@ -62,6 +63,7 @@ extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __at
 #include "vanishing_device.hpp"   // phase 5 of the prover as a leaf on device-resident transcripts
 #include "products_device.hpp"    // phase 4 likewise
 #include "commitments_device.hpp" // phases 1 to 3 likewise
+#include "prove_device.hpp"       // the five leaves as one call: the device-resident batch prover
 #include "verifier.hpp"
 
 // pk.get_vk(): the commitments to the fixed and permutation polynomials (blind 1), computed once per key
@@ -748,6 +750,61 @@ int bzh_commitments_batch_device(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const u
         ctx->pending_d2h.clear();
     }
     return rc;
+}
+
+int bzh_prove_device_plan(int curve, const uint8_t* circuit, size_t circuit_len, uint32_t shape8[8]) {
+    if (!circuit || !shape8) return BZH_E_ARG;
+    bzh_pk pk;
+    BZH_TRY(bzh::with_pasta_curve(curve, [&](auto c) {
+        bzh::ParsedKey<typename bzh::CurveInfo<decltype(c)>::SF> po;
+        return bzh::pk_parse_t<decltype(c)>(circuit, circuit_len, pk, po);
+    }));
+    size_t nd[4];
+    bzh::prove_device_draws(pk, nd);
+    const uint32_t shape[8] = {(uint32_t)nd[0], (uint32_t)nd[1], (uint32_t)nd[2], (uint32_t)nd[3], (uint32_t)(nd[0] + nd[1] + nd[2] + nd[3]),
+                               (uint32_t)bzh::prove_device_proof_bytes(pk), (uint32_t)bzh::prove_device_nown(pk), (uint32_t)bzh::prove_device_max_batch(pk)};
+    memcpy(shape8, shape, sizeof(shape));
+    return BZH_OK;
+}
+
+// rng_stride == 0: `rng` holds batch x 32-byte seeds (bzh_prove_batch_device_seeded)
+static int prove_batch_device_entry(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice, int form, int mem, const uint64_t* instances,
+                                    size_t instance_rows, const uint8_t* rng, size_t rng_stride, uint8_t* proofs, size_t proof_stride,
+                                    size_t* proof_lens, uint8_t* status) {
+    // what reads neither the key nor the device
+    if (!ctx || !pk || !batch || !advice || !rng || !proofs || !proof_lens) return BZH_E_ARG;
+    if ((form != BZH_FORM_CANONICAL && form != BZH_FORM_MONTGOMERY) || (mem != BZH_MEM_HOST && mem != BZH_MEM_DEVICE)) return BZH_E_ARG;
+    if (mem == BZH_MEM_DEVICE && (form != BZH_FORM_MONTGOMERY || ((uintptr_t)advice & 15))) return BZH_E_ARG;
+    bzh::KeyRuntime::Call in_flight(pk->rt);   // until the proofs are in the caller's buffers
+    // what reads the key
+    if (pk->device != ctx->device || (rng_stride != 0 && rng_stride < pk->rng_bytes) || (pk->ni && instance_rows && !instances) ||
+        instance_rows > pk->usable || batch > bzh::prove_device_max_batch(*pk))
+        return BZH_E_ARG;
+    if (!pk->q_ok || pk->en % 128) return BZH_E_RANGE;   // no VM v2 program, or a domain below its workgroup (bzh_vanishing_batch_device)
+    if (proof_stride < bzh::prove_device_proof_bytes(*pk)) return BZH_E_RANGE;
+    const bzh::PdPlan* plan = nullptr;
+    BZH_TRY(bzh::prove_device_plan_of(pk, &plan));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return bzh::with_pasta_curve(pk->curve, [&](auto c) {
+        return bzh::prove_device_t<decltype(c)>(ctx, pk, batch, advice, form, mem, instances, instance_rows, rng, rng_stride, *plan, proofs,
+                                                proof_stride, proof_lens, status);
+    });
+}
+
+int bzh_prove_batch_device(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice, int form, int mem, const uint64_t* instances,
+                           size_t instance_rows, const uint8_t* rng, size_t rng_stride, uint8_t* proofs, size_t proof_stride,
+                           size_t* proof_lens, uint8_t* status) {
+    if (rng_stride == 0) return BZH_E_ARG;
+    return prove_batch_device_entry(ctx, pk, batch, advice, form, mem, instances, instance_rows, rng, rng_stride, proofs, proof_stride,
+                                    proof_lens, status);
+}
+
+int bzh_prove_batch_device_seeded(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice, int form, int mem,
+                                  const uint64_t* instances, size_t instance_rows, const uint8_t* seeds, uint8_t* proofs, size_t proof_stride,
+                                  size_t* proof_lens, uint8_t* status) {
+    return prove_batch_device_entry(ctx, pk, batch, advice, form, mem, instances, instance_rows, seeds, 0, proofs, proof_stride, proof_lens,
+                                    status);
 }
 
 int bzh_rng_expand(const uint8_t* seed, uint64_t first_draw, size_t draws, uint8_t* out) {

@@ -461,7 +461,7 @@ struct Prover : DeviceColumns<C> {
     // so the destination outlives this scope) and land at the d2h_finish of this lookup's own commitment; lookups() reads them
     // there, before anything of this lookup goes into a transcript.  Committing the columns of a pair that turns out to have
     // failed is safe: such a pair keeps every index in bounds and still writes every row below `usable` of both columns with a
-    // reduced field element (it has more leftovers than repeated rows and drops the surplus: csrc/lookup_permute.hip).
+    // reduced field element (a run start without a table copy is filled with a leftover like a repeated row: csrc/lookup_permute.hip).
     // The workspace goes back to the arena when the scope ends, before the device has run any of this: its kernels and the copy
     // of the status words are queued on the ctx's stream, and so is everything that takes the same arena memory afterwards (all
     // device work of a prove call runs on that one stream), so the later work cannot overtake them.

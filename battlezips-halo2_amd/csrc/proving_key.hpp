@@ -8,6 +8,18 @@
 // ---------------------------------------------------------------------------
 // the proving key
 // ---------------------------------------------------------------------------
+namespace bzh {
+// what bzh_prove_batch_device derives from the KeyShape when the key first needs it (csrc/prove_device.hpp): the query structure
+// of the evaluations and the multiopen over the opened polynomials of a proof and the key's own.  rc: BZH_E_RANGE when those two
+// leaves do not take the circuit's queries
+struct PdPlan {
+    bool ready = false;
+    int rc = 0;
+    EvPlan ev;
+    MoPlan mo;
+};
+}  // namespace bzh
+
 // (the constraint system's shape, the multiopen structure and the vk commitments -- what the verifier reads -- are the KeyShape)
 struct bzh_pk : bzh::KeyShape {
     int device = 0;
@@ -49,6 +61,7 @@ struct bzh_pk : bzh::KeyShape {
     int vpass_select = BZH_VERIFY_PASS_HOST;  // BZH_VERIFY_PASS_*: where bzh_verify_batch runs the per-proof pass (bzh_pk_verify_pass_select)
     int vp_select = BZH_VERIFY_POINTS_HOST;   // BZH_VERIFY_POINTS_*: where bzh_verify_batch decompresses the proofs' points (bzh_pk_verify_select)
     size_t rng_bytes = 0;
+    bzh::PdPlan pd_plan;   // guarded by rt.mu until `ready`, read-only after
     // verifying key: the KeyShape's commitments to the fixed and permutation polynomials are computed at the first verification
     bool vk_ready = false;
     // the constraint-system part of the blob the key was made from, as bzh_vk keeps it (csrc/verifying_key.hpp)

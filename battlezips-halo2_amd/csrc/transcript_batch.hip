@@ -206,12 +206,14 @@ static int tb_device_init(bzh_transcript_batch* tb, const std::vector<uint64_t>&
 // the same object for a caller inside the library that already holds ctx->mu (the verifier's device pass, csrc/verifier.hpp):
 // device operands only, enqueue only, no argument checks beyond the kind
 // ---------------------------------------------------------------------------
-int tb_new_locked(bzh_ctx* ctx, int curve, size_t batch, bzh_transcript_batch** out) {
-    if (!ctx || !out || !valid_curve(curve) || !batch || batch > kMaxBatch) return BZH_E_ARG;
+int tb_new_locked(bzh_ctx* ctx, int curve, size_t batch, bzh_transcript_batch** out, size_t proof_cap) {
+    if (!ctx || !out || !valid_curve(curve) || !batch || batch > kMaxBatch || proof_cap > kMaxProofCap) return BZH_E_ARG;
+    const size_t pstride = round_up(proof_cap, 32);
+    if (pstride && batch > ((size_t)1 << 32) / pstride) return BZH_E_ARG;
     bzh_transcript_batch* tb = new (std::nothrow) bzh_transcript_batch();
     if (!tb) return BZH_E_OOM;
-    tb->ctx = ctx, tb->curve = curve, tb->batch = batch;
-    tb->S.batch = batch;
+    tb->ctx = ctx, tb->curve = curve, tb->batch = batch, tb->proof_cap = proof_cap;
+    tb->S.batch = batch, tb->S.pstride = pstride;
     std::vector<uint64_t> words;
     fresh_words(batch, words);
     const int rc = tb_device_init(tb, words);
@@ -277,6 +279,11 @@ int tb_squeeze_locked(bzh_transcript_batch* tb, int form, uint32_t* d_out) {
 }
 const uint8_t* tb_status_device(const bzh_transcript_batch* tb) { return tb->S.status; }
 uint8_t* tb_status_device_mut(bzh_transcript_batch* tb) { return tb->S.status; }
+int tb_reserve_points_locked(bzh_transcript_batch* tb, size_t points) { return scratch_ensure(tb, points * 64 + points + 256); }
+const uint8_t* tb_proofs_device(const bzh_transcript_batch* tb, size_t* pstride) {
+    *pstride = tb->S.pstride;
+    return tb->S.proofs;
+}
 
 }  // namespace bzh
 

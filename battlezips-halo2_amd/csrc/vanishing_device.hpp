@@ -101,16 +101,20 @@ template <class C>
 static int vanishing_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t* advice_polys, const uint64_t* instance_polys,
                               const uint64_t* lookup_polys, const uint64_t* z_polys, const uint64_t* theta, const uint64_t* beta,
                               const uint64_t* gamma, int form, int mem, const uint8_t* rng, size_t rng_stride, bzh_transcript_batch* tb,
-                              uint64_t* out_random, uint64_t* out_random_blind, uint64_t* out_h, uint64_t* out_h_blinds, uint8_t* status) {
+                              uint64_t* out_random, uint64_t* out_random_blind, uint64_t* out_h, uint64_t* out_h_blinds, uint8_t* status,
+                              bool chained = false) {
     using SF = typename CurveInfo<C>::SF;
     Arena& arena = pk->rt.arena_for(ctx->serial, ctx->device);
     // A BZH_MEM_DEVICE call returns with its work still queued on ctx->stream, and that work reads and writes the arena
     // (bzh_prove_batch never leaves any: it waits for its proofs).  Reusing the one merged block from its start is ordered
     // behind that work by the stream.  While the arena is still a list of blocks -- after a key's first call of a shape --
     // reset() frees them and allocates the merged block, so the queued work is waited for first: one stream wait on that
-    // call, none on the calls after it (include/bzh2.h says so).
-    if (arena.blocks.size() > 1) BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    arena.reset();
+    // call, none on the calls after it (include/bzh2.h says so).  `chained`: a step of bzh_prove_batch_device (prove_device.hpp),
+    // which has reset the arena itself, keeps its own buffers in it and wraps every step in an ArenaScope.
+    if (!chained) {
+        if (arena.blocks.size() > 1) BZH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        arena.reset();
+    }
     Prover<C> pv(ctx, *pk, B, arena);
     const bool host = mem == BZH_MEM_HOST, canonical = form == BZH_FORM_CANONICAL;
     const int field = pk->field;

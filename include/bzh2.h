@@ -806,6 +806,53 @@ int bzh_prove_batch_seeded(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_
 /* host: draws [first_draw, first_draw + draws) of the stream of `seed`, 64 bytes each, into out */
 int bzh_rng_expand(const uint8_t* seed, uint64_t first_draw, size_t draws, uint8_t* out);
 
+/* THE DEVICE-RESIDENT BATCH PROVER: create_proof as ONE call that runs the five leaves above -- the witness commitments, the grand
+ * products, the vanishing argument, the evaluations and the multiopen with its opening -- on one device transcript batch inside the
+ * library.  It takes what bzh_prove_batch takes and returns what it returns, and additionally reports failures PER PROOF.
+ * advice, form, mem, instances (host, canonical), instance_rows (0 is accepted, `instances` is then not read), rng / rng_stride (or
+ * seeds), proofs, proof_stride and proof_lens mean what they mean in bzh_prove_batch / bzh_prove_batch_seeded; with
+ * BZH_MEM_DEVICE `rng` may also be a device pointer (16-byte aligned, rng_stride a multiple of 16) -- the chain's natural position:
+ * the draws are then read where they lie.  proofs, proof_lens and status are host memory.  The proofs are byte-identical to
+ * bzh_prove_batch's for the same key, witness and draws, and bzh_prove_batch_device_seeded's to bzh_prove_batch_seeded's: it
+ * expands every proof's stream on the device with the same ChaCha20 expansion (bzh_rng_expand), no draw is generated or uploaded by
+ * the host.
+ * status, one byte per proof, folds the four leaves' per-proof bytes: bit 0 a lookup input is not in its table, bit 1 a grand product
+ * does not close, bit 2 the quotient's degree check failed, bit 3 the multiopen or the opening flagged the proof (coincident points,
+ * u_j = 0).  A flagged proof still gets all its bytes and disturbs no other proof.  With status != NULL the call returns BZH_OK and
+ * the caller reads the bytes; with status == NULL a batch with any flagged proof returns BZH_E_RANGE and writes nothing, as
+ * bzh_prove_batch fails the whole batch, and bzh_last_error names the first flagged proof and its bits.
+ * bzh_prove_device_plan is host only (no ctx, no device).  shape8: the draws per proof of the four drawing leaves in chain order
+ * (commitments, grand products, vanishing, multiopen with the opening); their sum (= rng_bytes_per_proof / 64 of bzh_pk_info); the
+ * proof bytes; nown, the polynomials of a proof that get opened (instance, advice, the random polynomial, grand products, permuted
+ * lookup columns, h(X)); the largest batch the call accepts, 65535 / max(na, ni, 2 * nl, nz, npieces): the commitments of a kind
+ * are one launch with one row of its grid per commitment.
+ * Inside, under the key's guard and in the key's workspace for this ctx: a new device transcript batch absorbs the key's vk_repr;
+ * the five leaf bodies run without their entry points' second round of argument checks; the proofs, the status bytes and the
+ * lengths are read back once.  The query lists and the rotation list of the evaluations and the multiopen are built from the key's
+ * own constraint system in upstream's order when the key first needs them and kept with the key.  The fixed and permutation
+ * polynomials are the key's own, with blind 1, read in place.  No copy of size n is made between the leaves: the evaluations and
+ * the multiopen read every polynomial where its leaf left it, through a table of (pointer, per-proof stride); one launch
+ * (k_pd_blinds) gathers the [batch][nown] blind row of the multiopen, one (k_pd_status) folds the status bytes.  With g_lagrange
+ * (bzh_pk_set_lagrange) the grand products are committed in the Lagrange basis as well -- the same bytes.  The digest, the blinds
+ * of the key's polynomials and the blind table's sources go up before the first launch, and each leaf body uploads its programs,
+ * registries and descriptor tables as its first work on the stream; after that the call only enqueues, makes ONE stream wait at
+ * the end for the read-back, and the one-time wait of the call that merges the workspace's blocks.  No challenge, scalar or point
+ * comes to the host before that read-back.  Its speed against bzh_prove_batch: DESIGN.md section 5.
+ * BZH_E_ARG, nothing written and the key usable: what bzh_prove_batch refuses (a NULL ctx, pk, advice, rng / seeds, proofs or
+ * proof_lens; batch == 0; unknown form or mem; BZH_MEM_DEVICE with canonical form; a key on another device than ctx; rng_stride
+ * below rng_bytes_per_proof; instance_rows > usable; instance rows without `instances`), a batch above the plan's limit, a
+ * misaligned device pointer.  BZH_E_RANGE, likewise: a key without a VM v2 quotient program (or an extended domain below its
+ * workgroup), a lookup whose expressions do not fit the expression interpreter, a circuit whose queries the evaluations or the
+ * multiopen do not take, a proof_stride below the proof bytes.  Every check but the lookup's (decided when the commitments leaf
+ * finds or compiles the key's cached programs) and the alignment of a device `rng` comes before the first use of ctx. */
+int bzh_prove_device_plan(int curve, const uint8_t* circuit, size_t circuit_len, uint32_t shape8[8]);
+int bzh_prove_batch_device(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice, int form, int mem, const uint64_t* instances,
+                           size_t instance_rows, const uint8_t* rng, size_t rng_stride, uint8_t* proofs, size_t proof_stride,
+                           size_t* proof_lens, uint8_t* status);
+int bzh_prove_batch_device_seeded(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice, int form, int mem,
+                                  const uint64_t* instances, size_t instance_rows, const uint8_t* seeds, uint8_t* proofs, size_t proof_stride,
+                                  size_t* proof_lens, uint8_t* status);
+
 /* ---- Params::new (halo2_proofs poly::commitment::Params; benches/shot.rs:58, benches/board.rs:51, and on every call of
  * the wasm exports, src/wasm/circuit_wasm.rs:57,97,145,180) -------------------------------------------------------
  * A pure function of k: g[i] = hash_to_curve("Halo2-Parameters")(0u8 || i as u32 LE), g_lagrange = inverse group FFT of

@@ -7,7 +7,11 @@ in host memory when it returns; the draws, 2.1 MB a proof, come from host memory
 crosses to the device, which is also the chain's position: its draws lie in device memory before the call) and `chain` (a new device transcript batch, common_scalars(vk_repr), then
 bzh_commitments_batch_device, bzh_grand_products_batch_device, bzh_vanishing_batch_device, bzh_evaluations_batch_device and
 bzh_multiopen_batch_device with the opening, every operand a BZH_MEM_DEVICE buffer in Montgomery form, one 64-byte draw stream
-per proof cut at the leaves' draw counts, and bzh_transcript_batch_proofs into host memory at the end).  One warm-up call and
+per proof cut at the leaves' draw counts, and bzh_transcript_batch_proofs into host memory at the end), `prove_batch_device`
+(bzh_prove_batch_device: the same chain inside the library in one call, the key's own fixed and permutation polynomials, no
+arrangement copies; the advice and the draws in device memory, the chain's position) and `prove_batch_device_seeded`
+(bzh_prove_batch_device_seeded, the seeds of `prove_batch_seeded`).  The two one-call settings use the key's real polynomials, so
+their proofs must verify: the tool checks verified == batch for them.  One warm-up call and
 five timed calls; the median is the figure.  The `chain` process then makes one more call with a stream wait after every leaf,
 whose wall times per leaf are `leaf_ms` (their sum is above the timed call's, which waits only where it must).
 
@@ -18,7 +22,7 @@ out, are uniform values in those two leaves' `shared` operand.  Their work does 
 then do not verify: byte parity with bzh_prove_batch and the oracle is tests/test_gpu_commitments_device.py's business, this
 tool only times.
 
-    python tools/ubench_device_chain.py > profiles/device_chain_calls.json
+    python tools/ubench_device_chain.py > profiles/prove_device_calls.json
 
 It only prints: one JSON object per setting and a final summary.  A setting whose process ends abnormally stops the run.
 """
@@ -109,17 +113,28 @@ def measure(args):
     row = {"k": k, "batch": B, "setting": args.setting, "draws_per_proof": total, "leaf_draws": [nd_c, nd_g, nd_v, nd_m],
            "queries": [len(P["ev"]), len(P["mo"])], "table_polynomials": nown, "shared_polynomials": nf + m}
 
-    if args.setting in ("prove_batch", "prove_batch_seeded"):
-        seeded = args.setting == "prove_batch_seeded"
+    if args.setting in ("prove_batch", "prove_batch_seeded", "prove_batch_device", "prove_batch_device_seeded"):
+        seeded = args.setting.endswith("_seeded")
+        one_call = "_device" in args.setting
         rng_list = None if seeded else [streams[b * 64 * total:(b + 1) * 64 * total] for b in range(B)]
         seeds = [streams[32 * b:32 * (b + 1)] for b in range(B)] if seeded else None
-        got = []
+        d_rng = torch.from_numpy(np.frombuffer(streams, dtype=np.uint8).copy()).to("cuda") if one_call and not seeded else None
+        got, flagged = [], []
 
         def once():
-            got[:] = pk.prove_batch(None, insts, rng_list, device_ptr=r.adv[0].data_ptr(), seeds=seeds, ctx=wctx)
+            if not one_call:
+                got[:] = pk.prove_batch(None, insts, rng_list, device_ptr=r.adv[0].data_ptr(), seeds=seeds, ctx=wctx)
+            elif seeded:
+                got[:], flagged[:] = pk.prove_batch_device(None, insts, seeds=seeds, device_ptr=r.adv[0].data_ptr(), ctx=wctx)
+            else:
+                got[:], flagged[:] = pk.prove_batch_device(None, insts, device_ptr=r.adv[0].data_ptr(), rng_device_ptr=d_rng.data_ptr(),
+                                                           rng_stride=64 * total, ctx=wctx)
         secs = timed(once)
         row["proof_bytes"] = len(got[0])
         row["verified"] = int(sum(pk.verify_batch(insts, got, ctx=wctx)))
+        if one_call:
+            row["flagged"] = int(sum(bool(x) for x in flagged))
+            assert row["verified"] == B and not row["flagged"], row
     else:
         cid, MO, DEV = bzh2.CURVE_VESTA, bzh2.FORM_MONTGOMERY, bzh2.MEM_DEVICE
         p_mod = pk.p
@@ -210,7 +225,8 @@ def measure(args):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--role", choices=["drive", "measure"], default="drive")
-    ap.add_argument("--setting", choices=["prove_batch", "prove_batch_seeded", "chain"], default="chain")
+    ap.add_argument("--setting", choices=["prove_batch", "prove_batch_seeded", "chain", "prove_batch_device", "prove_batch_device_seeded"],
+                    default="chain")
     ap.add_argument("--k", type=int, default=14)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--limit", type=int, default=240, help="seconds each child process may take")
@@ -223,7 +239,7 @@ def main():
     if args.role == "measure":
         return measure(args)
     rows = []
-    for setting in ("prove_batch", "prove_batch_seeded", "chain"):
+    for setting in ("prove_batch", "prove_batch_seeded", "chain", "prove_batch_device", "prove_batch_device_seeded"):
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--role", "measure", "--setting", setting, "--k", str(args.k), "--batch",
                             str(args.batch)], check=True, timeout=args.limit, stdout=subprocess.PIPE, text=True)
         print(r.stdout.strip(), flush=True)
