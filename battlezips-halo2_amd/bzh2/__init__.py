@@ -1181,6 +1181,8 @@ EXPORTS += ["bzh_circuit_create", "bzh_circuit_free", "bzh_circuit_last_error", 
             "bzh_shot_serialize", "bzh_pedersen_commit_host", "bzh_fixed_base_tables", "bzh_circuit_set_vk_repr", "bzh_circuit_vk_repr",
             "bzh_pedersen_commit_batch"]
 EXPORTS += ["bzh_synthesize_shot_with", "bzh_synthesize_board_with"]
+# game inputs in, proofs out, in one device-resident call (NativeProvingKey.prove_shots_device / prove_boards_device)
+EXPORTS += ["bzh_prove_shots_device", "bzh_prove_boards_device"]
 E_VERIFY = -6
 
 

@@ -34,6 +34,10 @@ def _bind():
                                          ctypes.c_size_t, _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), _VP]
     L.bzh_prove_batch_device_seeded.argtypes = [_VP, _VP, ctypes.c_size_t, _VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t,
                                                 ctypes.c_char_p, _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), _VP]
+    L.bzh_prove_shots_device.argtypes = [_VP, _VP, _VP, ctypes.c_size_t, _VP, _VP, _VP, _VP, ctypes.c_char_p, _VP, _VP, ctypes.c_size_t,
+                                         ctypes.POINTER(ctypes.c_size_t), _VP]
+    L.bzh_prove_boards_device.argtypes = [_VP, _VP, _VP, ctypes.c_size_t, _VP, _VP, _VP, ctypes.c_char_p, _VP, _VP, ctypes.c_size_t,
+                                          ctypes.POINTER(ctypes.c_size_t), _VP]
     L.bzh_pk_vk_repr.argtypes = [_VP, _VP, ctypes.POINTER(ctypes.c_int)]
     szp, u32p = ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32)
     L.bzh_vk_create.argtypes = [_VP, _VP, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_VP)]
@@ -416,6 +420,47 @@ class NativeProvingKey:
                                           _VP(proofs.ctypes.data), pstride, lens, st_p)
         ctx._check(rc, "bzh_prove_batch_device")
         return [bytes(proofs[b, :lens[b]]) for b in range(B)], (status[:B].copy() if want_status else None)
+
+    def _prove_game_device(self, layout, circuits, seeds, ctx, want_status, shot):
+        from .circuits import _limbs
+        L = _bind()
+        ctx = ctx or self.ctx
+        B = len(circuits)
+        assert len(seeds) == B and all(len(sd) == 32 for sd in seeds)
+        rows = layout.num_instance_rows
+        inst = np.zeros((max(B, 1), max(rows, 1), 4), dtype=np.uint64)
+        proofs = np.zeros((max(B, 1), max(self.max_proof_bytes, 1)), dtype=np.uint8)
+        lens = (ctypes.c_size_t * max(B, 1))()
+        status = np.zeros(max(B, 1), dtype=np.uint8)
+        st_p = _VP(status.ctypes.data) if want_status else None
+        boards = _limbs([c.board.value for c in circuits])
+        traps = _limbs([c.board_commitment_trapdoor for c in circuits])
+        tail = (b"".join(seeds), _VP(inst.ctypes.data), _VP(proofs.ctypes.data), self.max_proof_bytes, lens, st_p)
+        if shot:
+            shots, hits = _limbs([c.shot.value for c in circuits]), _limbs([c.hit.value for c in circuits])
+            rc = L.bzh_prove_shots_device(ctx.handle, self.handle, layout.handle, B, _VP(boards.ctypes.data), _VP(traps.ctypes.data),
+                                          _VP(shots.ctypes.data), _VP(hits.ctypes.data), *tail)
+        else:
+            ships = _limbs([s.value for c in circuits for s in c.ship_commitments])
+            rc = L.bzh_prove_boards_device(ctx.handle, self.handle, layout.handle, B, _VP(ships.ctypes.data), _VP(boards.ctypes.data),
+                                           _VP(traps.ctypes.data), *tail)
+        ctx._check(rc, "bzh_prove_shots_device" if shot else "bzh_prove_boards_device")
+        from . import limbs_to_int
+        instances = [[[limbs_to_int(inst[b, r]) for r in range(rows)]] for b in range(B)]
+        return instances, [bytes(proofs[b, :lens[b]]) for b in range(B)], (status[:B].copy() if want_status else None)
+
+    def prove_shots_device(self, layout, circuits, seeds, ctx: Context | None = None, want_status: bool = True):
+        """game inputs in, proofs out, in one device-resident call (bzh_prove_shots_device): `circuits` are bzh2.circuits.ShotCircuit,
+        `layout` the Shot CircuitLayout this key was made from, `seeds` 32 bytes per proof (the SECURITY note of prove_batch's seeds
+        holds).  Returns (instances, proofs, status): the instances as CircuitLayout.synthesize returns them, the proofs
+        byte-identical to layout.synthesize(where="device") followed by prove_batch_device(seeds=...), status one byte per proof
+        -- bits 0 .. 3 as prove_batch_device's, bits 4 .. 6 the synthesis status (exceptional addition, window point with x = 0,
+        non-canonical message) -- or None with want_status=False, when a flagged proof fails the whole batch with BZH_E_RANGE."""
+        return self._prove_game_device(layout, circuits, seeds, ctx, want_status, True)
+
+    def prove_boards_device(self, layout, circuits, seeds, ctx: Context | None = None, want_status: bool = True):
+        """prove_shots_device for bzh2.circuits.BoardCircuit and the Board layout (bzh_prove_boards_device)"""
+        return self._prove_game_device(layout, circuits, seeds, ctx, want_status, False)
 
 
 def _check(rc: int, where: str):

@@ -648,11 +648,14 @@ int bzh_circuit_vk_repr(const bzh_circuit* c, uint8_t* out_repr, int* is_placeho
 }
 
 // BZH_SYNTH_DEVICE: the inputs are checked and staged here, the witness is computed by csrc/synthesize_device.hip's kernels
-static int synthesize_device(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const BatchInputs& bi, uint64_t* advice, uint64_t* instances) {
-    bzh::SynLayout L;
+// step one, "check and pack the inputs": no device use (bzh::synth_pack_inputs hands it to the prover's translation unit)
+static int synthesize_device_pack(const bzh_circuit* c, size_t batch, const BatchInputs& bi, bzh::SynLayout* layout, std::vector<uint64_t>* packed,
+                                  std::string* err) {
+    bzh::SynLayout& L = *layout;
     BZH_TRY(bzh::synth_layout(c, &L));
     const bool shot = c->kind == BZH_CIRCUIT_SHOT;
-    std::vector<uint64_t> in(batch * L.in_words);
+    packed->assign(batch * L.in_words, 0);
+    std::vector<uint64_t>& in = *packed;
     try {
         // the host path's refusals that depend on the inputs alone, before anything is launched, with its error texts
         for (size_t i = 0; i < batch; i++) {
@@ -668,9 +671,22 @@ static int synthesize_device(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, c
         }
     } catch (const std::exception& e) {
         g_circuit_error = e.what();
-        ctx->last_error = e.what();
+        if (err) *err = e.what();
         return BZH_E_RANGE;
     }
+    return BZH_OK;
+}
+// step two, the run: enqueue, then read back
+static int synthesize_device(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const BatchInputs& bi, uint64_t* advice, uint64_t* instances) {
+    bzh::SynLayout L;
+    std::vector<uint64_t> in;
+    std::string err;
+    const int prc = synthesize_device_pack(c, batch, bi, &L, &in, &err);
+    if (prc) {
+        if (prc == BZH_E_RANGE) ctx->last_error = err;
+        return prc;
+    }
+    const bool shot = c->kind == BZH_CIRCUIT_SHOT;
     std::lock_guard<std::mutex> lk(ctx->mu);
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<uint32_t> status(batch);
@@ -681,9 +697,7 @@ static int synthesize_device(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, c
     BZH_TRY(bzh::synth_device_run(ctx, run));
     for (size_t i = 0; i < batch; i++) {
         if (!status[i]) continue;
-        const char* what = (status[i] & bzh::SYN_ST_MESSAGE)       ? "pedersen_commit: message repr is not a canonical scalar"
-                           : (status[i] & bzh::SYN_ST_WINDOW_X0)   ? "fixed-base mul: window point with x = 0"
-                                                                   : "incomplete addition: exceptional case";
+        const char* what = bzh::syn_status_text(status[i]);
         g_circuit_error = what;
         ctx->last_error = what;
         return BZH_E_RANGE;
@@ -701,6 +715,24 @@ static int synthesize_device(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, c
     }
     return BZH_OK;
 }
+
+}  // extern "C"
+namespace bzh {
+int synth_shape(const bzh_circuit* c, SynShape* out) {
+    if (!c || !out) return BZH_E_ARG;
+    out->kind = c->kind, out->n = c->keygen.n, out->num_advice = (size_t)c->cs.num_advice, out->num_instance = (size_t)c->cs.num_instance,
+    out->inst_rows = (size_t)c->num_instance_rows;
+    return BZH_OK;
+}
+int synth_pack_inputs(const bzh_circuit* c, size_t batch, const uint64_t* a, const uint64_t* b, const uint64_t* c_in, const uint64_t* d,
+                      SynLayout* layout, std::vector<uint64_t>* in, std::string* err) {
+    if (!c || !batch || !layout || !in || !a || !b || !c_in || (c->kind == BZH_CIRCUIT_SHOT && !d)) return BZH_E_ARG;
+    BatchInputs bi;
+    bi.a = a, bi.b = b, bi.c = c_in, bi.d = d;
+    return synthesize_device_pack(c, batch, bi, layout, in, err);
+}
+}  // namespace bzh
+extern "C" {
 
 static int synthesize_any(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const BatchInputs& bi, uint64_t* advice, int form, int mem,
                           uint64_t* instances, unsigned threads, int where = BZH_SYNTH_HOST) {

@@ -40,6 +40,11 @@ namespace bzh {
 //   ntt_run_padded above 2^11 and poly_batch_invert take A, the prefix scans and poly_kate_division take C.
 //   WS_STAGE, WS_IPA and WS_IPA_OUT live for a whole C ABI call.  No internal driver (msm_run*, ntt_run*, poly_*, lookup_permute)
 //   takes them, so their holder may call all of those, but not another holder of the same slot.
+//   The device synthesis (synth_device_enqueue) holds WS_STAGE -- layout, packed inputs, flags -- only while its three kernels
+//   run.  A caller that goes on to other holders of the slot in the same call (the game-input prover: the prover's leaves stage in
+//   WS_STAGE themselves) must therefore have the synthesis write what outlives those kernels, the status words and the
+//   commitments, into memory of its own (the key's arena), and must enqueue whatever still reads the packed inputs
+//   (k_pg_instances) before the first such holder.
 enum WsSlot {
     WS_SCRATCH_A = 0,   // MSM digits | multi-pass NTT scratch | batch inversion's prefix products | generators of a one-off table build
     WS_SCRATCH_B = 1,   // MSM buckets | bzh_lookup_permute's working set | Pedersen operands | bzh_bases_read's canonical copy
@@ -415,6 +420,14 @@ int evaluations_device_srcs(bzh_ctx* ctx, int curve, size_t batch, unsigned k, c
 // prove_device_status: d_slot[b] = {the four leaves' bytes of proof b folded into bits 0 .. 3, proof_len} (two words per proof).
 int prove_device_blinds(bzh_ctx* ctx, int field, const void* d_srcs, size_t nsrc, size_t nown, size_t batch, uint32_t* d_out);
 int prove_device_status(bzh_ctx* ctx, const uint8_t* d_leaf, size_t leaf_stride, size_t batch, uint32_t proof_len, uint32_t* d_slot);
+// prove_game.hip: the two lane kernels of bzh_prove_shots_device / bzh_prove_boards_device (the call itself reads the key:
+// csrc/prove_game.hpp); device pointers, 16-byte aligned, enqueue only.  prove_game_instances: from d_cm[b][16] (the commitment's
+// canonical x || y) and, for Shot, the low 128 bits of words 8 .. 11 and 12 .. 15 of d_in[b][in_words], the public inputs of proof
+// b as d_mont[b][rows] (Montgomery) and d_canon[b][rows] (canonical), rows = 4 (Shot) or 2 (Board).  prove_game_status: bits
+// 4 .. 6 of d_slot[b][0] |= d_syn_status[b] << 4 (d_slot: prove_device_status's two words per proof).
+int prove_game_instances(bzh_ctx* ctx, bool shot, const uint32_t* d_cm, const uint64_t* d_in, size_t in_words, size_t batch, uint32_t* d_mont,
+                         uint32_t* d_canon);
+int prove_game_status(bzh_ctx* ctx, const uint32_t* d_syn_status, size_t batch, uint32_t* d_slot);
 // vanishing.hip: the two kernels of bzh_vanishing_batch_device (the call itself reads the key: csrc/vanishing_device.hpp); device
 // pointers, 16-byte aligned unless said otherwise; enqueue only.
 // vanishing_consts: d_table[b][i] = value_i * challenge_b^exponent_i over the nconsts descriptors at d_descs (bzh_vanishing_const);

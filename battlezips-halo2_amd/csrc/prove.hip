@@ -46,6 +46,7 @@
 #include "products_scalars.hpp"    // (the column table as k_gp_factors reads it)
 #include "commitments_scalars.hpp" // (the constant descriptors as k_cm_consts reads them)
 #include "prove_device_scalars.hpp" // (the blind sources as k_pd_blinds reads them)
+#include "prove_game_scalars.hpp"   // (the status shift of k_pg_status; with it synthesize_device.hpp: the layout, the launch)
 #include "vm2_isa.hpp"
 
 // the table of quotient kernels generated at build time (quotient_builtin.hip); absent (null) in the generator's own link
@@ -64,6 +65,7 @@ extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __at
 #include "products_device.hpp"    // phase 4 likewise
 #include "commitments_device.hpp" // phases 1 to 3 likewise
 #include "prove_device.hpp"       // the five leaves as one call: the device-resident batch prover
+#include "prove_game.hpp"         // the device synthesis in front of it: game inputs in, proofs out
 #include "verifier.hpp"
 
 // pk.get_vk(): the commitments to the fixed and permutation polynomials (blind 1), computed once per key
@@ -805,6 +807,20 @@ int bzh_prove_batch_device_seeded(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const 
                                   size_t* proof_lens, uint8_t* status) {
     return prove_batch_device_entry(ctx, pk, batch, advice, form, mem, instances, instance_rows, seeds, 0, proofs, proof_stride, proof_lens,
                                     status);
+}
+
+int bzh_prove_shots_device(bzh_ctx* ctx, bzh_pk* pk, const bzh_circuit* circuit, size_t batch, const uint64_t* boards, const uint64_t* trapdoors,
+                           const uint64_t* shots, const uint64_t* hits, const uint8_t* seeds, uint64_t* instances, uint8_t* proofs,
+                           size_t proof_stride, size_t* proof_lens, uint8_t* status) {
+    return bzh::prove_game_entry("bzh_prove_shots_device", BZH_CIRCUIT_SHOT, ctx, pk, circuit, batch, boards, trapdoors, shots, hits, seeds, instances,
+                                 proofs, proof_stride, proof_lens, status);
+}
+
+int bzh_prove_boards_device(bzh_ctx* ctx, bzh_pk* pk, const bzh_circuit* circuit, size_t batch, const uint64_t* ship_commitments,
+                            const uint64_t* boards, const uint64_t* trapdoors, const uint8_t* seeds, uint64_t* instances, uint8_t* proofs,
+                            size_t proof_stride, size_t* proof_lens, uint8_t* status) {
+    return bzh::prove_game_entry("bzh_prove_boards_device", BZH_CIRCUIT_BOARD, ctx, pk, circuit, batch, ship_commitments, boards, trapdoors, nullptr,
+                                 seeds, instances, proofs, proof_stride, proof_lens, status);
 }
 
 int bzh_rng_expand(const uint8_t* seed, uint64_t first_draw, size_t draws, uint8_t* out) {

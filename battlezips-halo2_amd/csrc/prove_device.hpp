@@ -104,12 +104,25 @@ static int prove_device_plan_of(bzh_pk* pk, const PdPlan** out) {
     return pk->pd_plan.rc;
 }
 
+// The operands of the game-input calls (csrc/prove_game.hpp), which take them where they lie: the advice tensor is allocated from
+// the arena like a host call's and FILLED by the synthesis kernels (the zero fill and the three k_syn_* launches go on the stream
+// before the commitments leaf) instead of an upload; the instance buffer is the Montgomery [b][ni][inst_rows] that k_pg_instances
+// writes on the device, ni = 1; the synthesis status words are a fifth status source, folded into bits 4 .. 6 by k_pg_status
+// after k_pd_status.  The status words and the commitments lie in the arena, not in WS_STAGE (ctx.hpp, the slots' holders).
+struct PdGame {
+    const char* name;                 // the entry point, for bzh_last_error
+    const SynLayout* layout;          // with `inputs`: what synth_pack_inputs made
+    const uint64_t* inputs;           // host, batch x layout->in_words
+    uint64_t* instances_out;          // host, batch x inst_rows canonical rows, or null
+};
+
 // the call, for a caller that holds ctx->mu and has made every argument check.  rng_stride == 0: `rng` holds batch x 32-byte
-// seeds in host memory.  status: null, or one byte per proof (host)
+// seeds in host memory.  status: null, or one byte per proof (host).  game != null: `advice` and `instances` are not read, mem is
+// BZH_MEM_DEVICE, inst_rows the circuit's public inputs per proof
 template <class C>
 static int prove_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t* advice, int form, int mem, const uint64_t* instances,
                           size_t inst_rows, const uint8_t* rng, size_t rng_stride, const PdPlan& P, uint8_t* proofs, size_t proof_stride,
-                          size_t* proof_lens, uint8_t* status) {
+                          size_t* proof_lens, uint8_t* status, const PdGame* game = nullptr) {
     using SF = typename CurveInfo<C>::SF;
     Arena& arena = pk->rt.arena_for(ctx->serial, ctx->device);
     // (the merged-block rule and its one wait: vanishing_device_t)
@@ -163,8 +176,11 @@ static int prove_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t* ad
         return p;
     };
     const bool host = mem == BZH_MEM_HOST;
-    uint32_t* d_adv = host ? elems(B * na * n) : (uint32_t*)advice;
-    uint32_t* d_inst = instances ? elems(B * ni * inst_rows) : nullptr;
+    uint32_t* d_adv = (host || game) ? elems(B * na * n) : (uint32_t*)advice;
+    uint32_t* d_inst = (instances || game) ? elems(B * ni * inst_rows) : nullptr;
+    uint32_t* g_canon = game ? elems(B * inst_rows) : nullptr;                     // the canonical rows, read back with the proofs
+    uint32_t* g_cm = game ? elems(2 * B) : nullptr;                                // k_syn_ecc_tail's commitments
+    uint32_t* g_status = game ? (uint32_t*)arena.alloc(B * 4) : nullptr;           // ... and its status words
     uint32_t *o_adv = elems(B * na * n), *o_inst = elems(B * ni * n), *o_lc = elems(B * nl * 2 * n), *o_lp = elems(B * nl * 2 * n),
              *o_advp = elems(B * na * n), *o_instp = elems(B * ni * n), *o_lkp = elems(B * nl * 2 * n), *o_ab = elems(B * na),
              *o_lb = elems(B * nl * 2), *d_theta = elems(B), *d_beta = elems(B), *d_gamma = elems(B);
@@ -188,7 +204,7 @@ static int prove_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t* ad
     uint8_t* d_rng = rng_on_device ? (uint8_t*)rng : (uint8_t*)arena.alloc(B * total * 64);
     const size_t d_stride = rng_on_device ? rng_stride : total * 64;
     uint32_t* d_keys = rng_stride ? nullptr : (uint32_t*)arena.alloc(B * 32);
-    if (oom || !d_leaf || !d_slot || !d_bsrc || !d_rng || (!rng_stride && !d_keys)) return BZH_E_OOM;
+    if (oom || !d_leaf || !d_slot || !d_bsrc || !d_rng || (!rng_stride && !d_keys) || (game && !g_status)) return BZH_E_OOM;
 
     // what depends on the key and the workspace pointers alone, before the first launch: the digest, the blinds of the key's own
     // polynomials, the blind table's sources.  (Each leaf body uploads its own programs, registries and descriptors as its first
@@ -228,6 +244,15 @@ static int prove_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t* ad
     auto u64 = [](uint32_t* p) { return (uint64_t*)p; };
     const int MO = BZH_FORM_MONTGOMERY, DEV = BZH_MEM_DEVICE;
     mark("setup");
+    if (game) {
+        SynRun run;
+        run.layout = game->layout, run.batch = B, run.inputs = game->inputs, run.table = synth_table_host(), run.d_advice = d_adv;
+        const uint64_t* d_in = nullptr;
+        BZH_TRY(synth_device_enqueue(ctx, run, g_status, g_cm, &d_in));
+        // (reads the packed inputs in WS_STAGE: before the first leaf, which may take that slot)
+        BZH_TRY(prove_game_instances(ctx, game->layout->kind == BZH_CIRCUIT_SHOT, g_cm, d_in, game->layout->in_words, B, d_inst, g_canon));
+        mark("synthesis");
+    }
 
     BZH_TRY(tb_absorb_locked(tb, 2, d_vk, 1, 0, BZH_FORM_CANONICAL, nullptr));
     {
@@ -282,23 +307,34 @@ static int prove_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t* ad
     const TbInfo ti = tb_info(tb);
     if (ti.proof_len > proof_stride) return BZH_E_RANGE;
     BZH_TRY(prove_device_status(ctx, d_leaf, st_pitch, B, (uint32_t)ti.proof_len, d_slot));
+    if (game) BZH_TRY(prove_game_status(ctx, g_status, B, d_slot));
     size_t pstride = 0;
     const uint8_t* d_proofs = tb_proofs_device(tb, &pstride);
     std::vector<uint8_t> rows(B * pstride);
     std::vector<uint32_t> slot(2 * B);
     BZH_TRY(d2h_async(ctx, rows.data(), d_proofs, rows.size()));
     BZH_TRY(d2h_async(ctx, slot.data(), d_slot, B * 8));
+    std::vector<uint64_t> canon(game && game->instances_out ? B * inst_rows * 4 : 0);
+    BZH_TRY(d2h_async(ctx, canon.data(), g_canon, canon.size() * 8));
     BZH_TRY(d2h_finish(ctx));
     mark("proofs");
     if (!status)
         for (size_t b = 0; b < B; b++)
             if (slot[2 * b]) {
-                char text[160];
-                snprintf(text, sizeof(text), "bzh_prove_batch_device: proof %zu is flagged (status 0x%x: bit 0 lookup, 1 grand product, 2 degree, 3 opening)",
-                         b, (unsigned)slot[2 * b]);
+                char text[320];
+                if (!game)
+                    snprintf(text, sizeof(text), "bzh_prove_batch_device: proof %zu is flagged (status 0x%x: bit 0 lookup, 1 grand product, 2 degree, 3 opening)",
+                             b, (unsigned)slot[2 * b]);
+                else if (slot[2 * b] >> PG_STATUS_SHIFT)   // the text bzh_synthesize_* gives for the word
+                    snprintf(text, sizeof(text), "%s: proof %zu is flagged (status 0x%x: bits 4 to 6 synthesis): %s", game->name, b,
+                             (unsigned)slot[2 * b], syn_status_text(slot[2 * b] >> PG_STATUS_SHIFT));
+                else
+                    snprintf(text, sizeof(text), "%s: proof %zu is flagged (status 0x%x: bit 0 lookup, 1 grand product, 2 degree, 3 opening)", game->name,
+                             b, (unsigned)slot[2 * b]);
                 ctx->last_error = text;
                 return BZH_E_RANGE;
             }
+    if (!canon.empty()) memcpy(game->instances_out, canon.data(), canon.size() * 8);
     for (size_t b = 0; b < B; b++) {
         memcpy(proofs + b * proof_stride, &rows[b * pstride], slot[2 * b + 1]);
         proof_lens[b] = slot[2 * b + 1];

@@ -7,7 +7,8 @@
 //   k_syn_ecc_tail   one lane per proof: the three complete additions, Shot's native commitment cells, the commitment
 // The tensor is zeroed by a memset on the same stream first; a region's constants 0 and the rows >= rows_used are that fill.
 // One staged upload (layout + inputs) and one read-back (status words + commitments) per call; the read-back is the call's only
-// stream synchronisation.
+// stream synchronisation.  synth_device_enqueue is the same call without that read-back, for a caller that goes on working on the
+// device (the game-input prover, csrc/prove_game.hpp): the status words and the commitments go to device pointers of its own.
 #include <cstdio>
 
 #include "ctx.hpp"
@@ -80,7 +81,20 @@ static size_t up16(size_t v) { return (v + 255) & ~(size_t)255; }
 
 namespace bzh {
 
-int synth_device_run(bzh_ctx* ctx, const SynRun& run) {
+// WS_STAGE while the three kernels run: layout | inputs | flags (2 per proof), and for synth_device_run status (1 per proof) |
+// commitments (16 words per proof) after them
+struct SynStage {
+    size_t o_in, in_bytes, o_flags, o_status, status_bytes, o_inst;
+};
+static SynStage synth_stage(const SynLayout& L, size_t batch) {
+    SynStage s;
+    s.o_in = up16(sizeof(SynLayout)), s.in_bytes = batch * L.in_words * 8, s.o_flags = s.o_in + up16(s.in_bytes);
+    s.o_status = s.o_flags + up16(batch * 8), s.status_bytes = up16(batch * 4), s.o_inst = s.o_status + s.status_bytes;
+    return s;
+}
+
+int synth_device_enqueue(bzh_ctx* ctx, const SynRun& run, uint32_t* d_status, uint32_t* d_commitments, const uint64_t** d_inputs,
+                         hipEvent_t* ev) {
     const SynLayout& L = *run.layout;
     const size_t batch = run.batch;
     if (!ctx->syn_tbl) {
@@ -94,31 +108,23 @@ int synth_device_run(bzh_ctx* ctx, const SynRun& run) {
         }
         ctx->syn_tbl = tbl;
     }
-    // WS_STAGE: layout | inputs | flags (2 per proof) | status (1 per proof) | commitments (16 words per proof); the synthesis
-    // kernels below are all that runs while it is held
-    const size_t o_in = up16(sizeof(SynLayout)), in_bytes = batch * L.in_words * 8, o_flags = o_in + up16(in_bytes);
-    const size_t o_status = o_flags + up16(batch * 8), status_bytes = up16(batch * 4), o_inst = o_status + status_bytes;
-    const size_t rb_bytes = status_bytes + batch * 64, total = o_inst + batch * 64;
+    // the synthesis kernels below (and what the caller enqueues on *d_inputs right after them) are all that runs while the slot is
+    // held.  The slot keeps synth_device_run's size whoever calls, so that the two forms never grow it in turns
+    const SynStage S = synth_stage(L, batch);
     void* ws = nullptr;
-    BZH_TRY(ws_ensure(ctx, WS_STAGE, total, &ws));
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, S.o_inst + batch * 64, &ws));
     char* d = (char*)ws;
     char* slot = nullptr;
-    BZH_TRY(h2d_stage(ctx, o_flags, &slot));
-    memset(slot, 0, o_flags);
+    BZH_TRY(h2d_stage(ctx, S.o_flags, &slot));
+    memset(slot, 0, S.o_flags);
     memcpy(slot, &L, sizeof(SynLayout));
-    memcpy(slot + o_in, run.inputs, in_bytes);
-    BZH_TRY(h2d_commit(ctx, d, slot, o_flags));
+    memcpy(slot + S.o_in, run.inputs, S.in_bytes);
+    BZH_TRY(h2d_commit(ctx, d, slot, S.o_flags));
     const SynLayout* d_L = (const SynLayout*)d;
-    const uint64_t* d_in = (const uint64_t*)(d + o_in);
-    uint32_t *d_flags = (uint32_t*)(d + o_flags), *d_status = (uint32_t*)(d + o_status), *d_inst = (uint32_t*)(d + o_inst);
-    // BZH_PROVE_TRACE=1: the three kernels' times by events, on stderr (tools/ubench_synthesize.py reads the line)
-    const bool trace = getenv("BZH_PROVE_TRACE") != nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (trace) {
-        for (auto& e : ev) BZH_HIP_TRY(ctx, hipEventCreate(&e));
-    }
+    const uint64_t* d_in = (const uint64_t*)(d + S.o_in);
+    uint32_t* d_flags = (uint32_t*)(d + S.o_flags);
     auto mark = [&](int i) {
-        if (trace) (void)hipEventRecord(ev[i], ctx->stream);
+        if (ev) (void)hipEventRecord(ev[i], ctx->stream);
     };
     mark(0);
     BZH_HIP_TRY(ctx, hipMemsetAsync(run.d_advice, 0, batch * L.num_advice * (size_t)L.n * 32, ctx->stream));
@@ -131,10 +137,29 @@ int synth_device_run(bzh_ctx* ctx, const SynRun& run) {
                            d_flags);
         mark(3);
         hipLaunchKernelGGL(k_syn_ecc_tail, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, ctx->stream, d_L, d_in, batch, run.d_advice,
-                           (const uint32_t*)d_flags, d_status, d_inst);
+                           (const uint32_t*)d_flags, d_status, d_commitments);
         mark(4);
     }
     BZH_HIP_TRY(ctx, hipGetLastError());
+    if (d_inputs) *d_inputs = d_in;
+    return BZH_OK;
+}
+
+int synth_device_run(bzh_ctx* ctx, const SynRun& run) {
+    const size_t batch = run.batch;
+    const SynStage S = synth_stage(*run.layout, batch);
+    const size_t rb_bytes = S.status_bytes + batch * 64;
+    void* ws = nullptr;
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, S.o_inst + batch * 64, &ws));   // (the enqueue asks for the same bytes: the slot does not move)
+    char* d = (char*)ws;
+    uint32_t *d_status = (uint32_t*)(d + S.o_status), *d_inst = (uint32_t*)(d + S.o_inst);
+    // BZH_PROVE_TRACE=1: the three kernels' times by events, on stderr (tools/ubench_synthesize.py reads the line)
+    const bool trace = getenv("BZH_PROVE_TRACE") != nullptr;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (trace) {
+        for (auto& e : ev) BZH_HIP_TRY(ctx, hipEventCreate(&e));
+    }
+    BZH_TRY(synth_device_enqueue(ctx, run, d_status, d_inst, nullptr, trace ? ev : nullptr));
     std::vector<uint32_t> rb(rb_bytes / 4);
     BZH_TRY(d2h_async(ctx, rb.data(), d_status, rb_bytes));
     BZH_TRY(d2h_finish(ctx));
@@ -146,7 +171,7 @@ int synth_device_run(bzh_ctx* ctx, const SynRun& run) {
         for (auto& e : ev) (void)hipEventDestroy(e);
     }
     memcpy(run.status, rb.data(), batch * 4);
-    if (run.commitments) memcpy(run.commitments, rb.data() + status_bytes / 4, batch * 64);
+    if (run.commitments) memcpy(run.commitments, rb.data() + S.status_bytes / 4, batch * 64);
     return BZH_OK;
 }
 

@@ -12,6 +12,9 @@
 //   syn_incomplete_exceptional   add_incomplete_assign_region's refusal, on the normalised operands
 //   syn_ecc_tail            one lane per proof: the three complete additions, Shot's native commitment cells, the instance words
 #pragma once
+#include <string>
+#include <vector>
+
 #include "curve.cuh"
 #include "normalize.hpp"
 
@@ -392,9 +395,34 @@ struct SynRun {
     uint64_t* commitments = nullptr;       // batch x 8 canonical words (x || y), or null
     uint32_t* status = nullptr;            // batch words
 };
+// enqueue, then read back: one staged upload, the zero fill, the three kernels, one read-back (the call's only stream wait)
 int synth_device_run(bzh_ctx* ctx, const SynRun& run);
+// the enqueue-only form: the same upload, fill and kernels, the status words (batch) and the commitments (batch x 16 canonical
+// words, x || y) to DEVICE pointers of the caller's (16-byte aligned), no read-back and no stream wait.  run.status and
+// run.commitments are not read.  *d_inputs: where the packed inputs lie in WS_STAGE -- valid for kernels the caller enqueues before
+// anything else takes that slot.  ev: null, or five events recorded around the fill and the kernels (synth_device_run's trace).
+int synth_device_enqueue(bzh_ctx* ctx, const SynRun& run, uint32_t* d_status, uint32_t* d_commitments, const uint64_t** d_inputs,
+                         hipEvent_t* ev = nullptr);
+// the host path's text for a status word (the first of its throw sites that the word names)
+inline const char* syn_status_text(uint32_t st) {
+    return (st & SYN_ST_MESSAGE)     ? "pedersen_commit: message repr is not a canonical scalar"
+           : (st & SYN_ST_WINDOW_X0) ? "fixed-base mul: window point with x = 0"
+                                     : "incomplete addition: exceptional case";
+}
 // csrc/circuits.hip: the layout and the table of a circuit, for the launch and for the host twin's test program
 int synth_layout(const bzh_circuit* c, SynLayout* out);
 const uint32_t* synth_table_host();
+// csrc/circuits.hip: what a caller outside that file may know of a circuit object
+struct SynShape {
+    int kind;                                   // bzh_circuit_kind
+    size_t n, num_advice, num_instance, inst_rows;   // rows, advice columns, instance columns, public inputs per proof
+};
+int synth_shape(const bzh_circuit* c, SynShape* out);
+// csrc/circuits.hip: step one of a device synthesis, "check and pack the inputs" (no device use).  a .. d: the input arrays of
+// bzh_synthesize_shot (boards, trapdoors, shots, hits) or bzh_synthesize_board (ship_commitments, boards, trapdoors, null).
+// Fills the layout and `in` (batch x layout->in_words words) for SynRun.  BZH_E_RANGE with the host path's text in *err (and in
+// bzh_circuit_last_error) for what the host path refuses on the inputs alone: a non-canonical trapdoor, H and V sharing a bit.
+int synth_pack_inputs(const bzh_circuit* c, size_t batch, const uint64_t* a, const uint64_t* b, const uint64_t* c_in, const uint64_t* d,
+                      SynLayout* layout, std::vector<uint64_t>* in, std::string* err);
 
 }  // namespace bzh

@@ -969,6 +969,38 @@ int bzh_synthesize_shot_with(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, c
                              const uint64_t* hits, uint64_t* advice, int form, int mem, uint64_t* instances, unsigned threads, int where);
 int bzh_synthesize_board_with(bzh_ctx* ctx, const bzh_circuit* c, size_t batch, const uint64_t* ship_commitments, const uint64_t* boards,
                               const uint64_t* trapdoors, uint64_t* advice, int form, int mem, uint64_t* instances, unsigned threads, int where);
+/* THE GAME-INPUT PROVER: the reference's top-level operation -- game inputs in, {commitment, proof} out (src/wasm/circuit_wasm.rs,
+ * benches/{shot,board}.rs) -- for a batch, as ONE device-resident call: bzh_synthesize_*_with(BZH_SYNTH_DEVICE) and
+ * bzh_prove_batch_device_seeded joined on the device.  The game inputs are host pointers with the layout of bzh_synthesize_shot /
+ * bzh_synthesize_board; `seeds` is 32 bytes per proof, with the ChaCha20 expansion and the SECURITY note of
+ * bzh_prove_batch_device_seeded; `instances` (host, may be NULL) receives batch x {4, 2} canonical rows, exactly what
+ * bzh_synthesize_* writes; proofs, proof_stride, proof_lens and status are bzh_prove_batch_device's.
+ * Proofs, lengths and instances are byte-identical to bzh_synthesize_*_with(BZH_SYNTH_DEVICE) followed by
+ * bzh_prove_batch_device_seeded on the same inputs and seeds, and so to host synthesis followed by bzh_prove_batch_seeded.
+ * status keeps bits 0 .. 3 of bzh_prove_batch_device and adds the synthesis status at bits 4 .. 6: bit 4 "incomplete addition:
+ * exceptional case", bit 5 "fixed-base mul: window point with x = 0", bit 6 "pedersen_commit: message repr is not a canonical
+ * scalar" -- the inputs bzh_synthesize_* refuses after running.  A proof flagged by the synthesis still gets all its bytes and
+ * disturbs no other proof.  With status == NULL any flagged proof makes the call return BZH_E_RANGE and write nothing;
+ * bzh_last_error names the first flagged proof and its bits, and for a synthesis bit ends with the text bzh_synthesize_* gives.
+ * Inside: the inputs are checked and packed on the host and go up once (128 bytes a Shot proof, 384 a Board proof, plus the seed);
+ * the advice tensor lives in the key's workspace and is filled by the three synthesis kernels; one lane per proof makes the
+ * instance rows from the commitment where the synthesis left it (k_pg_instances) and folds the synthesis status (k_pg_status);
+ * nothing of size n is uploaded, and neither the status words nor the commitment come to the host between the two halves.  The
+ * call makes the one stream wait of bzh_prove_batch_device, for one read-back of the proofs, the status and length slots and the
+ * canonical instances (and the one-time wait of the call that merges the workspace's blocks).
+ * Refused before anything is launched, with the key and the ctx usable:
+ * BZH_E_ARG: a NULL ctx, pk, circuit, input array, seeds, proofs or proof_lens; batch == 0 or above 65536; a circuit of the other
+ * kind; a key on another device than ctx; a circuit that does not match the key -- compared are the curve (Vesta), n, the number of
+ * advice columns, the number of instance columns (one) and that the circuit's instance rows fit the key's usable rows.
+ * BZH_E_RANGE: a batch above bzh_prove_device_plan's limit; what bzh_prove_batch_device answers with BZH_E_RANGE (no VM v2
+ * quotient program, a proof_stride below the proof bytes); the inputs bzh_synthesize_* refuses on sight, with its text in
+ * bzh_last_error and bzh_circuit_last_error (a non-canonical trapdoor; H and V commitments sharing a bit). */
+int bzh_prove_shots_device(bzh_ctx* ctx, bzh_pk* pk, const bzh_circuit* circuit, size_t batch, const uint64_t* boards, const uint64_t* trapdoors,
+                           const uint64_t* shots, const uint64_t* hits, const uint8_t* seeds, uint64_t* instances, uint8_t* proofs,
+                           size_t proof_stride, size_t* proof_lens, uint8_t* status);
+int bzh_prove_boards_device(bzh_ctx* ctx, bzh_pk* pk, const bzh_circuit* circuit, size_t batch, const uint64_t* ship_commitments,
+                            const uint64_t* boards, const uint64_t* trapdoors, const uint8_t* seeds, uint64_t* instances, uint8_t* proofs,
+                            size_t proof_stride, size_t* proof_lens, uint8_t* status);
 int bzh_synthesize_bitify_test(const bzh_circuit* c, const uint64_t* value, const uint64_t* binary, uint64_t* advice);
 int bzh_board_witness(const int8_t* ships, const int32_t* options, uint64_t* ship_commitments, uint64_t* state);
 int bzh_shot_serialize(const uint8_t* xs, const uint8_t* ys, size_t count, uint64_t* out);
