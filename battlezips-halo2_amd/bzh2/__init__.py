@@ -1183,6 +1183,8 @@ EXPORTS += ["bzh_circuit_create", "bzh_circuit_free", "bzh_circuit_last_error", 
 EXPORTS += ["bzh_synthesize_shot_with", "bzh_synthesize_board_with"]
 # game inputs in, proofs out, in one device-resident call (NativeProvingKey.prove_shots_device / prove_boards_device)
 EXPORTS += ["bzh_prove_shots_device", "bzh_prove_boards_device"]
+# records in, accept / reject out, in one device-resident call (NativeVerifyingKey.verify_records)
+EXPORTS += ["bzh_verify_records_device"]
 E_VERIFY = -6
 
 

@@ -53,6 +53,8 @@ def _bind():
                                       ctypes.POINTER(ctypes.c_size_t), _VP, ctypes.POINTER(ctypes.c_int)]
     L.bzh_verify_batch_vk_with.argtypes = [_VP, _VP, _VP, _VP, ctypes.c_int, ctypes.c_size_t, _VP, ctypes.c_size_t, _VP, ctypes.c_size_t,
                                            ctypes.POINTER(ctypes.c_size_t), _VP, ctypes.POINTER(ctypes.c_int)]
+    L.bzh_verify_records_device.argtypes = [_VP, _VP, _VP, _VP, ctypes.c_size_t, ctypes.c_size_t, _VP, ctypes.c_size_t, _VP,
+                                            ctypes.POINTER(ctypes.c_int), _VP]
     L.bzh_pk_verify_pass_select.argtypes = [_VP, ctypes.c_int]
     L.bzh_pk_verify_pass_selected.argtypes = [_VP, ctypes.POINTER(ctypes.c_int)]
     L._bzh_native_bound = True
@@ -558,6 +560,30 @@ class NativeVerifyingKey:
                                             _VP(buf.ctypes.data), stride, lens, _VP(g0.ctypes.data), res)
         ctx._check(rc, "bzh_verify_batch_vk")
         return [bool(v) for v in res]
+
+    def verify_records(self, ctx: Context, params, records, n_inputs: int, g0_u_w=None, want_status: bool = True, record_stride: int | None = None):
+        """verify_board / verify_shot for a batch of binary records in one device-resident call (bzh_verify_records_device).
+        records: equal-length byte strings in the layout of bzh2.wire.Record.encode (or one contiguous uint8 array of
+        len(records) rows); n_inputs: 4 for Shot, 2 for Board; params: a bzh2.params.Params -- its g_lagrange table commits the
+        inputs.  g0_u_w (3 x 8 canonical limbs): checked against the SRS on the device when given; None: not checked, G_0 U W are
+        the SRS table's.  Returns (results, status): a list of bools, and one byte per record -- bit 0: refused before
+        verification (corrupt header, another n_inputs, another proof length, a non-canonical input) -- or None with
+        want_status=False."""
+        L = _bind()
+        bases = getattr(params, "bases", params)
+        lag = getattr(params, "bases_lagrange", None)
+        B = len(records)
+        buf = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in records), dtype=np.uint8)) if B else np.zeros(1, dtype=np.uint8)
+        stride = record_stride if record_stride is not None else (len(records[0]) if B else 0)
+        assert all(len(r) == stride for r in records) or record_stride is not None
+        g0 = np.ascontiguousarray(g0_u_w, dtype=np.uint64) if g0_u_w is not None else None
+        res = (ctypes.c_int * max(B, 1))()
+        status = np.zeros(max(B, 1), dtype=np.uint8)
+        rc = L.bzh_verify_records_device(ctx.handle, self.handle, bases.handle, lag.handle if lag is not None else None, B, n_inputs,
+                                         _VP(buf.ctypes.data), stride, _VP(g0.ctypes.data) if g0 is not None else None, res,
+                                         _VP(status.ctypes.data) if want_status else None)
+        ctx._check(rc, "bzh_verify_records_device")
+        return [bool(res[b]) for b in range(B)], (status[:B].copy() if want_status else None)
 
     def close(self):
         """bzh_vk_free.  Refused (BzhError, the key stays open) while a verify_batch on the key has started on any ctx and not

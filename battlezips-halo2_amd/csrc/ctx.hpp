@@ -477,6 +477,11 @@ int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t n
 // (taken to Montgomery form in place), d_scal canonical, d_cu batch x (k + 1) Montgomery; 16-byte aligned
 int ipa_check_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
                            const uint32_t* d_cu, int* ok);
+// the same launches without the read-back and the host comparison: *d_sums = the batch right sides' Jacobian points, then the batch
+// left sides', Montgomery, 24 words each, in WS_IPA -- valid until the next holder of that slot.  Enqueues only (msm_run's own waits
+// aside).
+int ipa_check_sums_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
+                          const uint32_t* d_cu, const uint32_t** d_sums);
 bool point_decompress(int curve, const uint8_t* in, uint64_t* xy_canonical);
 // sqrt_decompress.hip (device pointers, 16-byte aligned; elements and points in `form`).  batch_sqrt_run: in place, d_status[i] = 1
 // for a square (root written), 0 otherwise (element untouched).  decompress_run: n x 32 bytes -> n affine points x || y and one
@@ -535,5 +540,25 @@ struct VerifyPassArgs {
 int vp_gather_points(bzh_ctx* ctx, const VerifyPassArgs& a, uint32_t* d_out32);
 int vp_scalars_run(bzh_ctx* ctx, int curve, const VerifyPassArgs& a);
 int vp_assemble_run(bzh_ctx* ctx, const VerifyPassArgs& a);
+// verify_records.hip: the four lane kernels of bzh_verify_records_device (the call itself reads the key: csrc/verifier.hpp); device
+// pointers, 16-byte aligned unless said otherwise; enqueue only.  Lane bodies and what each argument holds: verify_records.hpp.
+struct VerifyRecordsArgs {
+    size_t batch = 0, rstride = 0, pstride = 0;   // records rstride bytes apart, proof rows pstride bytes apart: multiples of 16
+    uint32_t n_inputs = 0, proof_len = 0;         // what a record must say; 144 + proof_len <= rstride, proof_len <= pstride
+    const uint8_t* d_records = nullptr;
+    uint32_t* d_inst = nullptr;                   // batch x n_inputs elements, Montgomery
+    uint8_t* d_rows = nullptr;                    // batch x pstride bytes
+    uint8_t* d_pre = nullptr;                     // batch bytes, any alignment
+};
+int verify_records_parse(bzh_ctx* ctx, int curve, const VerifyRecordsArgs& a);
+// d_table: row 0 of the SRS window table (n_srs affine Montgomery points); d_given: 3 canonical points or null; d_out_xy: G_0 U W
+// canonical; d_mismatch: 3 bytes, any alignment
+int verify_records_srs(bzh_ctx* ctx, int curve, const uint32_t* d_table, size_t n_srs, const uint32_t* d_given, uint32_t* d_out_xy,
+                       uint8_t* d_mismatch);
+// d_jac: batch Jacobian sums, Montgomery in and canonical out; d_w_xy: W, affine Montgomery
+int verify_records_add_w(bzh_ctx* ctx, int curve, uint32_t* d_jac, const uint32_t* d_w_xy, size_t batch);
+// d_sums: ipa_check_sums_device's; d_out: results at [b], status at [pitch + b], any alignment
+int verify_records_result(bzh_ctx* ctx, int curve, const uint32_t* d_sums, size_t batch, const uint8_t* d_pre, const uint8_t* d_reject,
+                          uint8_t* d_out, size_t pitch);
 
 }  // namespace bzh

@@ -836,13 +836,12 @@ __global__ void __launch_bounds__(kSmallMsmThreads) k_ipa_small_msm(const uint32
     }
 }
 
-// The launches and the comparison, operands in device memory: d_s batch x (n + 2) scratch, d_cu Montgomery, d_pts canonical (taken
-// to Montgomery form in place), d_scal canonical, d_out 2 x batch Jacobian sums.
+// The launches, operands in device memory: d_s batch x (n + 2) scratch, d_cu Montgomery, d_pts canonical (taken to Montgomery form
+// in place), d_scal canonical, d_out 2 x batch Jacobian sums (Montgomery): the right sides, then the left sides.
 template <class C>
-static int ipa_check_run_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_s, const uint32_t* d_cu, uint32_t* d_pts,
-                           const uint32_t* d_scal, uint32_t* d_out, int* ok) {
+static int ipa_check_enqueue_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_s, const uint32_t* d_cu, uint32_t* d_pts,
+                               const uint32_t* d_scal, uint32_t* d_out) {
     using SF = typename CurveInfo<C>::SF;
-    using PB = typename C::Base;
     const size_t n = bases->n - 2, B = batch;
     unsigned k = 0;
     while (((size_t)1 << k) < n) k++;
@@ -855,6 +854,15 @@ static int ipa_check_run_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, s
     BZH_TRY(bases_to_montgomery(ctx, C::id, d_pts, B * nl));
     hipLaunchKernelGGL((k_ipa_small_msm<C>), dim3((unsigned)B), dim3(kSmallMsmThreads), 0, st, d_pts, d_scal, nl, d_out + B * 24);
     BZH_HIP_TRY(ctx, hipGetLastError());
+    return BZH_OK;
+}
+// ... and the comparison on the host: the sums come back and are normalised there
+template <class C>
+static int ipa_check_run_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_s, const uint32_t* d_cu, uint32_t* d_pts,
+                           const uint32_t* d_scal, uint32_t* d_out, int* ok) {
+    using PB = typename C::Base;
+    const size_t B = batch;
+    BZH_TRY(ipa_check_enqueue_t<C>(ctx, bases, batch, nl, d_s, d_cu, d_pts, d_scal, d_out));
     std::vector<uint64_t> jac(2 * B * 12), lhs(B * 8), rhs(B * 8);
     BZH_TRY(d2h_async(ctx, jac.data(), d_out, 2 * B * 96));
     BZH_TRY(d2h_finish(ctx));
@@ -909,6 +917,20 @@ int ipa_check_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, s
     uint32_t* d_s = (uint32_t*)arena;
     uint32_t* d_out = d_s + B * (n + 2) * 8;
     return with_curve(bases->curve, [&](auto c) { return ipa_check_run_t<decltype(c)>(ctx, bases, B, nl, d_s, d_cu, d_pts, d_scal, d_out, ok); });
+}
+
+int ipa_check_sums_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
+                          const uint32_t* d_cu, const uint32_t** d_sums) {
+    const size_t n = bases->n - 2, B = batch;
+    unsigned k = 0;
+    while (((size_t)1 << k) < n) k++;
+    if (((size_t)1 << k) != n || !B || !nl || !d_sums) return BZH_E_ARG;
+    void* arena = nullptr;   // WS_IPA as in ipa_check_batch_device
+    BZH_TRY(ws_ensure(ctx, WS_IPA, (B * (n + 2) * 8 + 2 * B * 24 + 256) * 4, &arena));
+    uint32_t* d_s = (uint32_t*)arena;
+    uint32_t* d_out = d_s + B * (n + 2) * 8;
+    *d_sums = d_out;
+    return with_curve(bases->curve, [&](auto c) { return ipa_check_enqueue_t<decltype(c)>(ctx, bases, B, nl, d_s, d_cu, d_pts, d_scal, d_out); });
 }
 
 // pasta_curves from_bytes for one compressed point (host): false = not on the curve / non-canonical

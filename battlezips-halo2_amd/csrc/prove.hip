@@ -552,6 +552,29 @@ int bzh_verify_batch_vk_with(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* sr
     return rc;
 }
 
+int bzh_verify_records_device(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch, size_t n_inputs,
+                              const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, int* results, uint8_t* status) {
+    if (!ctx || !vk || !srs || !g_lagrange || !records || !results) return BZH_E_ARG;
+    if (!n_inputs || n_inputs > BZH_RECORD_MAX_INPUTS || batch > bzh::kVerifyRecordsMaxBatch) return BZH_E_ARG;
+    bzh::KeyRuntime::Call in_flight(vk->rt);
+    const bzh::KeyShape& key = vk->shape;
+    // what reads the key alone comes before what reads the tables
+    if (key.ni != 1 || n_inputs > key.usable) return BZH_E_ARG;   // the reference's circuits: one instance column, its first rows
+    // (a key without a tape has no proof length to hold the stride against: that is BZH_E_RANGE below, whatever the stride)
+    if (key.vprog.ok && (record_stride < BZH_RECORD_HEADER_BYTES || record_stride - BZH_RECORD_HEADER_BYTES < key.vprog.proof_len)) return BZH_E_ARG;
+    if (srs->device != ctx->device || srs->curve != key.curve || srs->n != key.n + 2) return BZH_E_ARG;
+    if (g_lagrange->device != ctx->device || g_lagrange->curve != key.curve || (g_lagrange->n != key.n + 2 && g_lagrange->n != key.n + 3))
+        return BZH_E_ARG;
+    if (!batch) return BZH_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    bzh::Arena& arena = vk->rt.arena_for(ctx->serial, ctx->device);
+    return bzh::with_pasta_curve(key.curve, [&](auto c) {
+        return bzh::verify_records_t<decltype(c)>(ctx, key, srs, g_lagrange, arena, batch, n_inputs, records, record_stride, g0_u_w, results,
+                                                  status);
+    });
+}
+
 // rng_stride == 0: `rng` holds batch x 32-byte seeds (bzh_prove_batch_seeded)
 static int prove_batch_entry(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* advice, int form, int mem, const uint64_t* instances,
                              size_t instance_rows, const uint8_t* rng, size_t rng_stride, uint8_t* proofs, size_t proof_stride,

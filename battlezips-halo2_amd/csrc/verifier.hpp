@@ -224,38 +224,60 @@ static int verify_batch_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* sr
 // call): one decompress_run over key.vp_offsets, one bzh_transcript_batch walking key.vprog.schedule, k_vp_scalars over the
 // key's tape, the gather of the left side's points, ipa_check_batch_device.  A proof whose length is not the key's is rejected
 // here and its row is zero-filled.
-template <class C>
-static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* srs, const bzh_bases* g_lagrange, Arena& arena,
-                                 size_t batch, const uint64_t* instances, size_t inst_rows, const uint8_t* proofs, size_t proof_stride,
-                                 const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
-    const VerifyTape& vp = key.vprog;
-    if (!vp.ok) {
-        ctx->last_error = "bzh_verify_batch: this key's host pass has no device program (BZH_VERIFY_PASS_DEVICE)";
-        return BZH_E_RANGE;
-    }
-    arena.reset();
-    ColumnCommitter<C> pv(ctx, key, arena);
-    const size_t B = batch, np = key.vp_offsets.size(), np_all = B * np, kk = key.k, nl_cap = vp.nl_cap;
-    const size_t ni = (size_t)key.ni, ni1 = std::max<size_t>(ni, 1), plen = vp.proof_len, pstride = (plen + 31) & ~(size_t)31;
-    const bool trace = getenv("BZH_PROVE_TRACE") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto mark = [&](const char* name) {
-        if (!trace) return;
+// The pass has two front doors, verify_batch_device_t (instances and proofs from the caller's arrays, the instance commitments through
+// the host) and verify_records_t (records, everything on the device); what follows "instances and proofs are in HBM" is one body,
+// verify_pass_enqueue_t.
+static bool verify_pass_has_program(bzh_ctx* ctx, const KeyShape& key) {
+    if (key.vprog.ok) return true;
+    ctx->last_error = "bzh_verify_batch: this key's host pass has no device program (BZH_VERIFY_PASS_DEVICE)";
+    return false;
+}
+// the proof rows' pitch in HBM
+static size_t verify_pass_row_stride(const KeyShape& key) { return (key.vprog.proof_len + 31) & ~(size_t)31; }
+// host bytes into the (key, ctx) workspace, asynchronously (h2d_small copies whole 16-byte units: sources are padded copies)
+static int vd_put(bzh_ctx* ctx, Arena& arena, const void* src, size_t bytes, uint32_t** d) {
+    *d = (uint32_t*)arena.alloc(bytes + 16);
+    if (!*d) return BZH_E_OOM;
+    return h2d_small(ctx, *d, src, (bytes + 15) & ~(size_t)15);
+}
+// [bzh_verify_batch] lines on stderr under BZH_PROVE_TRACE=1
+struct VerifyTrace {
+    const bool on = getenv("BZH_PROVE_TRACE") != nullptr;
+    std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+    void mark(const char* name) {
+        if (!on) return;
         const auto now = std::chrono::steady_clock::now();
         fprintf(stderr, "[bzh_verify_batch] %-22s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(now - t_last).count());
         t_last = now;
-    };
-    std::vector<uint64_t> inst_xy;
-    BZH_TRY(instance_commitments<C>(pv, key, srs, g_lagrange, B, instances, inst_rows, g0_u_w, inst_xy));
-    mark("instance commitments");
+    }
+};
+// what a front door leaves in the (key, ctx) workspace: batch rows of verify_pass_row_stride() proof bytes, zero-filled where the
+// pre-reject byte is set; the instance commitments (batch x max(ni, 1)) and G_0 U W, affine canonical
+struct VerifyPassFront {
+    uint8_t* d_rows = nullptr;
+    const uint8_t* d_pre = nullptr;
+    const uint32_t *d_inst_xy = nullptr, *d_srs_xy = nullptr;
+};
+// what the body hands to the opening check: the left side's points (canonical) and scalars, (c, u_j), one reject byte per proof
+struct VerifyPassSides {
+    uint32_t *d_lc_pts = nullptr, *d_lc_scal = nullptr, *d_cu = nullptr;
+    const uint8_t* d_reject = nullptr;
+    size_t nl_cap = 0;
+};
+
+// The device pass from "instances and proofs are in HBM" on: enqueues everything up to k_vp_reject, then `finish` runs the opening
+// check and delivers the results its own way (read-back and host comparison, or a kernel).
+template <class C, class Finish>
+static int verify_pass_enqueue_t(bzh_ctx* ctx, const KeyShape& key, Arena& arena, size_t batch, const VerifyPassFront& front, VerifyTrace& tr,
+                                 Finish&& finish) {
+    const VerifyTape& vp = key.vprog;
+    const size_t B = batch, np = key.vp_offsets.size(), np_all = B * np, kk = key.k, nl_cap = vp.nl_cap;
+    const size_t ni1 = std::max<size_t>((size_t)key.ni, 1), pstride = verify_pass_row_stride(key);
+    const bool trace = tr.on;
+    auto mark = [&](const char* name) { tr.mark(name); };
     // the key's program and points, this call's operands: device memory out of the (key, ctx) workspace
     auto words = [&](size_t w) { return (uint32_t*)arena.alloc(w * 4); };
-    auto put = [&](const void* src, size_t bytes, uint32_t** d) -> int {
-        *d = (uint32_t*)arena.alloc(bytes + 16);
-        if (!*d) return BZH_E_OOM;
-        return h2d_small(ctx, *d, src, (bytes + 15) & ~(size_t)15);
-    };
-    // (h2d_small copies whole 16-byte units: the sources below are padded copies)
+    auto put = [&](const void* src, size_t bytes, uint32_t** d) -> int { return vd_put(ctx, arena, src, bytes, d); };
     auto padded = [](const void* p, size_t bytes) {
         std::vector<uint8_t> v((bytes + 15) & ~(size_t)15, 0);
         if (bytes) memcpy(v.data(), p, bytes);
@@ -265,7 +287,9 @@ static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_ba
     a.batch = B, a.pstride = pstride;
     a.nops = (uint32_t)vp.nops(), a.nslots = vp.nslots, a.nch = vp.nch, a.nev = (uint32_t)vp.ev_offsets.size();
     a.nl_cap = (uint32_t)nl_cap, a.ncu = (uint32_t)(kk + 1), a.np = (uint32_t)np, a.ni = (uint32_t)ni1, a.nfixed = (uint32_t)(key.fixed_commitments.size() / 8);
-    uint32_t *d_ops, *d_consts, *d_evo, *d_outs, *d_ptsrc, *d_vpo, *d_key_xy, *d_srs_xy, *d_inst_xy, *d_vk, *d_pre;
+    uint32_t *d_ops, *d_consts, *d_evo, *d_outs, *d_ptsrc, *d_vpo, *d_key_xy, *d_vk;
+    uint8_t* const d_rows = front.d_rows;
+    const uint32_t *d_inst_xy = front.d_inst_xy, *d_srs_xy = front.d_srs_xy;
     {
         const auto v = padded(vp.ops.data(), vp.ops.size() * 4);
         BZH_TRY(put(v.data(), v.size(), &d_ops));
@@ -296,15 +320,7 @@ static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_ba
         kx.resize(kx.size() + 8, 0);
         BZH_TRY(put(kx.data(), kx.size() * 8, &d_key_xy));
     }
-    BZH_TRY(put(g0_u_w, 3 * 64, &d_srs_xy));
-    BZH_TRY(put(inst_xy.data(), inst_xy.size() * 8, &d_inst_xy));
     BZH_TRY(put(key.vk_repr, 32, &d_vk));
-    std::vector<uint32_t> pre((B + 3) & ~(size_t)3, 0);
-    for (size_t b = 0; b < B; b++) pre[b] = proof_lens[b] != plen ? 1u : 0u;
-    std::vector<uint8_t> pre8((B + 15) & ~(size_t)15, 0);
-    for (size_t b = 0; b < B; b++) pre8[b] = (uint8_t)pre[b];
-    BZH_TRY(put(pre8.data(), pre8.size(), &d_pre));
-    uint8_t* d_rows = (uint8_t*)arena.alloc(B * pstride + 16);
     uint32_t* d_in = words(np_all * 8 + 8);
     uint32_t* d_xy = words(np_all * 16 + 16);
     uint8_t* d_st = (uint8_t*)arena.alloc(np_all + 16);
@@ -314,26 +330,12 @@ static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_ba
     uint32_t* d_lc_pts = words(B * nl_cap * 16);
     uint32_t* d_cu = words(B * (kk + 1) * 8);
     uint32_t* d_flags = words(B + 4);
-    uint8_t* d_reject = (uint8_t*)arena.alloc(pre8.size());
-    if (!d_rows || !d_in || !d_xy || !d_st || !d_ch || !d_slots || !d_lc_scal || !d_lc_pts || !d_cu || !d_flags || !d_reject) return BZH_E_OOM;
-    {   // the proofs: one upload
-        char* slot = nullptr;
-        BZH_TRY(h2d_stage(ctx, B * pstride, &slot));
-        for (size_t b = 0; b < B; b++) {
-            char* dst = slot + b * pstride;
-            if (pre[b]) {
-                memset(dst, 0, pstride);
-            } else {
-                memcpy(dst, proofs + b * proof_stride, plen);
-                if (pstride > plen) memset(dst + plen, 0, pstride - plen);
-            }
-        }
-        BZH_TRY(h2d_commit(ctx, d_rows, slot, B * pstride));
-    }
+    uint8_t* d_reject = (uint8_t*)arena.alloc((B + 15) & ~(size_t)15);
+    if (!d_in || !d_xy || !d_st || !d_ch || !d_slots || !d_lc_scal || !d_lc_pts || !d_cu || !d_flags || !d_reject) return BZH_E_OOM;
     a.d_proofs = d_rows, a.d_ops = d_ops, a.d_consts = d_consts, a.d_ev_offsets = d_evo, a.d_out_slots = d_outs, a.d_pt_src = d_ptsrc;
     a.d_vp_offsets = d_vpo, a.d_ch = d_ch, a.d_slots = d_slots, a.d_lc_scal = d_lc_scal, a.d_cu = d_cu, a.d_flags = d_flags;
     a.d_proof_xy = d_xy, a.d_key_xy = d_key_xy, a.d_inst_xy = d_inst_xy, a.d_srs_xy = d_srs_xy, a.d_point_status = d_st;
-    a.d_pre_reject = (const uint8_t*)d_pre, a.d_lc_pts = d_lc_pts, a.d_reject = d_reject;
+    a.d_pre_reject = front.d_pre, a.d_lc_pts = d_lc_pts, a.d_reject = d_reject;
     BZH_TRY(vp_gather_points(ctx, a, d_in));
     BZH_TRY(decompress_run(ctx, C::id, d_in, np_all, BZH_FORM_CANONICAL, d_xy, d_st));
     mark("vd:stage+decompress");
@@ -361,10 +363,9 @@ static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_ba
     BZH_TRY(vp_scalars_run(ctx, C::id, a));
     if (ev_b) (void)hipEventRecord(ev_b, ctx->stream);
     BZH_TRY(vp_assemble_run(ctx, a));
-    std::vector<uint8_t> rej(pre8.size(), 1);
-    BZH_TRY(d2h_async(ctx, rej.data(), d_reject, rej.size()));
-    std::vector<int> ok(B, 0);
-    BZH_TRY(ipa_check_batch_device(ctx, srs, B, nl_cap, d_lc_pts, d_lc_scal, d_cu, ok.data()));
+    VerifyPassSides sides;
+    sides.d_lc_pts = d_lc_pts, sides.d_lc_scal = d_lc_scal, sides.d_cu = d_cu, sides.d_reject = d_reject, sides.nl_cap = nl_cap;
+    BZH_TRY(finish(sides));
     if (ev_b) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, ev_a, ev_b) == hipSuccess)
@@ -372,7 +373,123 @@ static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_ba
     }
     if (ev_a) (void)hipEventDestroy(ev_a);
     if (ev_b) (void)hipEventDestroy(ev_b);
-    for (size_t b = 0; b < B; b++) results[b] = (ok[b] && !rej[b]) ? 1 : 0;
     mark("vd:ipa check");
     return BZH_OK;
+}
+
+// Front door of bzh_verify_batch / bzh_verify_batch_vk(_with) under BZH_VERIFY_PASS_DEVICE: the instance commitments through the
+// host (instance_commitments), the proofs staged on the host -- a proof whose length is not the key's is rejected here and its row
+// is zero-filled -- and, after the pass, the two sums per proof compared on the host.
+template <class C>
+static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* srs, const bzh_bases* g_lagrange, Arena& arena,
+                                 size_t batch, const uint64_t* instances, size_t inst_rows, const uint8_t* proofs, size_t proof_stride,
+                                 const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
+    if (!verify_pass_has_program(ctx, key)) return BZH_E_RANGE;
+    arena.reset();
+    ColumnCommitter<C> pv(ctx, key, arena);
+    const size_t B = batch, plen = key.vprog.proof_len, pstride = verify_pass_row_stride(key);
+    VerifyTrace tr;
+    std::vector<uint64_t> inst_xy;
+    BZH_TRY(instance_commitments<C>(pv, key, srs, g_lagrange, B, instances, inst_rows, g0_u_w, inst_xy));
+    tr.mark("instance commitments");
+    uint32_t *d_srs_xy, *d_inst_xy, *d_pre;
+    BZH_TRY(vd_put(ctx, arena, g0_u_w, 3 * 64, &d_srs_xy));
+    BZH_TRY(vd_put(ctx, arena, inst_xy.data(), inst_xy.size() * 8, &d_inst_xy));
+    std::vector<uint8_t> pre8((B + 15) & ~(size_t)15, 0);
+    for (size_t b = 0; b < B; b++) pre8[b] = proof_lens[b] != plen ? 1 : 0;
+    BZH_TRY(vd_put(ctx, arena, pre8.data(), pre8.size(), &d_pre));
+    uint8_t* d_rows = (uint8_t*)arena.alloc(B * pstride + 16);
+    if (!d_rows) return BZH_E_OOM;
+    {   // the proofs: one upload
+        char* slot = nullptr;
+        BZH_TRY(h2d_stage(ctx, B * pstride, &slot));
+        for (size_t b = 0; b < B; b++) {
+            char* dst = slot + b * pstride;
+            if (pre8[b]) {
+                memset(dst, 0, pstride);
+            } else {
+                memcpy(dst, proofs + b * proof_stride, plen);
+                if (pstride > plen) memset(dst + plen, 0, pstride - plen);
+            }
+        }
+        BZH_TRY(h2d_commit(ctx, d_rows, slot, B * pstride));
+    }
+    VerifyPassFront front;
+    front.d_rows = d_rows, front.d_pre = (const uint8_t*)d_pre, front.d_inst_xy = d_inst_xy, front.d_srs_xy = d_srs_xy;
+    return verify_pass_enqueue_t<C>(ctx, key, arena, B, front, tr, [&](const VerifyPassSides& s) -> int {
+        std::vector<uint8_t> rej(pre8.size(), 1);
+        BZH_TRY(d2h_async(ctx, rej.data(), s.d_reject, rej.size()));
+        std::vector<int> ok(B, 0);
+        BZH_TRY(ipa_check_batch_device(ctx, srs, B, s.nl_cap, s.d_lc_pts, s.d_lc_scal, s.d_cu, ok.data()));
+        for (size_t b = 0; b < B; b++) results[b] = (ok[b] && !rej[b]) ? 1 : 0;
+        return BZH_OK;
+    });
+}
+
+// bzh_verify_records_device: verify_board / verify_shot for a batch of binary records (csrc/record.hip), device-resident.  The
+// record bytes go up once -- with the caller's G_0 U W behind them, when given --, k_vr_parse checks and unpacks them, the prefix
+// MSM, k_vr_add_w and bzh_batch_normalize's launch make the instance commitments (Params::commit_lagrange with blind 1), the pass
+// runs, and k_vr_result compares the two sums of every opening on the device; one read-back of a result and a status byte per
+// record, and three bytes for the G_0 U W check, ends the call.  The stream is waited for by that read-back alone (msm_run's own
+// waits aside, and a workspace that has to grow on a first call).  The caller has checked the arguments.
+constexpr size_t kVerifyRecordsMaxBatch = 4096;   // bzh_verify_batch's own limit: what the pass's launches are exercised up to
+template <class C>
+static int verify_records_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* srs, const bzh_bases* g_lagrange, Arena& arena, size_t batch,
+                            size_t n_inputs, const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, int* results,
+                            uint8_t* status) {
+    if (!verify_pass_has_program(ctx, key)) return BZH_E_RANGE;
+    arena.reset();
+    const size_t B = batch, Bpad = (B + 15) & ~(size_t)15, plen = key.vprog.proof_len, pstride = verify_pass_row_stride(key);
+    const size_t rstride = (record_stride + 15) & ~(size_t)15, given_bytes = g0_u_w ? 3 * 64 : 0, out_bytes = 2 * Bpad + 16;
+    VerifyTrace tr;
+    uint8_t* d_records = (uint8_t*)arena.alloc(B * rstride + given_bytes);
+    uint8_t* d_rows = (uint8_t*)arena.alloc(B * pstride + 16);
+    uint8_t* d_pre = (uint8_t*)arena.alloc(Bpad);
+    uint32_t* d_inst = (uint32_t*)arena.alloc(B * n_inputs * 32);
+    uint32_t* d_jac = (uint32_t*)arena.alloc(B * 96);
+    uint32_t* d_inst_xy = (uint32_t*)arena.alloc(B * 64 + 64);
+    uint32_t* d_srs_xy = (uint32_t*)arena.alloc(3 * 64 + 64);
+    uint8_t* d_out = (uint8_t*)arena.alloc(out_bytes);
+    if (!d_records || !d_rows || !d_pre || !d_inst || !d_jac || !d_inst_xy || !d_srs_xy || !d_out) return BZH_E_OOM;
+    {   // the records: one upload
+        char* slot = nullptr;
+        BZH_TRY(h2d_stage(ctx, B * rstride + given_bytes, &slot));
+        for (size_t b = 0; b < B; b++) {
+            memcpy(slot + b * rstride, records + b * record_stride, record_stride);
+            if (rstride > record_stride) memset(slot + b * rstride + record_stride, 0, rstride - record_stride);
+        }
+        if (g0_u_w) memcpy(slot + B * rstride, g0_u_w, 3 * 64);
+        BZH_TRY(h2d_commit(ctx, d_records, slot, B * rstride + given_bytes));
+    }
+    VerifyRecordsArgs ra;
+    ra.batch = B, ra.rstride = rstride, ra.pstride = pstride, ra.n_inputs = (uint32_t)n_inputs, ra.proof_len = (uint32_t)plen;
+    ra.d_records = d_records, ra.d_inst = d_inst, ra.d_rows = d_rows, ra.d_pre = d_pre;
+    BZH_TRY(verify_records_parse(ctx, C::id, ra));
+    BZH_TRY(verify_records_srs(ctx, C::id, srs->d_xy, srs->n, g0_u_w ? (const uint32_t*)(d_records + B * rstride) : nullptr, d_srs_xy,
+                               d_out + 2 * Bpad));
+    tr.mark("vr:stage+parse");
+    // Params::commit_lagrange with blind 1: the inputs against the first n_inputs Lagrange points, plus W (the SRS table's last point)
+    BZH_TRY(msm_run(ctx, g_lagrange, d_inst, n_inputs, B, BZH_FORM_MONTGOMERY, d_jac));
+    BZH_TRY(verify_records_add_w(ctx, C::id, d_jac, srs->d_xy + (srs->n - 1) * 16, B));
+    BZH_TRY(normalize_run(ctx, C::id, d_jac, B, BZH_FORM_CANONICAL, d_inst_xy, nullptr, nullptr));
+    tr.mark("instance commitments");
+    VerifyPassFront front;
+    front.d_rows = d_rows, front.d_pre = d_pre, front.d_inst_xy = d_inst_xy, front.d_srs_xy = d_srs_xy;
+    return verify_pass_enqueue_t<C>(ctx, key, arena, B, front, tr, [&](const VerifyPassSides& s) -> int {
+        const uint32_t* d_sums = nullptr;
+        BZH_TRY(ipa_check_sums_device(ctx, srs, B, s.nl_cap, s.d_lc_pts, s.d_lc_scal, s.d_cu, &d_sums));
+        BZH_TRY(verify_records_result(ctx, C::id, d_sums, B, d_pre, s.d_reject, d_out, Bpad));
+        std::vector<uint8_t> out(out_bytes, 0);
+        BZH_TRY(d2h_async(ctx, out.data(), d_out, out_bytes));
+        BZH_TRY(d2h_finish(ctx));
+        if (out[2 * Bpad] | out[2 * Bpad + 1] | out[2 * Bpad + 2]) {
+            ctx->last_error = "bzh_verify_records_device: g0_u_w are not G_0, U, W of srs";
+            return BZH_E_ARG;
+        }
+        for (size_t b = 0; b < B; b++) {
+            results[b] = out[b];
+            if (status) status[b] = out[Bpad + b];
+        }
+        return BZH_OK;
+    });
 }

@@ -1142,6 +1142,33 @@ int bzh_record_decode(const uint8_t* record, size_t record_stride, uint64_t* pub
 int bzh_record_to_json(const uint8_t* record, size_t record_stride, char* out, size_t cap, size_t* len);
 int bzh_record_from_json(const char* text, size_t text_len, uint32_t kind, uint32_t index, uint8_t* record, size_t record_stride);
 
+/* ---- verify_board / verify_shot over a batch of records, device-resident (src/wasm/circuit_wasm.rs:86-116, 180-194) -------------
+ * bzh_verify_records_device reads `batch` binary records (host memory, the fixed-stride layout above, record_stride bytes apart)
+ * and decides accept or reject for each: what bzh_record_decode followed by bzh_verify_batch_vk decides, as ONE call in which
+ * nothing crosses the bus between the upload of the record bytes and the read-back of one result and one status byte per record.
+ * On the ctx's stream: a kernel checks every header and every public input against the modulus (limb by limb, as
+ * BinaryValue::from_repr(..).to_fp()) and unpacks inputs and proofs; the instance commitments are Params::commit_lagrange with
+ * blind 1 -- a prefix MSM over the first n_inputs points of g_lagrange, plus W, normalised by bzh_batch_normalize's launch --;
+ * the per-proof pass is BZH_VERIFY_PASS_DEVICE's; the two sums of every opening check are compared on the device.  The stream is
+ * waited for once, by the read-back (the MSMs' own waits aside, and a workspace that grows on a key's first call).
+ *   n_inputs   what every record must carry: 4 for Shot, 2 for Board
+ *   g0_u_w     G_0, U, W of srs as 3 affine canonical points, compared with the table on the device (BZH_E_ARG after the call's
+ *              one wait if they differ, results[] and status[] untouched), or NULL: no comparison, the table's points are used
+ *   results[b] 1 accept, 0 reject: exactly bzh_verify_batch_vk's on the decoded record
+ *   status[b]  (status may be NULL) bit 0: the record was refused before verification -- a non-zero reserved header field, an
+ *              n_inputs field other than the argument, a proof length other than the key's, or a public input that is not a
+ *              canonical Fp element; bits 1 .. 7 zero.  A refused record is results[b] = 0, never an error, and leaves its
+ *              neighbours alone.  `kind` and `index` are the caller's tags and are not read.
+ * The largest batch a call takes is 4096, bzh_verify_batch's own limit: the pass's launches (one row of a grid per proof, 65535
+ * rows) are exercised up to it.  Nothing selects this call: every other entry point keeps its path and its defaults.  Its speed
+ * has not been measured (tools/ubench_verify_records.py prints the comparison).
+ * BZH_E_ARG: a NULL ctx, vk, srs, g_lagrange, records or results; n_inputs == 0 or > BZH_RECORD_MAX_INPUTS; batch > 4096; a vk
+ * whose constraint system does not have exactly one instance column; record_stride < BZH_RECORD_HEADER_BYTES + the key's proof
+ * length; tables of another device, curve or size.  batch == 0: BZH_OK, nothing is touched.  BZH_E_RANGE: a key whose shape has
+ * no device program, as bzh_verify_batch_vk_with under BZH_VERIFY_PASS_DEVICE. */
+int bzh_verify_records_device(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch, size_t n_inputs,
+                              const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, int* results, uint8_t* status);
+
 #ifdef __cplusplus
 }
 #endif
