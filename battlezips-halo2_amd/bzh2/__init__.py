@@ -1185,6 +1185,7 @@ EXPORTS += ["bzh_synthesize_shot_with", "bzh_synthesize_board_with"]
 EXPORTS += ["bzh_prove_shots_device", "bzh_prove_boards_device"]
 # records in, accept / reject out, in one device-resident call (NativeVerifyingKey.verify_records)
 EXPORTS += ["bzh_verify_records_device"]
+EXPORTS += ["bzh_verify_records_accumulated", "bzh_verify_batch_vk_accumulated", "bzh_accumulation_weights", "bzh_ipa_check_accumulated"]
 E_VERIFY = -6
 
 
@@ -1447,4 +1448,7 @@ def __getattr__(name):
     if name == "NativeVerifyingKey":
         from .native import NativeVerifyingKey
         return NativeVerifyingKey
+    if name == "accumulation_weights":   # likewise: the weights of NativeVerifyingKey.verify_records_accumulated / verify_batch_accumulated
+        from .native import accumulation_weights
+        return accumulation_weights
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

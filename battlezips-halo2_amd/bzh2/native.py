@@ -55,6 +55,13 @@ def _bind():
                                            ctypes.POINTER(ctypes.c_size_t), _VP, ctypes.POINTER(ctypes.c_int)]
     L.bzh_verify_records_device.argtypes = [_VP, _VP, _VP, _VP, ctypes.c_size_t, ctypes.c_size_t, _VP, ctypes.c_size_t, _VP,
                                             ctypes.POINTER(ctypes.c_int), _VP]
+    L.bzh_verify_records_accumulated.argtypes = [_VP, _VP, _VP, _VP, ctypes.c_size_t, ctypes.c_size_t, _VP, ctypes.c_size_t, _VP,
+                                                 ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), _VP, ctypes.POINTER(ctypes.c_int)]
+    L.bzh_verify_batch_vk_accumulated.argtypes = [_VP, _VP, _VP, _VP, ctypes.c_size_t, _VP, ctypes.c_size_t, _VP, ctypes.c_size_t,
+                                                  ctypes.POINTER(ctypes.c_size_t), _VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int),
+                                                  ctypes.POINTER(ctypes.c_int)]
+    L.bzh_accumulation_weights.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, _VP]
+    L.bzh_ipa_check_accumulated.argtypes = [_VP, _VP, ctypes.c_size_t, ctypes.c_size_t, _VP, _VP, _VP, _VP, _VP, ctypes.POINTER(ctypes.c_int)]
     L.bzh_pk_verify_pass_select.argtypes = [_VP, ctypes.c_int]
     L.bzh_pk_verify_pass_selected.argtypes = [_VP, ctypes.POINTER(ctypes.c_int)]
     L._bzh_native_bound = True
@@ -69,6 +76,18 @@ def rng_expand(seed: bytes, first_draw: int, draws: int) -> bytes:
     if rc:
         raise BzhError(rc, "bzh_rng_expand")
     return out.tobytes()
+
+
+def accumulation_weights(curve: int, seed: bytes, batch: int) -> list:
+    """the weights of an accumulated batch verification (bzh_accumulation_weights): draw b of rng_expand(seed, b, 1) reduced into
+    the scalar field of `curve` as a 512-bit little-endian integer; a list of ints.  The seed must be unpredictable to the proofs'
+    author: see the SECURITY paragraph in include/bzh2.h."""
+    assert len(seed) == 32
+    out = np.zeros((max(batch, 1), 4), dtype=np.uint64)
+    rc = _bind().bzh_accumulation_weights(curve, seed, batch, _VP(out.ctypes.data))
+    if rc:
+        raise BzhError(rc, "bzh_accumulation_weights")
+    return [int.from_bytes(out[b].tobytes(), "little") for b in range(batch)]
 
 
 QUOTIENT_INTERPRETER, QUOTIENT_BUILTIN, QUOTIENT_MODULE = 0, 1, 2
@@ -584,6 +603,57 @@ class NativeVerifyingKey:
                                          _VP(status.ctypes.data) if want_status else None)
         ctx._check(rc, "bzh_verify_records_device")
         return [bool(res[b]) for b in range(B)], (status[:B].copy() if want_status else None)
+
+    def verify_records_accumulated(self, ctx: Context, params, records, n_inputs: int, seed: bytes | None = None, g0_u_w=None,
+                                   record_stride: int | None = None):
+        """verify_records with ONE accumulated opening check for the batch (bzh_verify_records_accumulated).  seed: 32 bytes that
+        the records' authors cannot predict, fresh per call; None draws os.urandom(32).  Returns (results, status, path): results
+        and status as verify_records returns them; path 0: the accumulated check accepted the included records, 1: it did not and
+        the per-record check ran as well."""
+        import os
+        L = _bind()
+        bases = getattr(params, "bases", params)
+        lag = getattr(params, "bases_lagrange", None)
+        B = len(records)
+        buf = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in records), dtype=np.uint8)) if B else np.zeros(1, dtype=np.uint8)
+        stride = record_stride if record_stride is not None else (len(records[0]) if B else 0)
+        assert all(len(r) == stride for r in records) or record_stride is not None
+        g0 = np.ascontiguousarray(g0_u_w, dtype=np.uint64) if g0_u_w is not None else None
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        assert len(seed) == 32
+        res = (ctypes.c_int * max(B, 1))()
+        status = np.zeros(max(B, 1), dtype=np.uint8)
+        path = ctypes.c_int(0)
+        rc = L.bzh_verify_records_accumulated(ctx.handle, self.handle, bases.handle, lag.handle if lag is not None else None, B, n_inputs,
+                                              _VP(buf.ctypes.data), stride, _VP(g0.ctypes.data) if g0 is not None else None, seed, res,
+                                              _VP(status.ctypes.data), ctypes.byref(path))
+        ctx._check(rc, "bzh_verify_records_accumulated")
+        return [bool(res[b]) for b in range(B)], status[:B].copy(), path.value
+
+    def verify_batch_accumulated(self, ctx: Context, params, instances, proofs, seed: bytes | None = None, lagrange: bool = True, g0_u_w=None):
+        """verify_batch under the device pass with ONE accumulated opening check (bzh_verify_batch_vk_accumulated); seed as in
+        verify_records_accumulated.  Returns (results, path)."""
+        import os
+        L = _bind()
+        bases = getattr(params, "bases", params)
+        lag = getattr(params, "bases_lagrange", None) if lagrange else None
+        g0 = np.ascontiguousarray(g0_u_w, dtype=np.uint64) if g0_u_w is not None else _g0_u_w(params)
+        B = len(proofs)
+        inst, rows = NativeProvingKey._instances(self, instances)
+        stride = max(max(len(pr) for pr in proofs), 1)
+        buf = np.zeros((B, stride), dtype=np.uint8)
+        lens = (ctypes.c_size_t * B)(*[len(pr) for pr in proofs])
+        for b, pr in enumerate(proofs):
+            buf[b, :len(pr)] = np.frombuffer(pr, dtype=np.uint8)
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        assert len(seed) == 32
+        res = (ctypes.c_int * B)()
+        path = ctypes.c_int(0)
+        rc = L.bzh_verify_batch_vk_accumulated(ctx.handle, self.handle, bases.handle, lag.handle if lag is not None else None, B,
+                                               _VP(inst.ctypes.data), rows, _VP(buf.ctypes.data), stride, lens, _VP(g0.ctypes.data), seed, res,
+                                               ctypes.byref(path))
+        ctx._check(rc, "bzh_verify_batch_vk_accumulated")
+        return [bool(v) for v in res], path.value
 
     def close(self):
         """bzh_vk_free.  Refused (BzhError, the key stays open) while a verify_batch on the key has started on any ctx and not

@@ -1106,6 +1106,15 @@ int bzh_ipa_verify(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* commitm
     return ipa_verify(ctx, bases, commitment_xy, x3, v, proof, proof_len, transcript, g0_u_w);
 }
 
+int bzh_ipa_check_accumulated(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
+                              const uint64_t* cu, const uint64_t* weights, const uint8_t* exclude, int* ok) {
+    if (!ctx || !bases || !batch || batch > 4096 || !nl || nl > 65536 || !lc_pts || !lc_scal || !cu || !weights || !ok) return BZH_E_ARG;
+    if (bases->n < 3 || bases->device != ctx->device) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ipa_check_accumulated(ctx, bases, batch, nl, lc_pts, lc_scal, cu, weights, exclude, ok);
+}
+
 int bzh_jacobian_to_affine(int curve, const uint64_t* xyz, size_t n, int form, uint64_t* out_xy) {
     if ((!xyz || !out_xy) && n) return BZH_E_ARG;
     if (!valid_curve(curve) || !valid_form(form)) return BZH_E_ARG;

@@ -475,13 +475,24 @@ int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t n
                     const uint64_t* cu, int* ok);
 // the same check with its operands already on the device (the verifier's device pass): d_pts batch x nl affine canonical points
 // (taken to Montgomery form in place), d_scal canonical, d_cu batch x (k + 1) Montgomery; 16-byte aligned
+// (pts_montgomery: as for ipa_check_sums_device below)
 int ipa_check_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
-                           const uint32_t* d_cu, int* ok);
+                           const uint32_t* d_cu, int* ok, bool pts_montgomery = false);
 // the same launches without the read-back and the host comparison: *d_sums = the batch right sides' Jacobian points, then the batch
 // left sides', Montgomery, 24 words each, in WS_IPA -- valid until the next holder of that slot.  Enqueues only (msm_run's own waits
-// aside).
+// aside).  pts_montgomery: d_pts are in Montgomery form already (ipa_check_accumulated_device ran on them) and are not converted.
 int ipa_check_sums_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
-                          const uint32_t* d_cu, const uint32_t** d_sums);
+                          const uint32_t* d_cu, const uint32_t** d_sums, bool pts_montgomery = false);
+// The accumulated check: ONE verdict for the whole batch, d_ok[0] = 1 when
+//     sum_b w'_b * ( sum_i d_scal[b][i] * d_pts[b][i] )  ==  < sum_b w'_b * c_b * s(u_b), G >,   w'_b = d_exclude[b] ? 0 : d_weights[b].
+// The operands are ipa_check_sums_device's (d_pts taken to Montgomery form in place); d_weights batch elements, Montgomery;
+// d_exclude batch bytes, any alignment, or null; an excluded opening's rows are not read.  Two MSMs whatever the batch: n + 2 terms
+// against `bases`, batch * nl terms on the ad-hoc table.  WS_IPA: O(n + batch * nl).  Enqueues only (msm_run's own waits aside).
+int ipa_check_accumulated_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
+                                 const uint32_t* d_cu, const uint32_t* d_weights, const uint8_t* d_exclude, uint8_t* d_ok);
+// the same with host operands (bzh_ipa_check_accumulated): lc_pts, lc_scal, cu and weights canonical; stages in WS_STAGE
+int ipa_check_accumulated(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
+                          const uint64_t* cu, const uint64_t* weights, const uint8_t* exclude, int* ok);
 bool point_decompress(int curve, const uint8_t* in, uint64_t* xy_canonical);
 // sqrt_decompress.hip (device pointers, 16-byte aligned; elements and points in `form`).  batch_sqrt_run: in place, d_status[i] = 1
 // for a square (root written), 0 otherwise (element untouched).  decompress_run: n x 32 bytes -> n affine points x || y and one

@@ -837,10 +837,11 @@ __global__ void __launch_bounds__(kSmallMsmThreads) k_ipa_small_msm(const uint32
 }
 
 // The launches, operands in device memory: d_s batch x (n + 2) scratch, d_cu Montgomery, d_pts canonical (taken to Montgomery form
-// in place), d_scal canonical, d_out 2 x batch Jacobian sums (Montgomery): the right sides, then the left sides.
+// in place; pts_montgomery: they already are, by the accumulated check that ran before on the same operands, and stay as they
+// are), d_scal canonical, d_out 2 x batch Jacobian sums (Montgomery): the right sides, then the left sides.
 template <class C>
 static int ipa_check_enqueue_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_s, const uint32_t* d_cu, uint32_t* d_pts,
-                               const uint32_t* d_scal, uint32_t* d_out) {
+                               const uint32_t* d_scal, uint32_t* d_out, bool pts_montgomery = false) {
     using SF = typename CurveInfo<C>::SF;
     const size_t n = bases->n - 2, B = batch;
     unsigned k = 0;
@@ -851,7 +852,7 @@ static int ipa_check_enqueue_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batc
     BZH_HIP_TRY(ctx, hipGetLastError());
     BZH_TRY(msm_run(ctx, bases, d_s, n + 2, B, BZH_FORM_MONTGOMERY, d_out));
     // left side: B independent nl-term sums
-    BZH_TRY(bases_to_montgomery(ctx, C::id, d_pts, B * nl));
+    if (!pts_montgomery) BZH_TRY(bases_to_montgomery(ctx, C::id, d_pts, B * nl));
     hipLaunchKernelGGL((k_ipa_small_msm<C>), dim3((unsigned)B), dim3(kSmallMsmThreads), 0, st, d_pts, d_scal, nl, d_out + B * 24);
     BZH_HIP_TRY(ctx, hipGetLastError());
     return BZH_OK;
@@ -859,10 +860,10 @@ static int ipa_check_enqueue_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batc
 // ... and the comparison on the host: the sums come back and are normalised there
 template <class C>
 static int ipa_check_run_t(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_s, const uint32_t* d_cu, uint32_t* d_pts,
-                           const uint32_t* d_scal, uint32_t* d_out, int* ok) {
+                           const uint32_t* d_scal, uint32_t* d_out, int* ok, bool pts_montgomery = false) {
     using PB = typename C::Base;
     const size_t B = batch;
-    BZH_TRY(ipa_check_enqueue_t<C>(ctx, bases, batch, nl, d_s, d_cu, d_pts, d_scal, d_out));
+    BZH_TRY(ipa_check_enqueue_t<C>(ctx, bases, batch, nl, d_s, d_cu, d_pts, d_scal, d_out, pts_montgomery));
     std::vector<uint64_t> jac(2 * B * 12), lhs(B * 8), rhs(B * 8);
     BZH_TRY(d2h_async(ctx, jac.data(), d_out, 2 * B * 96));
     BZH_TRY(d2h_finish(ctx));
@@ -907,7 +908,7 @@ int ipa_check_batch(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t n
 }
 
 int ipa_check_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
-                           const uint32_t* d_cu, int* ok) {
+                           const uint32_t* d_cu, int* ok, bool pts_montgomery) {
     const size_t n = bases->n - 2, B = batch;
     unsigned k = 0;
     while (((size_t)1 << k) < n) k++;
@@ -916,11 +917,13 @@ int ipa_check_batch_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, s
     BZH_TRY(ws_ensure(ctx, WS_IPA, (B * (n + 2) * 8 + 2 * B * 24 + 256) * 4, &arena));
     uint32_t* d_s = (uint32_t*)arena;
     uint32_t* d_out = d_s + B * (n + 2) * 8;
-    return with_curve(bases->curve, [&](auto c) { return ipa_check_run_t<decltype(c)>(ctx, bases, B, nl, d_s, d_cu, d_pts, d_scal, d_out, ok); });
+    return with_curve(bases->curve, [&](auto c) {
+        return ipa_check_run_t<decltype(c)>(ctx, bases, B, nl, d_s, d_cu, d_pts, d_scal, d_out, ok, pts_montgomery);
+    });
 }
 
 int ipa_check_sums_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
-                          const uint32_t* d_cu, const uint32_t** d_sums) {
+                          const uint32_t* d_cu, const uint32_t** d_sums, bool pts_montgomery) {
     const size_t n = bases->n - 2, B = batch;
     unsigned k = 0;
     while (((size_t)1 << k) < n) k++;
@@ -930,8 +933,199 @@ int ipa_check_sums_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, si
     uint32_t* d_s = (uint32_t*)arena;
     uint32_t* d_out = d_s + B * (n + 2) * 8;
     *d_sums = d_out;
-    return with_curve(bases->curve, [&](auto c) { return ipa_check_enqueue_t<decltype(c)>(ctx, bases, B, nl, d_s, d_cu, d_pts, d_scal, d_out); });
+    return with_curve(bases->curve, [&](auto c) {
+        return ipa_check_enqueue_t<decltype(c)>(ctx, bases, B, nl, d_s, d_cu, d_pts, d_scal, d_out, pts_montgomery);
+    });
 }
+
+// ---------------------------------------------------------------------------
+// The accumulated opening check: a random linear combination of the batch's B equations is ONE equation,
+//     sum_b w_b * ( sum_i lc_scal[b][i] * lc_pts[b][i] )  ==  < sum_b w_b * c_b * s(u_b) , G >
+// so the right side is one n-term MSM against the SRS on a vector a field kernel accumulates, and the left side one Pippenger MSM
+// over the B * nl ad-hoc points: no B x n buffer, no per-opening chain of doublings.  An excluded opening (weight 0) contributes
+// to neither side.  Workspace (WS_IPA): (n + 2) + B + B * nl scalars and two sums.
+// ---------------------------------------------------------------------------
+// w'_b = exclude[b] ? 0 : w_b   (Montgomery)
+template <class P>
+__global__ void __launch_bounds__(256) k_ipa_acc_weights(const uint32_t* __restrict__ w, const uint8_t* __restrict__ exclude, size_t batch,
+                                                           uint32_t* __restrict__ wp) {
+    const size_t b = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (b >= batch) return;
+    const bool out = exclude != nullptr && exclude[b] != 0;
+    fe_store(wp + b * 8, out ? fe_zero<P>() : fe_load<P>(w + b * 8));
+}
+
+// s_acc[i] = sum_b w'_b * c_b * prod_{j : bit (k-1-j) of i} u_(b,j)  for i < n;  s_acc[n] = s_acc[n+1] = 0.
+// A workgroup owns 2^ke consecutive i (ke = min(k, 8): 256 of them, or all n below that), one per lane, and walks the batch in
+// groups of kAccSGroup proofs.  Bit p of i selects u_(k-1-p); the low ke bits are split into kl = ke / 2 low and km = ke - kl
+// middle bits, the bits above ke are the workgroup's own.  Per group, lane (g, x) writes two LDS table entries of proof g:
+//   tl[g][x] = the product over the set bits of x among the kl low ones                          (at most kl products)
+//   tm[g][x] = w'_b c_b * the workgroup's bits * the set bits of x among the km middle ones     (at most 1 + (k - ke) + km)
+// and after a barrier every live lane adds tl[g][lo] * tm[g][mid] for the group's proofs: ONE product per (b, i), plus the
+// tables' at most kl + 1 + (k - ke) + km = k + 1 products per lane and group of 16, issued by all 256 lanes whatever ke is.
+// Per (b, i) that is 1 + (k + 1) / 16 for k >= 8 (kl = km = 4; 1.9 at k = 14), where walking all k bits per (b, i) costs k / 2.
+// For k < 8 the workgroup is the whole vector, kl = k / 2 (2 at k = 5, 3 at k = 6), and only 2^k of the 256 lanes are live in the
+// accumulate phase (32 at k = 5): the tables' k + 1 issues per group are then spread over 2^k elements, 1 + (k + 1) * 256 /
+// (16 * 2^k) per (b, i) -- 4 at k = 5 -- which at n <= 128 is a one-workgroup kernel of microseconds either way.
+// A proof of weight 0 leaves zero tables and its (c, u_j) row is not read; lanes past the batch in the last group likewise.
+// Reads d_cu in place, writes (n + 2) * 32 bytes, nothing proportional to B * n.
+// gfx950 (Pasta fields): 68 VGPRs, no scratch, 16 KB of LDS; k_ipa_acc_scale 57 VGPRs, k_ipa_acc_result 94, no scratch either.
+static constexpr unsigned kAccSGroup = 16, kAccSSlots = 16;
+template <class P>
+__global__ void __launch_bounds__(256) k_ipa_acc_s(const uint32_t* __restrict__ cu, const uint32_t* __restrict__ wp, size_t batch, size_t n,
+                                                     unsigned k, uint32_t* __restrict__ s_acc) {
+    __shared__ Fe<P> tl[kAccSGroup][kAccSSlots], tm[kAccSGroup][kAccSSlots];
+    const unsigned t = threadIdx.x, ke = k < 8 ? k : 8, kl = ke / 2, km = ke - kl;
+    const size_t base = (size_t)blockIdx.x << ke, i = base + t;
+    const bool live = t < (1u << ke);   // (the grid is n >> ke workgroups: base + t < n)
+    const unsigned lo = t & ((1u << kl) - 1u), mid = (t >> kl) & ((1u << km) - 1u);
+    const unsigned g = t / kAccSSlots, x = t % kAccSSlots;
+    Fe<P> acc = fe_zero<P>();
+    for (size_t b0 = 0; b0 < batch; b0 += kAccSGroup) {
+        const size_t b = b0 + g;
+        Fe<P> el = fe_zero<P>(), em = fe_zero<P>();
+        if (b < batch) {
+            const Fe<P> w = fe_load<P>(wp + b * 8);
+            if (!fe_is_zero(w)) {
+                const uint32_t* row = cu + b * (size_t)(k + 1) * 8;   // [c, u_0 .. u_(k-1)]: bit p of i takes row[k - p]
+                if (x < (1u << kl)) {
+                    el = fe_one<P>();
+                    for (unsigned p = 0; p < kl; p++)
+                        if ((x >> p) & 1) el = fe_mul(el, fe_load<P>(row + (size_t)(k - p) * 8));
+                }
+                if (x < (1u << km)) {
+                    em = fe_mul(w, fe_load<P>(row));
+                    for (unsigned p = ke; p < k; p++)   // the workgroup's bits: uniform
+                        if ((base >> p) & 1) em = fe_mul(em, fe_load<P>(row + (size_t)(k - p) * 8));
+                    for (unsigned p = 0; p < km; p++)
+                        if ((x >> p) & 1) em = fe_mul(em, fe_load<P>(row + (size_t)(k - kl - p) * 8));
+                }
+            }
+        }
+        __syncthreads();   // the previous group's tables have been read
+        tl[g][x] = el;
+        tm[g][x] = em;
+        __syncthreads();
+        const unsigned cnt = batch - b0 < kAccSGroup ? (unsigned)(batch - b0) : kAccSGroup;
+        if (live)
+            for (unsigned q = 0; q < cnt; q++) acc = fe_add(acc, fe_mul(tl[q][lo], tm[q][mid]));
+    }
+    if (live) fe_store(s_acc + i * 8, acc);
+    if (blockIdx.x == 0 && t < 2) fe_store(s_acc + (n + t) * 8, fe_zero<P>());   // no U / W contribution on the right
+}
+
+// scal'[b][i] = w'_b * lc_scal[b][i], canonical in and canonical out (a Montgomery factor times a canonical one), the form the
+// left side's msm_run is given.  The (0,0) padding of an opening's last slots is kept out of the sum HERE, by a zero scalar -- a
+// zero scalar has all-zero digits and k_msm_accumulate files it in no bucket, so the point is never loaded (its own aff_is_id
+// test in the saturated loop is a second guard, not what this path relies on); an opening of weight 0 gets zeros without its
+// rows being read.
+template <class C>
+__global__ void __launch_bounds__(256) k_ipa_acc_scale(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ scal,
+                                                         const uint32_t* __restrict__ wp, size_t total, size_t nl, uint32_t* __restrict__ out) {
+    using P = typename C::Base;
+    using SF = typename CurveInfo<C>::SF;
+    const size_t e = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (e >= total) return;
+    const Fe<SF> w = fe_load<SF>(wp + (e / nl) * 8);
+    Fe<SF> r = fe_zero<SF>();
+    if (!fe_is_zero(w)) {
+        Affine<P> q;
+        q.x = fe_load<P>(pts + e * 16);
+        q.y = fe_load<P>(pts + e * 16 + 8);
+        if (!aff_is_id(q)) r = fe_mul(w, fe_load<SF>(scal + e * 8));
+    }
+    fe_store(out + e * 8, r);
+}
+
+// one lane: the right sum (Jacobian, Montgomery) against the left sum (Jacobian, canonical: its MSM ran on canonical scalars), by
+// cross-multiplication as k_vr_result compares -- X1 Z2^2 = X2 Z1^2 and Y1 Z2^3 = Y2 Z1^3, or both the identity -- into one byte
+template <class C>
+__global__ void __launch_bounds__(64) k_ipa_acc_result(const uint32_t* __restrict__ sums, uint8_t* __restrict__ ok) {
+    using P = typename C::Base;
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const Fe<P> X1 = fe_load<P>(sums), Y1 = fe_load<P>(sums + 8), Z1 = fe_load<P>(sums + 16);
+    const Fe<P> X2 = fe_to_mont(fe_load<P>(sums + 24)), Y2 = fe_to_mont(fe_load<P>(sums + 32)), Z2 = fe_to_mont(fe_load<P>(sums + 40));
+    const bool id1 = fe_is_zero(Z1), id2 = fe_is_zero(Z2);
+    const Fe<P> z1s = fe_sqr(Z1), z2s = fe_sqr(Z2);
+    const bool ex = fe_eq(fe_mul(X1, z2s), fe_mul(X2, z1s));
+    const bool ey = fe_eq(fe_mul(Y1, fe_mul(z2s, Z2)), fe_mul(Y2, fe_mul(z1s, Z1)));
+    ok[0] = ((id1 && id2) || (!id1 && !id2 && ex && ey)) ? 1 : 0;
+}
+
+int ipa_check_accumulated_device(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, uint32_t* d_pts, const uint32_t* d_scal,
+                                 const uint32_t* d_cu, const uint32_t* d_weights, const uint8_t* d_exclude, uint8_t* d_ok) {
+    const size_t n = bases->n - 2, B = batch, na = B * nl;
+    unsigned k = 0;
+    while (((size_t)1 << k) < n) k++;
+    if (((size_t)1 << k) != n || !B || !nl || !d_weights || !d_ok) return BZH_E_ARG;
+    void* arena = nullptr;   // WS_IPA, held across the two MSMs (which take WS_SCRATCH_* only): O(n + B * nl)
+    BZH_TRY(ws_ensure(ctx, WS_IPA, ((n + 2) * 8 + B * 8 + na * 8 + 2 * 24 + 64) * 4, &arena));
+    uint32_t* d_s = (uint32_t*)arena;
+    uint32_t* d_wp = d_s + (n + 2) * 8;
+    uint32_t* d_sc = d_wp + B * 8;
+    uint32_t* d_sums = d_sc + na * 8;
+    return with_curve(bases->curve, [&](auto c) -> int {
+        using C = decltype(c);
+        using SF = typename CurveInfo<C>::SF;
+        hipStream_t st = ctx->stream;
+        const unsigned ke = k < 8 ? k : 8;
+        hipLaunchKernelGGL((k_ipa_acc_weights<SF>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, d_weights, d_exclude, B, d_wp);
+        hipLaunchKernelGGL((k_ipa_acc_s<SF>), dim3((unsigned)(n >> ke)), dim3(256), 0, st, d_cu, d_wp, B, n, k, d_s);
+        BZH_HIP_TRY(ctx, hipGetLastError());
+        BZH_TRY(msm_run(ctx, bases, d_s, n + 2, 1, BZH_FORM_MONTGOMERY, d_sums));
+        // left side: one sum over every opening's points, on an ad-hoc table (no window rows, no fe29 copy: the saturated loop,
+        // whose xyzz_madd takes P + P and P + (-P) -- points repeat across openings, so both occur)
+        BZH_TRY(bases_to_montgomery(ctx, C::id, d_pts, na));
+        hipLaunchKernelGGL((k_ipa_acc_scale<C>), dim3((unsigned)((na + 255) / 256)), dim3(256), 0, st, d_pts, d_scal, d_wp, na, nl, d_sc);
+        BZH_HIP_TRY(ctx, hipGetLastError());
+        bzh_bases tmp;
+        tmp.curve = C::id;
+        tmp.n = na;
+        tmp.d_xy = d_pts;
+        tmp.device = ctx->device;
+        BZH_TRY(msm_run(ctx, &tmp, d_sc, na, 1, BZH_FORM_CANONICAL, d_sums + 24));
+        hipLaunchKernelGGL((k_ipa_acc_result<C>), dim3(1), dim3(64), 0, st, d_sums, d_ok);
+        BZH_HIP_TRY(ctx, hipGetLastError());
+        return BZH_OK;
+    });
+}
+
+// the same with its operands in host memory (bzh_ipa_check_accumulated): uploaded as ipa_check_batch_t uploads, weights canonical
+int ipa_check_accumulated(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
+                          const uint64_t* cu, const uint64_t* weights, const uint8_t* exclude, int* ok) {
+    const size_t n = bases->n - 2, B = batch, na = B * nl, Bpad = (B + 15) & ~(size_t)15;
+    unsigned k = 0;
+    while (((size_t)1 << k) < n) k++;
+    if (((size_t)1 << k) != n || !B || !nl) return BZH_E_ARG;
+    void* arena = nullptr;   // WS_STAGE: the operands (the leaf holds WS_IPA)
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, (B * (k + 1) * 8 + na * 16 + na * 8 + B * 8) * 4 + Bpad + 64, &arena));
+    uint32_t* d_cu = (uint32_t*)arena;
+    uint32_t* d_pts = d_cu + B * (k + 1) * 8;
+    uint32_t* d_scal = d_pts + na * 16;
+    uint32_t* d_w = d_scal + na * 8;
+    uint8_t* d_ex = (uint8_t*)(d_w + B * 8);
+    uint8_t* d_ok = d_ex + Bpad;
+    return with_curve(bases->curve, [&](auto c) -> int {
+        using SF = typename CurveInfo<decltype(c)>::SF;
+        std::vector<Fe<SF>> cum(B * (k + 1)), wm(B);
+        for (size_t i = 0; i < cum.size(); i++) cum[i] = fe_to_mont(fe_from_u64<SF>(cu + 4 * i));
+        for (size_t b = 0; b < B; b++) wm[b] = fe_to_mont(fe_from_u64<SF>(weights + 4 * b));
+        std::vector<uint8_t> ex(Bpad, 0);
+        if (exclude) memcpy(ex.data(), exclude, B);
+        BZH_TRY(h2d_small(ctx, d_cu, cum.data(), cum.size() * 32));
+        BZH_TRY(h2d_small(ctx, d_pts, lc_pts, na * 64));
+        BZH_TRY(h2d_small(ctx, d_scal, lc_scal, na * 32));
+        BZH_TRY(h2d_small(ctx, d_w, wm.data(), B * 32));
+        BZH_TRY(h2d_small(ctx, d_ex, ex.data(), Bpad));
+        BZH_TRY(ipa_check_accumulated_device(ctx, bases, B, nl, d_pts, d_scal, d_cu, d_w, exclude ? d_ex : nullptr, d_ok));
+        uint8_t out[16] = {0};
+        BZH_TRY(d2h_async(ctx, out, d_ok, 16));
+        BZH_TRY(d2h_finish(ctx));
+        *ok = out[0] ? 1 : 0;
+        return BZH_OK;
+    });
+}
+
 
 // pasta_curves from_bytes for one compressed point (host): false = not on the curve / non-canonical
 bool point_decompress(int curve, const uint8_t* in, uint64_t* xy_canonical) {

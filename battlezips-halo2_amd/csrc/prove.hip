@@ -48,6 +48,7 @@
 #include "prove_device_scalars.hpp" // (the blind sources as k_pd_blinds reads them)
 #include "prove_game_scalars.hpp"   // (the status shift of k_pg_status; with it synthesize_device.hpp: the layout, the launch)
 #include "vm2_isa.hpp"
+#include "verify_records.hpp"      // (a record's refusal as k_vr_parse decides it: vr_record_refused_host)
 
 // the table of quotient kernels generated at build time (quotient_builtin.hip); absent (null) in the generator's own link
 extern "C" const bzh_builtin_quotient* bzh_builtin_quotients(size_t* count) __attribute__((weak));
@@ -470,7 +471,7 @@ int bzh_verify_batch(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_t* ins
         BZH_TRY(bzh::pk_fill_vk<C>(ctx, pk));
         if (pass_on_device)
             return bzh::verify_batch_device_t<C>(ctx, *pk, pk->srs, nullptr, arena, batch, instances, instance_rows, proofs, proof_stride, proof_lens,
-                                                 g0_u_w, results);
+                                                 g0_u_w, nullptr, results, nullptr);
         return bzh::verify_batch_t<C>(ctx, *pk, pk->srs, nullptr, arena, points_on_device, batch, instances, instance_rows, proofs, proof_stride,
                                       proof_lens, g0_u_w, results);
     });
@@ -518,9 +519,10 @@ int bzh_verify_batch_vk(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, co
                                     proof_lens, g0_u_w, results);
 }
 
-int bzh_verify_batch_vk_with(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, int pass_where,
-                             size_t batch, const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
-                             const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
+// bzh_verify_batch_vk_with, and with a seed bzh_verify_batch_vk_accumulated: the same checks, the same front door
+static int verify_batch_vk_entry(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, int pass_where,
+                                 size_t batch, const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
+                                 const size_t* proof_lens, const uint64_t* g0_u_w, const uint8_t* seed, int* results, int* path) {
     if (pass_where != BZH_VERIFY_PASS_HOST && pass_where != BZH_VERIFY_PASS_DEVICE) return BZH_E_ARG;
     if (!ctx || !vk || !srs || !batch || batch > 4096 || !proofs || !proof_lens || !g0_u_w || !results) return BZH_E_ARG;
     bzh::KeyRuntime::Call in_flight(vk->rt);
@@ -544,7 +546,7 @@ int bzh_verify_batch_vk_with(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* sr
     const int rc = bzh::with_pasta_curve(key.curve, [&](auto c) {
         if (pass_where == BZH_VERIFY_PASS_DEVICE)
             return bzh::verify_batch_device_t<decltype(c)>(ctx, key, srs, g_lagrange, arena, batch, instances, instance_rows, proofs, proof_stride,
-                                                           proof_lens, g0_u_w, results);
+                                                           proof_lens, g0_u_w, seed, results, path);
         return bzh::verify_batch_t<decltype(c)>(ctx, key, srs, g_lagrange, arena, false, batch, instances, instance_rows, proofs, proof_stride,
                                                 proof_lens, g0_u_w, results);
     });
@@ -552,8 +554,17 @@ int bzh_verify_batch_vk_with(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* sr
     return rc;
 }
 
-int bzh_verify_records_device(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch, size_t n_inputs,
-                              const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, int* results, uint8_t* status) {
+int bzh_verify_batch_vk_with(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, int pass_where,
+                             size_t batch, const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
+                             const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
+    return verify_batch_vk_entry(ctx, vk, srs, g_lagrange, pass_where, batch, instances, instance_rows, proofs, proof_stride, proof_lens, g0_u_w,
+                                 nullptr, results, nullptr);
+}
+
+// bzh_verify_records_device, and with a seed bzh_verify_records_accumulated: the same checks, the same front door
+static int verify_records_entry(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch, size_t n_inputs,
+                                const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, const uint8_t* seed, int* results,
+                                uint8_t* status, int* path) {
     if (!ctx || !vk || !srs || !g_lagrange || !records || !results) return BZH_E_ARG;
     if (!n_inputs || n_inputs > BZH_RECORD_MAX_INPUTS || batch > bzh::kVerifyRecordsMaxBatch) return BZH_E_ARG;
     bzh::KeyRuntime::Call in_flight(vk->rt);
@@ -570,9 +581,14 @@ int bzh_verify_records_device(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* s
     BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     bzh::Arena& arena = vk->rt.arena_for(ctx->serial, ctx->device);
     return bzh::with_pasta_curve(key.curve, [&](auto c) {
-        return bzh::verify_records_t<decltype(c)>(ctx, key, srs, g_lagrange, arena, batch, n_inputs, records, record_stride, g0_u_w, results,
-                                                  status);
+        return bzh::verify_records_t<decltype(c)>(ctx, key, srs, g_lagrange, arena, batch, n_inputs, records, record_stride, g0_u_w, seed,
+                                                  results, status, path);
     });
+}
+
+int bzh_verify_records_device(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch, size_t n_inputs,
+                              const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, int* results, uint8_t* status) {
+    return verify_records_entry(ctx, vk, srs, g_lagrange, batch, n_inputs, records, record_stride, g0_u_w, nullptr, results, status, nullptr);
 }
 
 // rng_stride == 0: `rng` holds batch x 32-byte seeds (bzh_prove_batch_seeded)
@@ -855,6 +871,29 @@ int bzh_rng_expand(const uint8_t* seed, uint64_t first_draw, size_t draws, uint8
         memcpy(out + i * 64, blk, 64);
     }
     return BZH_OK;
+}
+
+int bzh_accumulation_weights(int curve, const uint8_t* seed, size_t batch, uint64_t* out) {
+    if (!seed || (!out && batch) || (curve != bzh::VestaCurve::id && curve != bzh::PallasCurve::id)) return BZH_E_ARG;
+    return bzh::with_pasta_curve(curve, [&](auto c) {
+        bzh::accumulation_weights_t<typename bzh::CurveInfo<decltype(c)>::SF>(seed, batch, BZH_FORM_CANONICAL, out);
+        return BZH_OK;
+    });
+}
+
+int bzh_verify_records_accumulated(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch,
+                                   size_t n_inputs, const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, const uint8_t* seed,
+                                   int* results, uint8_t* status, int* path) {
+    if (!seed) return BZH_E_ARG;
+    return verify_records_entry(ctx, vk, srs, g_lagrange, batch, n_inputs, records, record_stride, g0_u_w, seed, results, status, path);
+}
+
+int bzh_verify_batch_vk_accumulated(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch,
+                                    const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
+                                    const size_t* proof_lens, const uint64_t* g0_u_w, const uint8_t* seed, int* results, int* path) {
+    if (!seed) return BZH_E_ARG;
+    return verify_batch_vk_entry(ctx, vk, srs, g_lagrange, BZH_VERIFY_PASS_DEVICE, batch, instances, instance_rows, proofs, proof_stride,
+                                 proof_lens, g0_u_w, seed, results, path);
 }
 
 }  // extern "C"

@@ -377,17 +377,39 @@ static int verify_pass_enqueue_t(bzh_ctx* ctx, const KeyShape& key, Arena& arena
     return BZH_OK;
 }
 
+// The accumulation weights of a batch (bzh_accumulation_weights): w_b = draw b of bzh_rng_expand(seed, ..), 64 bytes, reduced as
+// Field::random reduces them (from_bytes_wide); out: batch x 4 limbs in `form`
+template <class SF>
+static void accumulation_weights_t(const uint8_t* seed, size_t batch, int form, uint64_t* out) {
+    uint32_t key[8], blk[16];
+    memcpy(key, seed, 32);
+    for (size_t b = 0; b < batch; b++) {
+        chacha20_block(key, b, blk);
+        fe_to_u64<SF>(out + 4 * b, h_from_u512<SF>(reinterpret_cast<const uint8_t*>(blk)), form);
+    }
+}
+// The accumulated ending of a device pass (bzh_verify_records_accumulated, bzh_verify_batch_vk_accumulated): ONE opening check for
+// the batch, every proof the pass rejected -- its reject byte folds the pre-reject byte in -- excluded with weight 0; the verdict
+// byte lands at d_ok.  skip: the host already knows that every record is refused, and no MSM is launched.
+static int verify_pass_accumulated(bzh_ctx* ctx, const bzh_bases* srs, size_t batch, const VerifyPassSides& s, const uint32_t* d_weights,
+                                   bool skip, uint8_t* d_ok) {
+    if (skip) return BZH_OK;
+    return ipa_check_accumulated_device(ctx, srs, batch, s.nl_cap, s.d_lc_pts, s.d_lc_scal, s.d_cu, d_weights, s.d_reject, d_ok);
+}
+
 // Front door of bzh_verify_batch / bzh_verify_batch_vk(_with) under BZH_VERIFY_PASS_DEVICE: the instance commitments through the
 // host (instance_commitments), the proofs staged on the host -- a proof whose length is not the key's is rejected here and its row
 // is zero-filled -- and, after the pass, the two sums per proof compared on the host.
+// With a seed (bzh_verify_batch_vk_accumulated) the weights go up behind the proofs and the pass ends in the accumulated check; if
+// that does not accept, the per-proof ending runs on the same operands and *path = 1.
 template <class C>
 static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* srs, const bzh_bases* g_lagrange, Arena& arena,
                                  size_t batch, const uint64_t* instances, size_t inst_rows, const uint8_t* proofs, size_t proof_stride,
-                                 const size_t* proof_lens, const uint64_t* g0_u_w, int* results) {
+                                 const size_t* proof_lens, const uint64_t* g0_u_w, const uint8_t* seed, int* results, int* path) {
     if (!verify_pass_has_program(ctx, key)) return BZH_E_RANGE;
     arena.reset();
     ColumnCommitter<C> pv(ctx, key, arena);
-    const size_t B = batch, plen = key.vprog.proof_len, pstride = verify_pass_row_stride(key);
+    const size_t B = batch, plen = key.vprog.proof_len, pstride = verify_pass_row_stride(key), weight_bytes = seed ? B * 32 : 0;
     VerifyTrace tr;
     std::vector<uint64_t> inst_xy;
     BZH_TRY(instance_commitments<C>(pv, key, srs, g_lagrange, B, instances, inst_rows, g0_u_w, inst_xy));
@@ -398,11 +420,11 @@ static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_ba
     std::vector<uint8_t> pre8((B + 15) & ~(size_t)15, 0);
     for (size_t b = 0; b < B; b++) pre8[b] = proof_lens[b] != plen ? 1 : 0;
     BZH_TRY(vd_put(ctx, arena, pre8.data(), pre8.size(), &d_pre));
-    uint8_t* d_rows = (uint8_t*)arena.alloc(B * pstride + 16);
+    uint8_t* d_rows = (uint8_t*)arena.alloc(B * pstride + weight_bytes + 16);
     if (!d_rows) return BZH_E_OOM;
-    {   // the proofs: one upload
+    {   // the proofs, and behind them the accumulation weights (Montgomery) when there is a seed: one upload
         char* slot = nullptr;
-        BZH_TRY(h2d_stage(ctx, B * pstride, &slot));
+        BZH_TRY(h2d_stage(ctx, B * pstride + weight_bytes, &slot));
         for (size_t b = 0; b < B; b++) {
             char* dst = slot + b * pstride;
             if (pre8[b]) {
@@ -412,17 +434,41 @@ static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_ba
                 if (pstride > plen) memset(dst + plen, 0, pstride - plen);
             }
         }
-        BZH_TRY(h2d_commit(ctx, d_rows, slot, B * pstride));
+        if (seed) accumulation_weights_t<typename CurveInfo<C>::SF>(seed, B, BZH_FORM_MONTGOMERY, (uint64_t*)(slot + B * pstride));
+        BZH_TRY(h2d_commit(ctx, d_rows, slot, B * pstride + weight_bytes));
     }
     VerifyPassFront front;
     front.d_rows = d_rows, front.d_pre = (const uint8_t*)d_pre, front.d_inst_xy = d_inst_xy, front.d_srs_xy = d_srs_xy;
-    return verify_pass_enqueue_t<C>(ctx, key, arena, B, front, tr, [&](const VerifyPassSides& s) -> int {
+    // today's ending: the pass's reject bytes, and the two sums of every opening compared on the host
+    auto per_proof = [&](const VerifyPassSides& s, bool pts_montgomery) -> int {
         std::vector<uint8_t> rej(pre8.size(), 1);
         BZH_TRY(d2h_async(ctx, rej.data(), s.d_reject, rej.size()));
         std::vector<int> ok(B, 0);
-        BZH_TRY(ipa_check_batch_device(ctx, srs, B, s.nl_cap, s.d_lc_pts, s.d_lc_scal, s.d_cu, ok.data()));
+        BZH_TRY(ipa_check_batch_device(ctx, srs, B, s.nl_cap, s.d_lc_pts, s.d_lc_scal, s.d_cu, ok.data(), pts_montgomery));
         for (size_t b = 0; b < B; b++) results[b] = (ok[b] && !rej[b]) ? 1 : 0;
         return BZH_OK;
+    };
+    if (!seed) return verify_pass_enqueue_t<C>(ctx, key, arena, B, front, tr, [&](const VerifyPassSides& s) -> int { return per_proof(s, false); });
+    uint8_t* d_ok = (uint8_t*)arena.alloc(16);
+    if (!d_ok) return BZH_E_OOM;
+    return verify_pass_enqueue_t<C>(ctx, key, arena, B, front, tr, [&](const VerifyPassSides& s) -> int {
+        bool skip = true;   // a wrong length is all the host knows of a proof: when it refuses them all, no MSM is launched
+        for (size_t b = 0; b < B; b++) skip = skip && pre8[b] != 0;
+        BZH_TRY(verify_pass_accumulated(ctx, srs, B, s, (const uint32_t*)(d_rows + B * pstride), skip, d_ok));
+        std::vector<uint8_t> rej(pre8.size(), 1);
+        uint8_t okb[16] = {0};
+        BZH_TRY(d2h_async(ctx, rej.data(), s.d_reject, rej.size()));
+        if (!skip) BZH_TRY(d2h_async(ctx, okb, d_ok, 16));
+        BZH_TRY(d2h_finish(ctx));   // the call's one wait when the batch is accepted
+        if (path) *path = 0;
+        if (skip || okb[0]) {
+            for (size_t b = 0; b < B; b++) results[b] = rej[b] ? 0 : 1;
+            return BZH_OK;
+        }
+        // not accepted: which proof fails is the per-proof ending's to say, on the same operands (the left sides' points are in
+        // Montgomery form already and are not converted again)
+        if (path) *path = 1;
+        return per_proof(s, true);
     });
 }
 
@@ -435,14 +481,15 @@ static int verify_batch_device_t(bzh_ctx* ctx, const KeyShape& key, const bzh_ba
 constexpr size_t kVerifyRecordsMaxBatch = 4096;   // bzh_verify_batch's own limit: what the pass's launches are exercised up to
 template <class C>
 static int verify_records_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* srs, const bzh_bases* g_lagrange, Arena& arena, size_t batch,
-                            size_t n_inputs, const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, int* results,
-                            uint8_t* status) {
+                            size_t n_inputs, const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, const uint8_t* seed,
+                            int* results, uint8_t* status, int* path) {
     if (!verify_pass_has_program(ctx, key)) return BZH_E_RANGE;
     arena.reset();
     const size_t B = batch, Bpad = (B + 15) & ~(size_t)15, plen = key.vprog.proof_len, pstride = verify_pass_row_stride(key);
     const size_t rstride = (record_stride + 15) & ~(size_t)15, given_bytes = g0_u_w ? 3 * 64 : 0, out_bytes = 2 * Bpad + 16;
+    const size_t weight_bytes = seed ? B * 32 : 0;   // bzh_verify_records_accumulated: the weights (Montgomery) behind the records
     VerifyTrace tr;
-    uint8_t* d_records = (uint8_t*)arena.alloc(B * rstride + given_bytes);
+    uint8_t* d_records = (uint8_t*)arena.alloc(B * rstride + given_bytes + weight_bytes);
     uint8_t* d_rows = (uint8_t*)arena.alloc(B * pstride + 16);
     uint8_t* d_pre = (uint8_t*)arena.alloc(Bpad);
     uint32_t* d_inst = (uint32_t*)arena.alloc(B * n_inputs * 32);
@@ -451,15 +498,17 @@ static int verify_records_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* 
     uint32_t* d_srs_xy = (uint32_t*)arena.alloc(3 * 64 + 64);
     uint8_t* d_out = (uint8_t*)arena.alloc(out_bytes);
     if (!d_records || !d_rows || !d_pre || !d_inst || !d_jac || !d_inst_xy || !d_srs_xy || !d_out) return BZH_E_OOM;
-    {   // the records: one upload
+    {   // the records, G_0 U W and the weights behind them when given: one slot of all three, one upload
         char* slot = nullptr;
-        BZH_TRY(h2d_stage(ctx, B * rstride + given_bytes, &slot));
+        BZH_TRY(h2d_stage(ctx, B * rstride + given_bytes + weight_bytes, &slot));
         for (size_t b = 0; b < B; b++) {
             memcpy(slot + b * rstride, records + b * record_stride, record_stride);
             if (rstride > record_stride) memset(slot + b * rstride + record_stride, 0, rstride - record_stride);
         }
         if (g0_u_w) memcpy(slot + B * rstride, g0_u_w, 3 * 64);
-        BZH_TRY(h2d_commit(ctx, d_records, slot, B * rstride + given_bytes));
+        if (seed)
+            accumulation_weights_t<typename CurveInfo<C>::SF>(seed, B, BZH_FORM_MONTGOMERY, (uint64_t*)(slot + B * rstride + given_bytes));
+        BZH_TRY(h2d_commit(ctx, d_records, slot, B * rstride + given_bytes + weight_bytes));
     }
     VerifyRecordsArgs ra;
     ra.batch = B, ra.rstride = rstride, ra.pstride = pstride, ra.n_inputs = (uint32_t)n_inputs, ra.proof_len = (uint32_t)plen;
@@ -475,9 +524,10 @@ static int verify_records_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* 
     tr.mark("instance commitments");
     VerifyPassFront front;
     front.d_rows = d_rows, front.d_pre = d_pre, front.d_inst_xy = d_inst_xy, front.d_srs_xy = d_srs_xy;
-    return verify_pass_enqueue_t<C>(ctx, key, arena, B, front, tr, [&](const VerifyPassSides& s) -> int {
+    // today's ending: the two sums of every opening, compared on the device, one read-back
+    auto per_proof = [&](const VerifyPassSides& s, bool pts_montgomery) -> int {
         const uint32_t* d_sums = nullptr;
-        BZH_TRY(ipa_check_sums_device(ctx, srs, B, s.nl_cap, s.d_lc_pts, s.d_lc_scal, s.d_cu, &d_sums));
+        BZH_TRY(ipa_check_sums_device(ctx, srs, B, s.nl_cap, s.d_lc_pts, s.d_lc_scal, s.d_cu, &d_sums, pts_montgomery));
         BZH_TRY(verify_records_result(ctx, C::id, d_sums, B, d_pre, s.d_reject, d_out, Bpad));
         std::vector<uint8_t> out(out_bytes, 0);
         BZH_TRY(d2h_async(ctx, out.data(), d_out, out_bytes));
@@ -491,5 +541,35 @@ static int verify_records_t(bzh_ctx* ctx, const KeyShape& key, const bzh_bases* 
             if (status) status[b] = out[Bpad + b];
         }
         return BZH_OK;
+    };
+    if (!seed) return verify_pass_enqueue_t<C>(ctx, key, arena, B, front, tr, [&](const VerifyPassSides& s) -> int { return per_proof(s, false); });
+    return verify_pass_enqueue_t<C>(ctx, key, arena, B, front, tr, [&](const VerifyPassSides& s) -> int {
+        // what k_vr_parse decides, on the host's copy of the records: when it refuses them all, no MSM is launched
+        bool skip = true;
+        for (size_t b = 0; b < B && skip; b++)
+            skip = vr_record_refused_host<typename CurveInfo<C>::SF>(records + b * record_stride, (uint32_t)plen, (uint32_t)n_inputs);
+        uint8_t* d_ok = d_out + 2 * Bpad + 8;   // behind the three G_0 U W bytes
+        BZH_TRY(verify_pass_accumulated(ctx, srs, B, s, (const uint32_t*)(d_records + B * rstride + given_bytes), skip, d_ok));
+        std::vector<uint8_t> rej(Bpad, 1), pre(Bpad, 1);
+        uint8_t tail[16] = {0};
+        BZH_TRY(d2h_async(ctx, rej.data(), s.d_reject, Bpad));
+        BZH_TRY(d2h_async(ctx, pre.data(), d_pre, Bpad));
+        BZH_TRY(d2h_async(ctx, tail, d_out + 2 * Bpad, 16));
+        BZH_TRY(d2h_finish(ctx));   // the call's one wait when the batch is accepted
+        if (tail[0] | tail[1] | tail[2]) {
+            ctx->last_error = "bzh_verify_records_accumulated: g0_u_w are not G_0, U, W of srs";
+            return BZH_E_ARG;
+        }
+        if (path) *path = 0;
+        if (skip || tail[8]) {
+            for (size_t b = 0; b < B; b++) {
+                results[b] = rej[b] ? 0 : 1;
+                if (status) status[b] = pre[b] ? 1 : 0;
+            }
+            return BZH_OK;
+        }
+        // not accepted: the per-proof ending on the same operands says which record fails (the points are in Montgomery form already)
+        if (path) *path = 1;
+        return per_proof(s, true);
     });
 }

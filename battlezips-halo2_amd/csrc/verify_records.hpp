@@ -55,17 +55,34 @@ BZH_HD bool vr_below(const Fe<P>& x) {
     return fe_lt_p(t);
 }
 
+// what refuses a record before verification, in two pieces: the header against what the call expects, and one public input
+// against the record format's modulus and the key's scalar field
+BZH_HD bool vr_header_refused(const uint8_t* rec, uint32_t proof_len, uint32_t n_inputs) {
+    const uint32_t w0 = vr_word(rec, 0), w1 = vr_word(rec, 1), w3 = vr_word(rec, 3);
+    return w0 != proof_len || (w1 & 0xffu) != n_inputs || (w1 >> 16) != 0 || w3 != 0;
+}
+template <class SF>
+BZH_HD bool vr_input_refused(const Fe<SF>& v) {
+    return !vr_below<FpParams>(v) || !fe_lt_p(v);
+}
+// the same decision for a whole record on the host (the accumulated call: a batch refused to the last record launches no MSM)
+template <class SF>
+inline bool vr_record_refused_host(const uint8_t* rec, uint32_t proof_len, uint32_t n_inputs) {
+    bool refuse = vr_header_refused(rec, proof_len, n_inputs);
+    for (uint32_t j = 0; j < n_inputs; j++) refuse = refuse || vr_input_refused<SF>(norm_load<SF>(rec + 16 + 32 * (size_t)j));
+    return refuse;
+}
+
 // a: VerifyRecordsArgs (csrc/ctx.hpp); SF: the key's scalar field
 template <class SF, class A>
 BZH_HD void vr_parse_lane(const A& a, size_t b, uint32_t i) {
     const uint8_t* rec = a.d_records + b * a.rstride;
-    const uint32_t w0 = vr_word(rec, 0), w1 = vr_word(rec, 1), w3 = vr_word(rec, 3);
-    bool refuse = w0 != a.proof_len || (w1 & 0xffu) != a.n_inputs || (w1 >> 16) != 0 || w3 != 0;
+    bool refuse = vr_header_refused(rec, a.proof_len, a.n_inputs);
     Fe<SF> mine = fe_zero<SF>();
 #pragma unroll 1
     for (uint32_t j = 0; j < a.n_inputs; j++) {
         const Fe<SF> v = norm_load<SF>(rec + 16 + 32 * (size_t)j);
-        refuse = refuse || !vr_below<FpParams>(v) || !fe_lt_p(v);
+        refuse = refuse || vr_input_refused<SF>(v);
         mine = fe_csel(j == i, v, mine);
     }
     norm_store<SF>(a.d_inst + (b * a.n_inputs + i) * 8, fe_to_mont(fe_csel(!refuse, mine, fe_zero<SF>())));

@@ -805,6 +805,16 @@ int bzh_prove_batch_seeded(bzh_ctx* ctx, bzh_pk* pk, size_t batch, const uint64_
                            size_t instance_rows, const uint8_t* seeds, uint8_t* proofs, size_t proof_stride, size_t* proof_lens);
 /* host: draws [first_draw, first_draw + draws) of the stream of `seed`, 64 bytes each, into out */
 int bzh_rng_expand(const uint8_t* seed, uint64_t first_draw, size_t draws, uint8_t* out);
+/* host, no ctx, no device: the weights of an accumulated batch verification (bzh_verify_records_accumulated,
+ * bzh_verify_batch_vk_accumulated, bzh_ipa_check_accumulated).  out[b] (4 canonical limbs) = draw b of bzh_rng_expand(seed, b, 1, ..),
+ * 64 bytes, reduced into the scalar field of `curve` (BZH_CURVE_VESTA / BZH_CURVE_PALLAS) exactly as bzh_random_field reduces a
+ * 64-byte draw (from_bytes_wide).  BZH_E_ARG: a NULL seed, a NULL out with batch != 0, another curve.
+ * SECURITY: the weights of a batch are a function of `seed`; the seed MUST come from a cryptographically secure generator
+ * (getrandom(2), OsRng, os.urandom), fresh per call and drawn AFTER the records of the batch are fixed.  With a seed the proofs'
+ * author can predict, invalid proofs can be made to cancel each other and the batch is accepted.  With an unpredictable seed a batch
+ * that contains an invalid included proof passes the accumulated check with probability at most 1/|F|.  Fixed seeds are for tests
+ * and benchmarks only. */
+int bzh_accumulation_weights(int curve, const uint8_t seed[32], size_t batch, uint64_t* out);
 
 /* THE DEVICE-RESIDENT BATCH PROVER: create_proof as ONE call that runs the five leaves above -- the witness commitments, the grand
  * products, the vanishing argument, the evaluations and the multiopen with its opening -- on one device transcript batch inside the
@@ -1168,6 +1178,41 @@ int bzh_record_from_json(const char* text, size_t text_len, uint32_t kind, uint3
  * no device program, as bzh_verify_batch_vk_with under BZH_VERIFY_PASS_DEVICE. */
 int bzh_verify_records_device(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch, size_t n_inputs,
                               const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, int* results, uint8_t* status);
+
+/* ---- a batch verified with ONE accumulated opening check ------------------------------------------------------------------------
+ * All B opening checks of a batch are linear equations in group elements, so a random linear combination of them is one equation:
+ *     sum_b w_b * ( sum_i lc_scal[b][i] * lc_pts[b][i] )  ==  < sum_b w_b * c_b * s(u_b) , G >
+ * The right side is ONE n-term MSM against the SRS on a vector a field kernel accumulates ((n + 2) * 32 bytes instead of
+ * B * (n + 2) * 32), the left side ONE Pippenger MSM over the B * nl points of the batch.  The weights are
+ * bzh_accumulation_weights(curve, seed, B, ..): read its SECURITY paragraph -- `seed` is 32 bytes of a cryptographically secure
+ * generator, fresh per call, drawn after the records are fixed.
+ * bzh_verify_records_accumulated takes what bzh_verify_records_device takes, bzh_verify_batch_vk_accumulated what
+ * bzh_verify_batch_vk_with(.., BZH_VERIFY_PASS_DEVICE, ..) takes, and `seed`; everything up to the opening check is that call's,
+ * launch for launch.  Then:
+ *   - a record refused before verification, or a proof the pass rejects (a point off the curve, a non-canonical scalar, ..), is
+ *     EXCLUDED: weight 0 on both sides.  It is results[b] = 0 and does not make the batch fail.
+ *   - the accumulated check runs and its one byte comes back with the reject bytes: the call's one wait.  Accepted: results[b] = 1
+ *     for every included record, *path = 0.
+ *   - not accepted: the per-proof ending of bzh_verify_records_device (bzh_verify_batch_vk_with) runs on the same device operands
+ *     and says exactly which record fails; *path = 1.  A failing batch therefore costs BOTH checks.
+ *   - a batch in which every record is refused on the host's reading (header, inputs, proof length) launches no MSM; *path = 0.
+ * results[] and status[] equal bzh_verify_records_device's (results[] bzh_verify_batch_vk_with's) on the same input, for every
+ * seed -- up to the 1/|F| above.  path may be NULL.  Argument refusals, the 4096 limit, batch == 0 and BZH_E_RANGE are that
+ * call's; in addition a NULL seed is BZH_E_ARG.  Nothing selects these calls.  Measured: DESIGN.md section 7,
+ * tools/ubench_verify_accumulated.py. */
+int bzh_verify_records_accumulated(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch,
+                                   size_t n_inputs, const uint8_t* records, size_t record_stride, const uint64_t* g0_u_w, const uint8_t seed[32],
+                                   int* results, uint8_t* status, int* path);
+int bzh_verify_batch_vk_accumulated(bzh_ctx* ctx, const bzh_vk* vk, const bzh_bases* srs, const bzh_bases* g_lagrange, size_t batch,
+                                    const uint64_t* instances, size_t instance_rows, const uint8_t* proofs, size_t proof_stride,
+                                    const size_t* proof_lens, const uint64_t* g0_u_w, const uint8_t seed[32], int* results, int* path);
+/* the accumulated check alone, operands in host memory: lc_pts batch x nl affine canonical points ((0,0) = padding, never added),
+ * lc_scal batch x nl, cu batch x (k + 1) (c, u_0 .. u_(k-1)) and weights batch x 4 limbs, all canonical; exclude: batch bytes or
+ * NULL, a non-zero byte gives the opening weight 0; bases: the n + 2 points (g | u | w).  *ok = 1 when
+ * sum_b w'_b (sum_i lc_scal[b][i] lc_pts[b][i]) = < sum_b w'_b c_b s(u_b), g >.  BZH_E_ARG: a NULL pointer but exclude, batch == 0
+ * or > 4096, nl == 0 or > 65536, n not a power of two, a table of another device. */
+int bzh_ipa_check_accumulated(bzh_ctx* ctx, const bzh_bases* bases, size_t batch, size_t nl, const uint64_t* lc_pts, const uint64_t* lc_scal,
+                              const uint64_t* cu, const uint64_t* weights, const uint8_t* exclude, int* ok);
 
 #ifdef __cplusplus
 }
