@@ -94,8 +94,14 @@ def generators_device(ctx: Context, first: int, count: int, form: int = FORM_CAN
 
 
 def group_ifft(ctx: Context, g: np.ndarray) -> np.ndarray:
+    """The inverse group FFT of n = 2^k Vesta points (bzh_group_ifft): (n, 8) uint64 canonical limbs x || y in and out, (0, 0) the
+    identity.  g is left as it is."""
     g = np.ascontiguousarray(g, dtype=np.uint64)
+    if g.ndim != 2 or g.shape[1] != 8:
+        raise ValueError("group_ifft: g is an (n, 8) array of canonical limbs, got shape %r" % (g.shape,))
     n = g.shape[0]
+    if n < 1 or n & (n - 1):
+        raise ValueError("group_ifft: the number of points is a power of two, got %d" % n)
     k = n.bit_length() - 1
     out = np.zeros((n, 8), dtype=np.uint64)
     ctx._check(_bind().bzh_group_ifft(ctx.handle, CURVE_VESTA, _VP(g.ctypes.data), k, _VP(out.ctypes.data)), "bzh_group_ifft")
