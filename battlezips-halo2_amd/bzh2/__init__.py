@@ -1313,6 +1313,43 @@ def _ctx_vm2_eval(self, field: int, ops, columns, consts, size: int, batch: int 
 
 Context.vm2_eval = _ctx_vm2_eval
 
+EXPORTS += ["bzh_vm2_eval_cosets", "bzh_pk_workspace_select", "bzh_pk_workspace_selected", "bzh_workspace_plan", "bzh_workspace_plan_items", "bzh_pk_workspace_peak"]
+
+
+def _ctx_vm2_eval_cosets(self, field: int, ops, columns, column_extended, consts, log_n: int, batch: int = 1, nlds: int = 0,
+                         column_strides=None, const_stride: int = 0, form: int = FORM_CANONICAL, mem: int = MEM_HOST, out=None,
+                         nconsts: int | None = None, out_size: int | None = None):
+    """Run a VM v2 program coset by coset (bzh_vm2_eval_cosets) over `batch` vectors of 8 * 2^log_n rows and return register r0 of
+    every row, (batch * 8 * 2^log_n, 4) uint64 -- what vm2_eval returns over the same data.  column_extended[c] true: column c as
+    for vm2_eval, 8 n rows per vector; false: eight blocks of n rows per vector, block j = rows j, j + 8, ... (coset j), vector v
+    of block j at j * batch * stride + v * stride elements (a shared column: at j * n).  The rest as for vm2_eval; out_size
+    (default 8 * 2^log_n) is what the call is told `out` holds per vector."""
+    L = load()
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    L.bzh_vm2_eval_cosets.argtypes = [vp, ctypes.c_int, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_char_p, sz, vp, sz, sz,
+                                      ctypes.c_uint, sz, sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
+    ops = np.ascontiguousarray(ops, dtype=VM2_OP_DTYPE)
+    size = 8 << log_n
+    if mem == MEM_HOST:
+        columns = [_as_elems(c) for c in columns]
+        if out is None:
+            out = np.zeros((batch * size, 4), dtype=np.uint64)
+    ncols = len(columns)
+    ptrs = (vp * max(ncols, 1))(*[c.ctypes.data if mem == MEM_HOST else int(c) for c in columns])
+    strides = (sz * max(ncols, 1))(*(column_strides if column_strides is not None else [0] * ncols))
+    flags = bytes(1 if f else 0 for f in column_extended) or b"\0"
+    cv = _as_elems(consts) if len(consts) else np.zeros((1, 4), dtype=np.uint64)
+    if nconsts is None:
+        nconsts = (const_stride or cv.shape[0]) if len(consts) else 0
+    out_ptr = (out.ctypes.data if isinstance(out, np.ndarray) else int(out))
+    rc = L.bzh_vm2_eval_cosets(self.handle, field, _vp(ops), len(ops), ptrs, strides, flags, ncols, _vp(cv), nconsts, const_stride, log_n,
+                               size if out_size is None else out_size, batch, nlds, form, mem, vp(out_ptr))
+    self._check(rc, "bzh_vm2_eval_cosets")
+    return out
+
+
+Context.vm2_eval_cosets = _ctx_vm2_eval_cosets
+
 
 # ---- multiopen / lookup helpers ---------------------------------------------------------------------
 EXPORTS += ["bzh_kate_division", "bzh_kate_division_batch", "bzh_permute_expression_pair"]

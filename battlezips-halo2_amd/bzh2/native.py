@@ -92,6 +92,32 @@ def accumulation_weights(curve: int, seed: bytes, batch: int) -> list:
 
 QUOTIENT_INTERPRETER, QUOTIENT_BUILTIN, QUOTIENT_MODULE = 0, 1, 2
 LOOKUP_HOST, LOOKUP_DEVICE = 0, 1
+WORKSPACE_EXTENDED, WORKSPACE_COSETWISE = 0, 1
+
+
+class _WorkspaceItems(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("n", "extended", "columns", "column_bytes", "cosets_bytes", "cosets_extended_bytes",
+                                                      "witness_bytes", "quotient_bytes", "tail_bytes", "staging_bytes", "total_bytes")]
+
+
+def workspace_plan(curve: int, circuit_blob: bytes, batch: int, mode: int = WORKSPACE_EXTENDED) -> int:
+    """arena bytes one prove call of `batch` proofs takes in `mode` (bzh_workspace_plan; host only, needs no GPU)"""
+    L = load()
+    L.bzh_workspace_plan.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                     ctypes.POINTER(ctypes.c_size_t)]
+    blob, out = bytes(circuit_blob), ctypes.c_size_t()
+    _check(L.bzh_workspace_plan(curve, blob, len(blob), batch, mode, ctypes.byref(out)), "bzh_workspace_plan")
+    return out.value
+
+
+def workspace_plan_items(curve: int, circuit_blob: bytes, batch: int, mode: int = WORKSPACE_EXTENDED) -> dict:
+    """the items bzh_workspace_plan sums (bzh_workspace_plan_items: the fields of bzh_workspace_items, include/bzh2.h)"""
+    L = load()
+    L.bzh_workspace_plan_items.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                           ctypes.POINTER(_WorkspaceItems)]
+    blob, it = bytes(circuit_blob), _WorkspaceItems()
+    _check(L.bzh_workspace_plan_items(curve, blob, len(blob), batch, mode, ctypes.byref(it)), "bzh_workspace_plan_items")
+    return {name: int(getattr(it, name)) for name, _ in _WorkspaceItems._fields_}
 VERIFY_POINTS_HOST, VERIFY_POINTS_DEVICE = 0, 1
 VERIFY_PASS_HOST, VERIFY_PASS_DEVICE = 0, 1
 
@@ -267,6 +293,35 @@ class NativeProvingKey:
         L = _bind()
         L.bzh_pk_lookup_select.argtypes = [_VP, ctypes.c_int]
         self.ctx._check(L.bzh_pk_lookup_select(self.handle, where), "bzh_pk_lookup_select")
+
+    # ---- where the quotient reads the per-proof columns -------------------------------------------------------
+    def workspace_selected(self) -> int:
+        """WORKSPACE_EXTENDED (every per-proof column on the whole extended coset; every new key's default) or
+        WORKSPACE_COSETWISE (n-sized buffers, the quotient coset by coset through the interpreter whatever quotient_select
+        says: include/bzh2.h)"""
+        L = _bind()
+        L.bzh_pk_workspace_selected.argtypes = [_VP, ctypes.POINTER(ctypes.c_int)]
+        w = ctypes.c_int()
+        self.ctx._check(L.bzh_pk_workspace_selected(self.handle, ctypes.byref(w)), "bzh_pk_workspace_selected")
+        return w.value
+
+    def workspace_select(self, mode: int):
+        L = _bind()
+        L.bzh_pk_workspace_select.argtypes = [_VP, ctypes.c_int]
+        self.ctx._check(L.bzh_pk_workspace_select(self.handle, mode), "bzh_pk_workspace_select")
+
+    def workspace_peak(self) -> int:
+        """the most arena bytes the key's last call held at once (bzh_pk_workspace_peak): what workspace_plan estimates"""
+        L = _bind()
+        L.bzh_pk_workspace_peak.argtypes = [_VP, ctypes.POINTER(ctypes.c_size_t)]
+        out = ctypes.c_size_t()
+        self.ctx._check(L.bzh_pk_workspace_peak(self.handle, ctypes.byref(out)), "bzh_pk_workspace_peak")
+        return out.value
+
+    def workspace_plan(self, batch: int, mode: int | None = None) -> int:
+        """arena bytes one prove call of `batch` proofs of this key's circuit takes (bzh2.workspace_plan), in `mode` or the
+        key's current mode"""
+        return workspace_plan(self.curve, self.blob, batch, self.workspace_selected() if mode is None else mode)
 
     # ---- where bzh_verify_batch decompresses the proofs' points ----------------------------------------------
     def verify_selected(self) -> int:

@@ -836,6 +836,85 @@ int bzh_vm2_eval(bzh_ctx* ctx, int field, const void* ops, size_t nops, const ui
     return BZH_OK;  // staging reuse by the next call is stream-ordered
 }
 
+// The same program coset by coset (k_expr_vm2_cosets): see include/bzh2.h for the layout of an n-sized column
+int bzh_vm2_eval_cosets(bzh_ctx* ctx, int field, const void* ops, size_t nops, const uint64_t* const* columns, const size_t* column_strides,
+                        const uint8_t* column_extended, size_t ncols, const uint64_t* consts, size_t nconsts, size_t const_stride,
+                        unsigned log_n, size_t out_size, size_t batch, int nlds, int form, int mem, uint64_t* out) {
+    BZH_POLY_PROLOGUE((field != BZH_FIELD_FP && field != BZH_FIELD_FQ) || !ops || !nops || nops > (size_t)INT32_MAX ||
+                      (!columns && ncols) || (!column_extended && ncols) || (!consts && nconsts) || !out || log_n > 27 || !batch ||
+                      batch > 65535 || nlds < 0 || (const_stride && const_stride < nconsts));
+    const size_t n = (size_t)1 << log_n, en = n * 8;
+    if (out_size != en) return BZH_E_ARG;
+    // 8-byte limbs in host memory; whole 32-byte elements in device memory (the kernels load and store them as 16-byte halves)
+    const uintptr_t align = mem == BZH_MEM_DEVICE ? 31 : 7;
+    uintptr_t all = (uintptr_t)out | (mem == BZH_MEM_HOST ? (uintptr_t)consts : 0);
+    for (size_t c = 0; c < ncols; c++) all |= (uintptr_t)columns[c];
+    if (all & align) return BZH_E_ARG;
+    if (mem == BZH_MEM_DEVICE && form != BZH_FORM_MONTGOMERY) return BZH_E_ARG;
+    const ExprOp2* prog = (const ExprOp2*)ops;
+    for (size_t i = 0; i < nops; i++) {
+        if (!vm2_op_valid(prog[i], ncols, nconsts, nlds)) return BZH_E_ARG;
+        // a rotation is a step on the extended domain: only a multiple of 8 stays on the lane's coset
+        if (prog[i].reads_a() && prog[i].a_kind == BZH_EXPR_COLUMN && prog[i].a_rot % 8) return BZH_E_ARG;
+        if (prog[i].reads_b() && prog[i].b_kind == BZH_EXPR_COLUMN && prog[i].b_rot % 8) return BZH_E_ARG;
+    }
+    // column c, vector v: an extended column at columns[c] + v * stride (8 n elements); an n-sized one as eight blocks, coset j's
+    // at columns[c] + j * block, block = batch * stride (or n when shared), vector v at + v * stride
+    std::vector<size_t> strides(ncols, 0), reps(ncols, 1), rows(ncols, 0), block(ncols, 0);
+    std::vector<uint32_t> shifts(ncols, 0);
+    size_t host_elems = 0;
+    for (size_t c = 0; c < ncols; c++) {
+        rows[c] = column_extended[c] ? en : n;
+        shifts[c] = column_extended[c] ? 0u : 3u;
+        strides[c] = (column_strides && batch > 1) ? column_strides[c] : 0;
+        if (strides[c] && strides[c] < rows[c]) return BZH_E_ARG;
+        reps[c] = strides[c] ? batch : 1;
+        block[c] = strides[c] ? batch * strides[c] : n;
+        host_elems += reps[c] * en;
+    }
+    const size_t nconst_total = const_stride ? const_stride * (batch - 1) + nconsts : nconsts;
+    Stager s{ctx, field, form};
+    if ((rc = s.begin(((mem == BZH_MEM_HOST ? host_elems + batch * en : 0) + nconst_total) * 32 + nops * sizeof(ExprOp2) +
+                      ncols * (8 * sizeof(void*) + sizeof(size_t) + 4 + 64 * 11) + 2048)))
+        return rc;
+    std::vector<const uint32_t*> ptrs(8 * ncols);   // [coset][column]
+    for (size_t c = 0; c < ncols; c++) {
+        const uint32_t* base = (const uint32_t*)columns[c];
+        if (mem == BZH_MEM_HOST) {   // staged densely: extended (reps, 8 n) | n-sized (8, reps, n)
+            uint32_t* d = s.carve(reps[c] * en * 32);
+            const size_t pieces = column_extended[c] ? 1 : 8;
+            for (size_t j = 0; j < pieces; j++)
+                for (size_t v = 0; v < reps[c]; v++)
+                    BZH_HIP_TRY(ctx, hipMemcpyAsync(d + (j * reps[c] + v) * rows[c] * 8, columns[c] + (j * block[c] + v * strides[c]) * 4,
+                                                    rows[c] * 32, hipMemcpyHostToDevice, ctx->stream));
+            if (form == BZH_FORM_CANONICAL && (rc = field_convert(ctx, field, d, reps[c] * en, 1))) return rc;
+            base = d;
+            if (strides[c]) strides[c] = rows[c];
+            block[c] = reps[c] * n;
+        }
+        for (size_t j = 0; j < 8; j++) ptrs[j * ncols + c] = column_extended[c] ? base : base + j * block[c] * 8;
+    }
+    uint32_t *d_consts = nullptr, *d_prog = s.carve(nops * sizeof(ExprOp2)), *d_ptrs[8], *d_strides = s.carve(ncols * sizeof(size_t) + 8),
+             *d_shifts = s.carve(ncols * 4 + 8);
+    for (size_t j = 0; j < 8; j++) d_ptrs[j] = s.carve(ncols * sizeof(void*) + 8);
+    if ((rc = s.in(consts, nconst_total, &d_consts))) return rc;
+    if ((rc = h2d_small(ctx, d_prog, ops, nops * sizeof(ExprOp2)))) return rc;
+    if (ncols) {
+        if ((rc = h2d_small(ctx, d_strides, strides.data(), ncols * sizeof(size_t)))) return rc;
+        if ((rc = h2d_small(ctx, d_shifts, shifts.data(), ncols * 4))) return rc;
+        for (size_t j = 0; j < 8; j++)
+            if ((rc = h2d_small(ctx, d_ptrs[j], ptrs.data() + j * ncols, ncols * sizeof(void*)))) return rc;
+    }
+    uint32_t* d_out = mem == BZH_MEM_HOST ? s.carve(batch * en * 32) : (uint32_t*)out;
+    const uint32_t* const* tables[8];
+    for (size_t j = 0; j < 8; j++) tables[j] = (const uint32_t* const*)d_ptrs[j];
+    rc = expr_eval2_cosets(ctx, field, d_prog, (int)nops, tables, (const size_t*)d_strides, d_shifts, d_consts, const_stride, log_n, batch,
+                           nlds, d_out, nullptr);
+    if (rc) return rc;
+    if (mem == BZH_MEM_HOST) return s.out(out, d_out, batch * en);
+    return BZH_OK;  // staging reuse by the next call is stream-ordered
+}
+
 int bzh_ipa_open_batch(bzh_ctx* ctx, const bzh_bases* bases, const uint64_t* polys, int form, int mem, size_t batch,
                        const uint64_t* blinds, const uint64_t* x3s, const uint8_t* rng, size_t rng_stride,
                        bzh_transcript* const* transcripts, uint64_t* out_v) {

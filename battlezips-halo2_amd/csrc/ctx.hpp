@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -351,6 +352,11 @@ int expr_eval(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint3
 // VM v2 (stack-discipline registers + LDS slot file): the prover's quotient evaluator
 int expr_eval2(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint32_t* const* d_cols, const size_t* d_strides,
                const uint32_t* d_consts, size_t const_stride, size_t size, size_t batch, int nlds, uint32_t* d_out);
+// ... coset by coset: eight launches of 2^log_n lanes fill the 8 * 2^log_n rows of d_out (k_expr_vm2_cosets).  d_cols_by_coset: 8
+// column pointer tables (host array of device pointers), d_shifts: 0 / 3 per column; refill(j), when set, runs before launch j
+int expr_eval2_cosets(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint32_t* const* const* d_cols_by_coset,
+                      const size_t* d_strides, const uint32_t* d_shifts, const uint32_t* d_consts, size_t const_stride, unsigned log_n,
+                      size_t batch, int nlds, uint32_t* d_out, const std::function<int(unsigned)>& refill);
 // ipa.hip
 int random_field(bzh_ctx* ctx, int field, const uint32_t* d_raw, size_t count, uint32_t* d_out);
 int ipa_open(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint64_t* blinds,

@@ -169,20 +169,30 @@ int expr_eval(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint3
 // quotient programs with column leaves in slots, csrc/quotient_compiler.hpp)
 static constexpr int kVm2Threads = 128, kVm2ThreadsSmall = 64;
 
-template <class P, int kRows>
-__global__ void __launch_bounds__(kRows) k_expr_vm2(const ExprOp2* __restrict__ prog, int nops, const uint32_t* const* __restrict__ cols,
-                                                           const size_t* __restrict__ strides, const uint32_t* __restrict__ consts,
-                                                           size_t const_stride, size_t size, uint32_t* __restrict__ out) {
+// The interpreter's body, shared by its two kernels.  kCosets = false: k_expr_vm2, one lane per row of a `size`-row domain.
+// kCosets = true: k_expr_vm2_cosets, one launch per coset j of the eight an 8 * size extended domain is made of -- lane r stands
+// for the extended row R = 8 r + j, rotations stay in extended-domain steps (multiples of 8: R + rot stays on coset j), and a leaf
+// of column c reads index ((R + rot) & (8 size - 1)) >> shifts[c]: shift 0 for a column that lies on the extended domain (the
+// key's), 3 for one of `size` elements that holds coset j alone (a per-proof column); the result goes to row R of the 8 size
+// output.  The shift is wave-uniform like the stride: one more scalar load per column leaf, no branch in the instruction loop.
+template <class P, int kRows, bool kCosets>
+__device__ __forceinline__ void expr_vm2_body(const ExprOp2* __restrict__ prog, int nops, const uint32_t* const* __restrict__ cols,
+                                              const size_t* __restrict__ strides, const uint32_t* __restrict__ shifts, unsigned coset,
+                                              const uint32_t* __restrict__ consts, size_t const_stride, size_t size,
+                                              uint32_t* __restrict__ out) {
     extern __shared__ uint4 vm2_lds[];
-    const size_t r = blockIdx.x * (size_t)kRows + threadIdx.x, v = blockIdx.y;
-    if (r >= size) return;   // size is a multiple of the block size for every domain the prover uses; no barriers below
-    const size_t mask = size - 1;
+    const size_t lane_row = blockIdx.x * (size_t)kRows + threadIdx.x, v = blockIdx.y;
+    if (lane_row >= size) return;   // size is a multiple of the block size for every domain the prover uses; no barriers below
+    const size_t out_size = kCosets ? size * 8 : size;
+    const size_t r = kCosets ? lane_row * 8 + coset : lane_row;
+    const size_t mask = out_size - 1;
     const uint32_t* cv = consts + v * const_stride * 8;
     const unsigned t = threadIdx.x;
     Fe<P> r0 = fe_zero<P>(), r1 = r0, r2 = r0, r3 = r0;
     auto leaf = [&](int kind, int idx, int rot) -> Fe<P> {
         if (kind == BZH_EXPR_COLUMN) {
-            const size_t row = (r + (size_t)(int64_t)rot) & mask;
+            size_t row = (r + (size_t)(int64_t)rot) & mask;
+            if constexpr (kCosets) row >>= shifts[idx];
             return fe_load<P>(cols[idx] + (v * strides[idx] + row) * 8);
         }
         if (kind == BZH_EXPR_CONST) return fe_load<P>(cv + (size_t)idx * 8);
@@ -226,7 +236,24 @@ __global__ void __launch_bounds__(kRows) k_expr_vm2(const ExprOp2* __restrict__ 
 #undef VM2_SL
 #undef VM2_SS
 #undef VM2_ARITH
-    fe_store(out + (v * size + r) * 8, r0);
+    fe_store(out + (v * out_size + r) * 8, r0);
+}
+
+template <class P, int kRows>
+__global__ void __launch_bounds__(kRows) k_expr_vm2(const ExprOp2* __restrict__ prog, int nops, const uint32_t* const* __restrict__ cols,
+                                                           const size_t* __restrict__ strides, const uint32_t* __restrict__ consts,
+                                                           size_t const_stride, size_t size, uint32_t* __restrict__ out) {
+    expr_vm2_body<P, kRows, false>(prog, nops, cols, strides, nullptr, 0, consts, const_stride, size, out);
+}
+
+// coset j of an 8 n extended domain: n lanes per vector, the result at rows 8 r + j of the vector's 8 n output
+template <class P, int kRows>
+__global__ void __launch_bounds__(kRows) k_expr_vm2_cosets(const ExprOp2* __restrict__ prog, int nops,
+                                                                  const uint32_t* const* __restrict__ cols,
+                                                                  const size_t* __restrict__ strides, const uint32_t* __restrict__ shifts,
+                                                                  unsigned coset, const uint32_t* __restrict__ consts, size_t const_stride,
+                                                                  size_t n, uint32_t* __restrict__ out) {
+    expr_vm2_body<P, kRows, true>(prog, nops, cols, strides, shifts, coset, consts, const_stride, n, out);
 }
 
 // program: ExprOp2[nops] on the device; result in r0; nlds LDS slots (32 bytes per thread each)
@@ -248,6 +275,37 @@ int expr_eval2(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint
         return BZH_OK;
     }));
     BZH_HIP_TRY(ctx, hipGetLastError());
+    return BZH_OK;
+}
+
+// The same program coset by coset: eight launches of n = 2^log_n lanes per vector fill the 8 n rows of d_out.  d_shifts: per
+// column 0 (8 n elements, read at the extended row) or 3 (n elements: the column on ONE coset).  d_cols_by_coset[j]: the column
+// pointer table of launch j (the n-sized columns differ from coset to coset when all eight are resident: bzh_vm2_eval_cosets),
+// or one table for all eight launches when `refill` rewrites the n-sized buffers before launch j (the prover).  The last
+// workgroup of a vector is partial when n is below the workgroup's rows.
+int expr_eval2_cosets(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint32_t* const* const* d_cols_by_coset,
+                      const size_t* d_strides, const uint32_t* d_shifts, const uint32_t* d_consts, size_t const_stride, unsigned log_n,
+                      size_t batch, int nlds, uint32_t* d_out, const std::function<int(unsigned)>& refill) {
+    const size_t n = (size_t)1 << log_n;
+    const size_t per_row = (size_t)std::max(nlds, 1) * 2 * sizeof(uint4);
+    const int threads = per_row * kVm2Threads <= 64 * 1024 ? kVm2Threads : kVm2ThreadsSmall;
+    const size_t lds = per_row * (size_t)threads;
+    if (lds > 64 * 1024) return BZH_E_RANGE;
+    const dim3 grid((unsigned)((n + (size_t)threads - 1) / (size_t)threads), (unsigned)batch), block((unsigned)threads);
+    const ExprOp2* p = (const ExprOp2*)d_prog;
+    for (unsigned j = 0; j < 8; j++) {
+        if (refill) BZH_TRY(refill(j));
+        ScopedTimer t(ctx, BZH_T_QUOTIENT);
+        const uint32_t* const* d_cols = d_cols_by_coset[j];
+        BZH_TRY(with_pasta_field(field, [&](auto f) {
+            if (threads == kVm2Threads)
+                hipLaunchKernelGGL((k_expr_vm2_cosets<decltype(f), kVm2Threads>), grid, block, lds, ctx->stream, p, nops, d_cols, d_strides, d_shifts, j, d_consts, const_stride, n, d_out);
+            else
+                hipLaunchKernelGGL((k_expr_vm2_cosets<decltype(f), kVm2ThreadsSmall>), grid, block, lds, ctx->stream, p, nops, d_cols, d_strides, d_shifts, j, d_consts, const_stride, n, d_out);
+            return BZH_OK;
+        }));
+        BZH_HIP_TRY(ctx, hipGetLastError());
+    }
     return BZH_OK;
 }
 

@@ -356,6 +356,56 @@ int bzh_pk_lookup_selected(bzh_pk* pk, int* where) {
     return BZH_OK;
 }
 
+int bzh_pk_workspace_select(bzh_pk* pk, int mode) {
+    if (!pk || (mode != BZH_WORKSPACE_EXTENDED && mode != BZH_WORKSPACE_COSETWISE)) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
+    pk->ws_select = mode;
+    return BZH_OK;
+}
+
+int bzh_pk_workspace_selected(bzh_pk* pk, int* mode) {
+    if (!pk) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(pk->rt.mu);
+    if (mode) *mode = pk->ws_select;
+    return BZH_OK;
+}
+
+int bzh_workspace_plan_items(int curve, const uint8_t* circuit, size_t circuit_len, size_t batch, int mode, bzh_workspace_items* items) {
+    if (!circuit || !items || !batch || batch > 65535 || (mode != BZH_WORKSPACE_EXTENDED && mode != BZH_WORKSPACE_COSETWISE))
+        return BZH_E_ARG;
+    bzh_pk pk;
+    BZH_TRY(bzh::with_pasta_curve(curve, [&](auto c) {
+        bzh::ParsedKey<typename bzh::CurveInfo<decltype(c)>::SF> po;
+        return bzh::pk_parse_t<decltype(c)>(circuit, circuit_len, pk, po, false);   // counts only: no quotient program is compiled
+    }));
+    const bzh::WorkspaceItems w = bzh::workspace_items(pk, batch, mode);
+    items->n = pk.n, items->extended = pk.en;
+    items->columns = (uint64_t)std::max(pk.na, 1) + (uint64_t)std::max(pk.ni, 1) + (uint64_t)std::max(pk.nsets + pk.nl, 1) + 2 * (uint64_t)pk.nl;
+    items->column_bytes = w.column_bytes;
+    items->cosets_bytes = w.cosets_bytes, items->cosets_extended_bytes = w.cosets_extended_bytes;
+    items->witness_bytes = w.witness_bytes, items->quotient_bytes = w.quotient_bytes, items->tail_bytes = w.tail_bytes;
+    items->staging_bytes = w.staging_bytes;
+    items->total_bytes = w.total_bytes;
+    return BZH_OK;
+}
+
+int bzh_pk_workspace_peak(const bzh_pk* pk, size_t* arena_bytes) {
+    if (!pk || !arena_bytes) return BZH_E_ARG;
+    std::lock_guard<std::mutex> lk(const_cast<bzh_pk*>(pk)->rt.mu);
+    size_t peak = 0;
+    for (auto& kv : pk->rt.arenas) peak = std::max(peak, kv.second->peak);
+    *arena_bytes = peak;
+    return BZH_OK;
+}
+
+int bzh_workspace_plan(int curve, const uint8_t* circuit, size_t circuit_len, size_t batch, int mode, size_t* arena_bytes) {
+    if (!arena_bytes) return BZH_E_ARG;
+    bzh_workspace_items items;
+    BZH_TRY(bzh_workspace_plan_items(curve, circuit, circuit_len, batch, mode, &items));
+    *arena_bytes = (size_t)items.total_bytes;
+    return BZH_OK;
+}
+
 int bzh_pk_verify_select(bzh_pk* pk, int where) {
     if (!pk || (where != BZH_VERIFY_POINTS_HOST && where != BZH_VERIFY_POINTS_DEVICE)) return BZH_E_ARG;
     std::lock_guard<std::mutex> lk(pk->rt.mu);

@@ -81,11 +81,18 @@ struct Prover : DeviceColumns<C> {
         t_last = now;
     }
 
+    // BZH_WORKSPACE_COSETWISE (bzh_pk_workspace_select, read once per call): no per-proof column is taken to the extended coset;
+    // the quotient is evaluated one coset of n points at a time out of n-sized buffers (cosetwise_setup, cosetwise_launch).
+    const bool cosetwise = [&] {
+        std::lock_guard<std::mutex> lk(pk.rt.mu);
+        return pk.ws_select == BZH_WORKSPACE_COSETWISE;
+    }();
     // The quotient's per-proof columns on the extended coset exist for the quotient alone.  When the builtin kernel's
     // unsaturated-limb flavour will run (decided once per call), coeff_to_extended writes them straight as fe29 planes
     // (9 words per element, ntt_store_out) and no saturated copy is ever made.
     const bool q29 = [&] {
         if constexpr (!fe29_supported<SF>()) return false;
+        if (cosetwise) return false;   // (that mode always runs the interpreter, in saturated limbs)
         std::lock_guard<std::mutex> lk(pk.rt.mu);
         return pk.q_ok && pk.q_builtin29 && pk.key29 && pk.q_select == BZH_QUOTIENT_BUILTIN && pk.en % 128 == 0 && pk.ek >= 12 &&
                pk.ek <= 27 /* 32-bit byte offsets into a plane (fe29_load_planes_g) */ && !getenv("BZH_QUOTIENT_V1");
@@ -345,6 +352,92 @@ struct Prover : DeviceColumns<C> {
         return expr_eval2(ctx, field, pa.prog, (int)pg.ops.size(), d_ptrs, d_strides, d_consts, nc, size, B, pg.nlds, d_out);
     }
 
+    // ---- the quotient coset by coset (BZH_WORKSPACE_COSETWISE) --------------------------------------------------------------
+    // The extended domain is eight cosets of the n-sized one: with w = eomega^8 and zeta_j = zeta eomega^j, extended point 8 r + j
+    // is zeta_j w^r.  A column's values on coset j are ONE n-point transform of its coefficients with coset shift zeta_j, and a
+    // rotation (a multiple of 8 extended steps) never leaves the coset.  So: per-proof coefficient forms -> n-sized buffers
+    // (carved once, refilled for every j: a copy and an in-place ntt_run per buffer), one k_expr_vm2_cosets launch per j for the
+    // whole batch, the key's own columns read where they lie at 8 r + j, h written at 8 r + j.  Always the interpreter.
+    struct CosetSeg {
+        const uint32_t* polys;   // `count` polynomials of n coefficients
+        uint32_t* buf;           // their values on the current coset
+        size_t count;
+    };
+    struct CosetWork {
+        std::vector<CosetSeg> segs;
+        Cols reg;
+        uint32_t* d_shifts = nullptr;
+    };
+    bool cosetwise_fits() const { return pk.q_ok && pk.ek == pk.k + 3 && !getenv("BZH_QUOTIENT_V1"); }
+    // carves the four buffers (their sizes are workspace_items': the plan and the carve cannot drift apart), builds the registry
+    // over them and uploads the per-column shifts.  lk_p: one (B, 2, n) block per lookup (lk_cols == 2), or one (B, 2 nl, n) block
+    int cosetwise_setup(const uint32_t* adv_p, const uint32_t* inst_p, const uint32_t* z_p, const std::vector<const uint32_t*>& lk_p,
+                        size_t lk_cols, CosetWork& cw) {
+        if (!cosetwise_fits()) {
+            ctx->last_error = "BZH_WORKSPACE_COSETWISE needs a circuit the quotient interpreter fits and an extended domain of 8 n";
+            return BZH_E_RANGE;
+        }
+        const WorkspaceItems wi = workspace_items(pk, B, BZH_WORKSPACE_COSETWISE);
+        uint32_t* b_adv = (uint32_t*)arena.alloc(wi.adv_bytes);
+        uint32_t* b_inst = (uint32_t*)arena.alloc(wi.inst_bytes);
+        uint32_t* b_z = (uint32_t*)arena.alloc(wi.z_bytes);
+        uint32_t* b_lk = nl ? (uint32_t*)arena.alloc(wi.lk_bytes) : nullptr;
+        if (!b_adv || !b_inst || !b_z || (nl && !b_lk)) return BZH_E_OOM;
+        cw.segs.push_back({adv_p, b_adv, B * (size_t)na});
+        if (ni) cw.segs.push_back({inst_p, b_inst, B * (size_t)ni});
+        if (nz) cw.segs.push_back({z_p, b_z, B * (size_t)nz});
+        QuotientPtrs qp;
+        qp.adv = b_adv, qp.inst = b_inst, qp.z = b_z, qp.lk_cols = lk_cols;
+        const size_t lk_block = wi.lk_bytes / 4 / (size_t)std::max(nl, 1);   // words of one lookup's (B, 2, n) block
+        for (int i = 0; i < nl; i++) {
+            if (lk_cols == 2) {
+                cw.segs.push_back({lk_p[i], b_lk + (size_t)i * lk_block, B * 2});
+                qp.lk.push_back(b_lk + (size_t)i * lk_block);
+            } else {
+                if (i == 0) cw.segs.push_back({lk_p[0], b_lk, B * lk_cols});
+                qp.lk.push_back(b_lk + (size_t)i * 2 * n * 8);
+            }
+        }
+        quotient_registry(pk, qp, false, cw.reg, n);
+        std::vector<uint32_t> shifts(cw.reg.ptr.size());
+        for (size_t c = 0; c < shifts.size(); c++) shifts[c] = cw.reg.stride[c] ? 3u : 0u;   // per-proof: n-sized | the key's: on 8 n
+        cw.d_shifts = (uint32_t*)arena.alloc(shifts.size() * 4);
+        if (!cw.d_shifts) return BZH_E_OOM;
+        return h2d_small(ctx, cw.d_shifts, shifts.data(), shifts.size() * 4);
+    }
+    int cosetwise_launch(const CosetWork& cw, const ProgramArgs& pa, uint32_t* d_out) {
+        const Program2& pg = pk.qprog;
+        Fe<SF> w, shift;
+        {
+            uint64_t t[4];
+            memcpy(t, pk.eomega, 32);
+            w = fe_from_u64<SF>(t);
+            memcpy(t, pk.zeta, 32);
+            shift = fe_from_u64<SF>(t);
+        }
+        if (ctx->profiling) {   // as launch_quotient counts: every column read once over the 8 n rows and h written -- plus what
+            double cols_read = 0, refilled = 0;   // this mode adds: each per-proof polynomial copied (read + write) eight times
+            for (size_t i = 0; i < cw.reg.ptr.size() - pk.hoist_cols; i++) cols_read += cw.reg.stride[i] ? (double)B : 1.0;
+            for (const CosetSeg& sg : cw.segs) refilled += (double)sg.count;
+            ctx->alg_bytes[BZH_T_QUOTIENT] += ((cols_read + (double)B) * (double)en + refilled * 8.0 * 2.0 * (double)n) * 32.0;
+        }   // (the eight n-point transforms per polynomial are counted by ntt_run itself, under BZH_T_NTT)
+        const uint32_t* const* tables[8];
+        for (auto& t : tables) t = (const uint32_t* const*)pa.ptrs;
+        auto refill = [&](unsigned j) -> int {
+            uint64_t sh[4];
+            fe_to_u64<SF>(sh, shift);   // zeta eomega^j, Montgomery limbs as ntt_run takes them
+            shift = fe_mul(shift, w);
+            (void)j;
+            for (const CosetSeg& sg : cw.segs) {
+                BZH_HIP_TRY(ctx, hipMemcpyAsync(sg.buf, sg.polys, sg.count * n * 32, hipMemcpyDeviceToDevice, st));
+                BZH_TRY(ntt_run(ctx, field, sg.buf, pk.k, sg.count, pk.omega, sh, 0, BZH_FORM_MONTGOMERY));
+            }
+            return BZH_OK;
+        };
+        return expr_eval2_cosets(ctx, field, pa.prog, (int)pg.ops.size(), tables, (const size_t*)pa.strides, cw.d_shifts, pa.consts,
+                                 pg.consts.size(), pk.k, B, pg.nlds, d_out, refill);
+    }
+
     // ---- the phases of create_proof, in protocol order ---------------------------------------------------------------------
     // the opening point x w^r of proof b.  reads xs, omega_m, omega_inv; caches omega^r in wp
     Fe<SF> rot(size_t b, int r) {
@@ -440,7 +533,7 @@ struct Prover : DeviceColumns<C> {
     // so that it runs on the device while the host sorts the lookups (a second call does nothing).
     // reads inst_polys, adv_polys; fills inst_cosets, adv_cosets
     int extend_witness() {
-        if (adv_cosets) return BZH_OK;
+        if (adv_cosets || cosetwise) return BZH_OK;
         inst_cosets = ext_alloc(B * std::max(ni, 1));
         adv_cosets = ext_alloc(B * na);
         if (!inst_cosets || !adv_cosets) return BZH_E_OOM;
@@ -639,13 +732,13 @@ struct Prover : DeviceColumns<C> {
     int grand_products() {
         zs = dalloc(B * std::max(nz, 1) * n);
         z_polys = dalloc(B * std::max(nz, 1) * n);
-        z_cosets = ext_alloc(B * std::max(nz, 1));
+        z_cosets = cosetwise ? nullptr : ext_alloc(B * std::max(nz, 1));
         // numerators and denominators of ALL grand products side by side, [product][proof][row]: one batch inversion, one
         // element-wise product and one scan for the lot (they were per product; the permutation sets are chained only through a
         // scalar carried from one set's last row into the next, applied afterwards)
         uint32_t* den_all = dalloc(B * std::max(nz, 1) * n);
         uint32_t* zt_all = dalloc(B * std::max(nz, 1) * n);
-        if (!zs || !z_polys || !z_cosets || !den_all || !zt_all) return BZH_E_OOM;
+        if (!zs || !z_polys || (!z_cosets && !cosetwise) || !den_all || !zt_all) return BZH_E_OOM;
         z_blinds.resize(B * std::max(nz, 1));
         BZH_TRY(product_factors(den_all, zt_all));
         if (nz) {
@@ -664,9 +757,10 @@ struct Prover : DeviceColumns<C> {
             for (size_t b = 0; b < B; b++)
                 for (int i = 0; i < nz; i++) bzh_transcript_write_point(T[b], C::id, &xy[(b * nz + i) * 8]);
             mark(" gp:commit");
-            BZH_TRY(to_extended(z_cosets, z_polys, B * nz));
+            if (!cosetwise) BZH_TRY(to_extended(z_cosets, z_polys, B * nz));
             mark(" gp:extend_z");
         }
+        if (cosetwise) return BZH_OK;
         for (auto& d : lk) {
             d.cosets = ext_alloc(B * 2);
             if (!d.cosets) return BZH_E_OOM;
@@ -677,6 +771,17 @@ struct Prover : DeviceColumns<C> {
 
     // the quotient's values on the extended coset -> h (B x en).  reads the cosets of every column, env
     int quotient() {
+        if (cosetwise) {
+            CosetWork cw;
+            std::vector<const uint32_t*> lk_p;
+            for (int i = 0; i < nl; i++) lk_p.push_back(lk[i].polys);
+            BZH_TRY(cosetwise_setup(adv_polys, inst_polys, z_polys, lk_p, 2, cw));
+            std::vector<uint32_t> cv;
+            BZH_TRY(fill_consts(pk.qprog.consts, B, 8, put_saturated, cv));
+            ProgramArgs pa;
+            BZH_TRY(quotient_args(cw.reg, cv.data(), cv.size() * 4, pa));
+            return cosetwise_launch(cw, pa, h);
+        }
         Cols reg;
         QuotientPtrs qp;
         qp.adv = adv_cosets, qp.inst = inst_cosets, qp.z = z_cosets;

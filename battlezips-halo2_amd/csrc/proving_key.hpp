@@ -56,6 +56,7 @@ struct bzh_pk : bzh::KeyShape {
     hipModule_t q_module = nullptr;
     hipFunction_t q_fn = nullptr;
     int q_select = BZH_QUOTIENT_INTERPRETER;
+    int ws_select = BZH_WORKSPACE_EXTENDED;   // BZH_WORKSPACE_*: where the quotient reads the per-proof columns (bzh_pk_workspace_select)
     int lk_select = BZH_LOOKUP_DEVICE;   // BZH_LOOKUP_*: where the lookup argument's columns are permuted (bzh_pk_lookup_select)
     bool lk_chosen = false;   // bzh_pk_lookup_select was called: lk_select holds for every batch size (else see kLookupDeviceMinBatch, prover.hpp)
     int vpass_select = BZH_VERIFY_PASS_HOST;  // BZH_VERIFY_PASS_*: where bzh_verify_batch runs the per-proof pass (bzh_pk_verify_pass_select)
@@ -153,8 +154,11 @@ struct Key29Layout {
 //   fe29 planes (planes = true): 9 en words a column, stride = WORDS between consecutive proofs, the key's columns out of pk.key29;
 // stride 0 = shared (key-owned).  The hoisted columns come last.  Cols::add keeps what it has: compile_quotient calls this a
 // second time, once it knows how many hoisted columns there are.
-static void quotient_registry(const bzh_pk& pk, const QuotientPtrs& q, bool planes, Cols& reg) {
-    const size_t en = pk.en, m = pk.perm_columns.size(), w = planes ? 9 : 8, su = planes ? 9 * en : en;
+// proof_elems (saturated elements only): the elements of ONE per-proof column when that is not en -- n, for the coset-wise
+// workspace, whose per-proof columns hold one coset of n points at a time (workspace_items below); the key's stay at en.
+static void quotient_registry(const bzh_pk& pk, const QuotientPtrs& q, bool planes, Cols& reg, size_t proof_elems = 0) {
+    const size_t en = pk.en, pe = proof_elems && !planes ? proof_elems : en, m = pk.perm_columns.size(), w = planes ? 9 : 8,
+                 su = planes ? 9 * en : pe;
     const int na = pk.na, nf = pk.nf, ni = pk.ni, nsets = pk.nsets, nl = pk.nl, nz = pk.nsets + pk.nl;
     auto at = [&](const uint32_t* base, size_t elems) -> const uint32_t* { return base ? base + elems * w : nullptr; };
     const Key29Layout k29(pk);
@@ -163,20 +167,66 @@ static void quotient_registry(const bzh_pk& pk, const QuotientPtrs& q, bool plan
     const uint32_t* k_sigma = planes ? at(pk.key29, k29.sigma * en) : pk.sigma_cosets;
     const uint32_t* k_misc = planes ? at(pk.key29, k29.misc * en) : pk.l0;
     const uint32_t* k_hoist = planes ? at(pk.key29, k29.hoist * en) : pk.hoist;
-    for (int i = 0; i < na; i++) reg.add(key(K_ADV, i), at(q.adv, (size_t)i * en), (size_t)na * su);
+    for (int i = 0; i < na; i++) reg.add(key(K_ADV, i), at(q.adv, (size_t)i * pe), (size_t)na * su);
     for (int i = 0; i < nf; i++) reg.add(key(K_FIX, i), at(k_fixed, (size_t)i * en), 0);
-    for (int i = 0; i < ni; i++) reg.add(key(K_INST, i), at(q.inst, (size_t)i * en), (size_t)ni * su);
+    for (int i = 0; i < ni; i++) reg.add(key(K_INST, i), at(q.inst, (size_t)i * pe), (size_t)ni * su);
     for (size_t j = 0; j < m; j++) reg.add(key(K_SIGMA, j), at(k_sigma, j * en), 0);
-    for (int i = 0; i < nsets; i++) reg.add(key(K_PZ, i), at(q.z, (size_t)i * en), (size_t)nz * su);
+    for (int i = 0; i < nsets; i++) reg.add(key(K_PZ, i), at(q.z, (size_t)i * pe), (size_t)nz * su);
     for (int i = 0; i < nl; i++) {
         const uint32_t* c = (size_t)i < q.lk.size() ? q.lk[i] : nullptr;
         reg.add(key(K_LA, i), c, q.lk_cols * su);
-        reg.add(key(K_LS, i), at(c, en), q.lk_cols * su);
-        reg.add(key(K_LZ, i), at(q.z, (size_t)(nsets + i) * en), (size_t)nz * su);
+        reg.add(key(K_LS, i), at(c, pe), q.lk_cols * su);
+        reg.add(key(K_LZ, i), at(q.z, (size_t)(nsets + i) * pe), (size_t)nz * su);
     }
     static const int misc[5] = {M_L0, M_LLAST, M_LBLIND, M_X, M_TINV};
     for (size_t i = 0; i < 5; i++) reg.add(key(K_MISC, misc[i]), at(k_misc, i * en), 0);
     for (size_t hi = 0; hi < pk.hoist_cols; hi++) reg.add(key(K_HOIST, hi), at(k_hoist, hi * en), 0);
+}
+
+// What one prove call of `batch` proofs takes from its arena, by item (bzh_workspace_plan; host only).  The `cosets` items are
+// the buffers the quotient reads the per-proof columns from -- every one on the whole extended coset (BZH_WORKSPACE_EXTENDED:
+// en elements a column, what Prover::ext_alloc hands out in saturated limbs) or on one coset of n points at a time
+// (BZH_WORKSPACE_COSETWISE: n elements a column; Prover::cosetwise_setup carves exactly these four sizes).  The other items
+// count the call's column-sized buffers as the phases of prover.hpp allocate them: per-proof columns over the domain and as
+// coefficients with the grand products' factors (witness), h (quotient), and the largest stretch of the phases after it
+// (tail: random polynomial and its draws, the pieces, then the evaluation gather or the multiopen's buffers with the opening's
+// draws).  What the launches stage besides (programs, constants, blinds, status words) is covered by an allowance, staging:
+// 1 MiB + 64 KiB a proof.  tests/test_gpu_workspace_cosetwise.py holds the total against the arena's high-water mark.
+struct WorkspaceItems {
+    size_t column_bytes = 0;                                    // one per-proof column where the quotient reads it
+    size_t adv_bytes = 0, inst_bytes = 0, z_bytes = 0, lk_bytes = 0;   // the four coset buffers of the batch
+    size_t cosets_bytes = 0, cosets_extended_bytes = 0;         // their sum in this mode | in BZH_WORKSPACE_EXTENDED
+    size_t witness_bytes = 0, quotient_bytes = 0, tail_bytes = 0, staging_bytes = 0, total_bytes = 0;
+};
+static WorkspaceItems workspace_items(const bzh_pk& pk, size_t batch, int mode) {
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };   // Arena::alloc's rounding
+    const size_t B = batch, n = pk.n, en = pk.en, na = (size_t)pk.na, ni = (size_t)std::max(pk.ni, 1), nl = (size_t)pk.nl,
+                 nz = (size_t)std::max(pk.nsets + pk.nl, 1), npieces = (size_t)pk.npieces, m = pk.perm_columns.size(),
+                 nq = pk.rot_sets.size(), col = n * 32;
+    WorkspaceItems w;
+    auto cosets = [&](size_t elems, size_t* sum) {
+        const size_t a = al(B * std::max<size_t>(na, 1) * elems * 32), i = al(B * ni * elems * 32), z = al(B * nz * elems * 32), l = nl * al(B * 2 * elems * 32);
+        *sum = a + i + z + l;
+        if (elems == (mode == BZH_WORKSPACE_COSETWISE ? n : en)) w.adv_bytes = a, w.inst_bytes = i, w.z_bytes = z, w.lk_bytes = l;
+    };
+    cosets(en, &w.cosets_extended_bytes);
+    if (mode == BZH_WORKSPACE_COSETWISE) cosets(n, &w.cosets_bytes);
+    else w.cosets_bytes = w.cosets_extended_bytes;
+    w.column_bytes = (mode == BZH_WORKSPACE_COSETWISE ? n : en) * 32;
+    // (per lookup: compressed input and table, the permuted pair, its coefficients -- and the two canonical copies the host
+    // permutation sorts from, Prover::permute_on_host, counted for every batch though batches of 8 and more permute on the device)
+    w.witness_bytes = B * col * (2 * ni + 2 * na + 8 * nl + 4 * nz);
+    w.quotient_bytes = al(B * en * 32);
+    size_t J = pk.instance_queries.size() + pk.advice_queries.size() + pk.fixed_queries.size() + 1 + m + 5 * nl, J2 = 0;
+    if (pk.nsets) J += 3 * (size_t)pk.nsets - 1;
+    for (auto& rs : pk.rot_sets) J2 += rs.size();
+    const size_t ipa_draws = al(B * 64 * (n + 1 + 2 * (size_t)pk.k));
+    const size_t multiopen = std::max(B * col * (3 + nq + J2), B * col * (5 + 5 * nq) + ipa_draws);
+    w.tail_bytes = B * col * (3 + npieces) + std::max(B * col * J, multiopen);
+    // an allowance, not a count: programs and their constant tables, blinding draws, blinds, status words, point tables
+    w.staging_bytes = ((size_t)1 << 20) + B * ((size_t)64 << 10);
+    w.total_bytes = w.witness_bytes + w.cosets_bytes + w.quotient_bytes + w.tail_bytes + w.staging_bytes;
+    return w;
 }
 
 // every term of the quotient's numerator in protocol order (gates, permutation argument, lookups); *tinv = the 1 / (X^n - 1) column

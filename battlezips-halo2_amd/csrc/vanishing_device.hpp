@@ -146,16 +146,23 @@ static int vanishing_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t
     BZH_TRY(operand(beta, B, false, &d_beta));
     BZH_TRY(operand(gamma, B, false, &d_gamma));
 
-    // every column on the extended coset (fe29 planes when the unsaturated kernel will run), as extend_witness / grand_products
-    uint32_t* adv_cosets = pv.ext_alloc(B * std::max<size_t>(na, 1));
-    uint32_t* inst_cosets = pv.ext_alloc(B * std::max<size_t>(ni, 1));
-    uint32_t* z_cosets = pv.ext_alloc(B * std::max<size_t>(nz, 1));
-    uint32_t* lk_cosets = pv.ext_alloc(B * std::max<size_t>(2 * nl, 1));
-    if (!adv_cosets || !inst_cosets || !z_cosets || !lk_cosets) return BZH_E_OOM;
-    BZH_TRY(pv.to_extended(inst_cosets, d_inst, B * ni));
-    BZH_TRY(pv.to_extended(adv_cosets, d_adv, B * na));
-    BZH_TRY(pv.to_extended(z_cosets, d_z, B * nz));
-    BZH_TRY(pv.to_extended(lk_cosets, d_lk, B * nl * 2));
+    // every column on the extended coset (fe29 planes when the unsaturated kernel will run), as extend_witness / grand_products;
+    // BZH_WORKSPACE_COSETWISE: none of them -- n-sized buffers over the coefficient forms, refilled coset by coset at the launch
+    uint32_t *adv_cosets = nullptr, *inst_cosets = nullptr, *z_cosets = nullptr, *lk_cosets = nullptr;
+    typename Prover<C>::CosetWork cw;
+    if (pv.cosetwise) {
+        BZH_TRY(pv.cosetwise_setup(d_adv, d_inst, d_z, std::vector<const uint32_t*>(1, d_lk), 2 * nl, cw));
+    } else {
+        adv_cosets = pv.ext_alloc(B * std::max<size_t>(na, 1));
+        inst_cosets = pv.ext_alloc(B * std::max<size_t>(ni, 1));
+        z_cosets = pv.ext_alloc(B * std::max<size_t>(nz, 1));
+        lk_cosets = pv.ext_alloc(B * std::max<size_t>(2 * nl, 1));
+        if (!adv_cosets || !inst_cosets || !z_cosets || !lk_cosets) return BZH_E_OOM;
+        BZH_TRY(pv.to_extended(inst_cosets, d_inst, B * ni));
+        BZH_TRY(pv.to_extended(adv_cosets, d_adv, B * na));
+        BZH_TRY(pv.to_extended(z_cosets, d_z, B * nz));
+        BZH_TRY(pv.to_extended(lk_cosets, d_lk, B * nl * 2));
+    }
 
     // the results: the caller's device buffers (Montgomery until the call's last launches), or the workspace
     uint32_t* rp = host ? pv.dalloc(B * n) : (uint32_t*)out_random;
@@ -183,15 +190,16 @@ static int vanishing_device_t(bzh_ctx* ctx, bzh_pk* pk, size_t B, const uint64_t
     Cols reg;
     QuotientPtrs qp;
     qp.adv = adv_cosets, qp.inst = inst_cosets, qp.z = z_cosets, qp.lk_cols = 2 * nl;
-    for (size_t i = 0; i < nl; i++) qp.lk.push_back(lk_cosets + i * 2 * en * (pv.q29 ? 9 : 8));
-    quotient_registry(*pk, qp, pv.q29, reg);
+    for (size_t i = 0; i < nl && !pv.cosetwise; i++) qp.lk.push_back(lk_cosets + i * 2 * en * (pv.q29 ? 9 : 8));
+    if (!pv.cosetwise) quotient_registry(*pk, qp, pv.q29, reg);
     typename Prover<C>::ProgramArgs pa;
-    BZH_TRY(pv.quotient_args(reg, nullptr, std::max<size_t>(B * nc, 1) * pv.quotient_const_words() * 4, pa));
+    BZH_TRY(pv.quotient_args(pv.cosetwise ? cw.reg : reg, nullptr, std::max<size_t>(B * nc, 1) * pv.quotient_const_words() * 4, pa));
     void* d_descs = arena.alloc(std::max<size_t>(nc, 1) * sizeof(VnConst));
     if (!d_descs) return BZH_E_OOM;
     BZH_TRY(h2d_small(ctx, d_descs, descs.data(), nc * sizeof(VnConst)));
     BZH_TRY(vanishing_consts(ctx, field, d_descs, nc, B, d_theta, d_beta, d_gamma, d_y, form, pv.q29, pa.consts));
-    BZH_TRY(pv.launch_quotient(reg, en, pa, h));
+    if (pv.cosetwise) BZH_TRY(pv.cosetwise_launch(cw, pa, h));
+    else BZH_TRY(pv.launch_quotient(reg, en, pa, h));
     BZH_TRY(ntt_run(ctx, field, h, pk->ek, B, pk->eomega, pk->zeta, 1, BZH_FORM_MONTGOMERY));
 
     // the degree check, per proof

@@ -277,6 +277,20 @@ int bzh_vm2_eval(bzh_ctx* ctx, int field, const void* ops, size_t nops, const ui
                  size_t ncols, const uint64_t* consts, size_t nconsts, size_t const_stride, unsigned log_size, size_t batch, int nlds,
                  int form, int mem, uint64_t* out);
 
+/* The same program evaluated COSET BY COSET, as the prover's BZH_WORKSPACE_COSETWISE does it, without a proving key.  The 8 n
+ * rows of a vector (n = 2^log_n) are eight cosets of n rows: row R = 8 r + j is row r of coset j.  One launch per coset; a leaf
+ * of column c at rotation rot reads index ((R + rot) & (8 n - 1)) >> shift, shift 0 for a column with column_extended[c] != 0 (8 n
+ * elements per vector, laid out as for bzh_vm2_eval) and 3 for an n-sized one, which is given as EIGHT blocks, one per coset:
+ * coset j's values of vector v start at columns[c] + j * block + v * column_strides[c] elements, block = batch * column_strides[c],
+ * or n for a shared column (stride 0); block j holds the column's rows j, j + 8, j + 16, ...  out: batch x 8 n values, equal word
+ * for word to bzh_vm2_eval's over the same data.  BZH_E_ARG, out untouched: whatever bzh_vm2_eval refuses (the multiple of 128
+ * excepted: a last workgroup may be partial); a column leaf that is read with a rotation that is not a multiple of 8 (it would
+ * leave the coset); out_size != 8 * 2^log_n; log_n above 27; a stride below the column's rows; `out`, `consts` or a column
+ * pointer that is not aligned to 8 bytes (BZH_MEM_HOST) or to 32 bytes (BZH_MEM_DEVICE). */
+int bzh_vm2_eval_cosets(bzh_ctx* ctx, int field, const void* ops, size_t nops, const uint64_t* const* columns, const size_t* column_strides,
+                        const uint8_t* column_extended, size_t ncols, const uint64_t* consts, size_t nconsts, size_t const_stride,
+                        unsigned log_n, size_t out_size, size_t batch, int nlds, int form, int mem, uint64_t* out);
+
 /* ---- inner-product-argument opening (halo2_proofs poly::commitment::{create_proof, verify_proof}) --
  * Step 9 of plonk::create_proof and the heart of verify_proof (benches/board.rs:80-86).
  * `bases` must hold n + 2 points: the n = 2^k SRS generators followed by U and W (Params.u, Params.w);
@@ -682,6 +696,50 @@ int bzh_pk_quotient_selected(bzh_pk* pk, int* flavour, int* builtin_available);
 typedef enum { BZH_LOOKUP_HOST = 0, BZH_LOOKUP_DEVICE = 1 } bzh_lookup_where;
 int bzh_pk_lookup_select(bzh_pk* pk, int where);
 int bzh_pk_lookup_selected(bzh_pk* pk, int* where);
+/* Where the quotient reads the per-proof columns (advice, instance, grand products, permuted lookup columns) in bzh_prove_batch,
+ * bzh_prove_batch_seeded, bzh_vanishing_batch_device and everything built on it (bzh_prove_batch_device[_seeded],
+ * bzh_prove_shots_device, bzh_prove_boards_device).  BZH_WORKSPACE_EXTENDED (every new key's default): each of them on the whole
+ * extended coset, 8 n elements, until the call ends.  BZH_WORKSPACE_COSETWISE: none of them is ever taken there; the extended
+ * domain is eight cosets of the n-sized one, and for each coset the coefficient forms go through one n-point transform into
+ * n-sized buffers that are reused, followed by one launch of the interpreter for the batch (k_expr_vm2_cosets) that reads the
+ * key's columns where they lie and writes its share of the quotient's 8 n values.  Same quotient, same proof bytes, same
+ * statuses; an eighth of the memory for these columns (bzh_workspace_plan), eight launches and eight transforms where there was
+ * one of each.  COSETWISE OVERRIDES THE QUOTIENT FLAVOUR: the quotient always runs the interpreter in this mode -- the builtin
+ * kernels and loaded modules index 8 n columns -- while bzh_pk_quotient_selected keeps reporting the caller's choice, which is
+ * in force again after a return to BZH_WORKSPACE_EXTENDED.  A circuit the interpreter does not fit, or an extended domain other
+ * than 8 n, makes the prove calls return BZH_E_RANGE in this mode.  BZH_E_ARG: NULL key or an unknown value. */
+typedef enum { BZH_WORKSPACE_EXTENDED = 0, BZH_WORKSPACE_COSETWISE = 1 } bzh_workspace_mode;
+int bzh_pk_workspace_select(bzh_pk* pk, int mode);
+int bzh_pk_workspace_selected(bzh_pk* pk, int* mode);
+/* What one prove call of `batch` proofs takes from the key's per-ctx arena in `mode`, in bytes: pure host code (no ctx, no
+ * device), like bzh_vanishing_plan.  The figure is the sum of the items below, which count the call's column-sized buffers as
+ * the phases allocate them, plus an allowance for what the launches stage; it is not below the arena's high-water mark
+ * (bzh_pk_workspace_peak) and above it by no more than the allowance for the batches the tests run; `cosets_bytes` is the term the mode
+ * changes, and the prover carves its coset-wise buffers with the sizes this same function computes.  cosets_extended_bytes is
+ * that term in BZH_WORKSPACE_EXTENDED whatever `mode` is: the two modes' totals differ by 7/8 of it.  Apart from the coset term
+ * the items are a MODEL of the phases' allocations, held against the arena only for the Shot circuit at k = 11, batch 3; for
+ * other circuits and sizes nothing has compared it with an arena, and a circuit with more lookups or a larger quotient
+ * program can stage more than the allowance: size with a margin, or read bzh_pk_workspace_peak after a first call.  In EXTENDED mode with the
+ * builtin quotient kernel in unsaturated limbs the columns take 9/8 of the figure (36 bytes an element).  BZH_E_ARG: a blob
+ * that does not parse, batch 0 or above 65535, an unknown mode, a NULL argument. */
+typedef struct bzh_workspace_items {
+    uint64_t n, extended;             /* rows of the domain | of the extended domain */
+    uint64_t columns;                 /* per-proof columns the quotient reads */
+    uint64_t column_bytes;            /* one of them where the quotient reads it: 32 * extended | 32 * n */
+    uint64_t cosets_bytes;            /* all of them for the batch, in `mode` */
+    uint64_t cosets_extended_bytes;   /* ... in BZH_WORKSPACE_EXTENDED */
+    uint64_t witness_bytes;           /* the per-proof columns over the domain and as coefficients, the grand products' factors */
+    uint64_t quotient_bytes;          /* h: 32 * extended per proof */
+    uint64_t tail_bytes;              /* the largest stretch after the quotient: random polynomial, pieces, evaluation gather or multiopen */
+    uint64_t staging_bytes;           /* an allowance for what the launches stage (programs, constants, blinds): 1 MiB + 64 KiB a proof */
+    uint64_t total_bytes;             /* their sum: what bzh_workspace_plan returns */
+} bzh_workspace_items;
+int bzh_workspace_plan(int curve, const uint8_t* circuit, size_t circuit_len, size_t batch, int mode, size_t* arena_bytes);
+int bzh_workspace_plan_items(int curve, const uint8_t* circuit, size_t circuit_len, size_t batch, int mode, bzh_workspace_items* items);
+/* The high-water mark of the key's arenas, in bytes handed out at once, since the start of the LAST call on each ctx (the
+ * largest over the ctxs that have used the key; 0 before any call): what bzh_workspace_plan is an estimate of.  Read it when no
+ * call is running on the key.  BZH_E_ARG: a NULL argument. */
+int bzh_pk_workspace_peak(const bzh_pk* pk, size_t* arena_bytes);
 /* Where bzh_verify_batch decompresses the points of the proofs: BZH_VERIFY_POINTS_HOST inside the per-proof host pass, one
  * square root at a time (every new key's default); BZH_VERIFY_POINTS_DEVICE gathers the 32-byte strings of the whole batch --
  * their offsets in a proof depend on the key only --, decompresses them in one bzh_affine_decompress launch on the ctx's
