@@ -1175,6 +1175,7 @@ EXPORTS += ["bzh_pk_verify_pass_select", "bzh_pk_verify_pass_selected", "bzh_ver
 EXPORTS += ["bzh_hash_to_curve", "bzh_params_generators", "bzh_group_ifft", "bzh_params_create", "bzh_params_free", "bzh_params_bases",
             "bzh_params_points"]
 EXPORTS += ["bzh_hash_to_curve_batch", "bzh_map_to_curve_batch", "bzh_params_generators_device", "bzh_params_create_with"]
+EXPORTS += ["bzh_params_file_info", "bzh_params_encode", "bzh_params_write", "bzh_params_read"]
 # circuit front end (bzh2/circuits.py)
 EXPORTS += ["bzh_circuit_create", "bzh_circuit_free", "bzh_circuit_last_error", "bzh_circuit_blob", "bzh_circuit_describe",
             "bzh_circuit_info", "bzh_synthesize_shot", "bzh_synthesize_board", "bzh_synthesize_bitify_test", "bzh_board_witness",

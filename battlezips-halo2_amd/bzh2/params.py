@@ -29,6 +29,11 @@ def _bind():
     L.bzh_map_to_curve_batch.argtypes = [_VP, ctypes.c_int, _VP, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _VP, u8p]
     L.bzh_params_generators_device.argtypes = [_VP, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _VP]
     L.bzh_params_create_with.argtypes = [_VP, ctypes.c_uint, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_VP)]
+    szp = ctypes.POINTER(ctypes.c_size_t)
+    L.bzh_params_file_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), szp]
+    L.bzh_params_encode.argtypes = [ctypes.c_uint, _VP, _VP, _VP, _VP, _VP, ctypes.c_size_t, szp]
+    L.bzh_params_write.argtypes = [_VP, _VP, _VP, ctypes.c_size_t, szp]
+    L.bzh_params_read.argtypes = [_VP, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_VP), _VP]
     L._bzh_params_bound = True
     return L
 
@@ -108,6 +113,51 @@ def group_ifft(ctx: Context, g: np.ndarray) -> np.ndarray:
     return out
 
 
+E_RANGE = -4
+CHECK_POINTS, CHECK_LAGRANGE, CHECK_FULL = 0, 1, 2
+_CHECKS = {"points": CHECK_POINTS, "lagrange": CHECK_LAGRANGE, "full": CHECK_FULL}
+BAD_DECODE, BAD_LAGRANGE, BAD_GENERATORS = 1, 2, 4
+SECTIONS = ("g", "g_lagrange", "w", "u")
+
+
+class ParamsFileError(ValueError):
+    """bzh_params_read refused a params file: the fields of its bzh_params_verdict -- bits (BAD_DECODE, or BAD_LAGRANGE |
+    BAD_GENERATORS), and section (index into SECTIONS), first_bad, n_bad of the offending points (include/bzh2.h)."""
+
+    def __init__(self, bits: int, section: int, first_bad: int, n_bad: int, detail: str = ""):
+        self.bits, self.section, self.first_bad, self.n_bad = bits, section, first_bad, n_bad
+        super().__init__(detail or "params file refused: bits %d, %s[%d], %d bad" % (bits, SECTIONS[section & 3], first_bad, n_bad))
+
+
+def file_info(data: bytes):
+    """(k, n) of a params file's header after the length check (bzh_params_file_info, host only)"""
+    data = bytes(data)
+    k, n = ctypes.c_uint(), ctypes.c_size_t()
+    rc = _bind().bzh_params_file_info(data, len(data), ctypes.byref(k), ctypes.byref(n))
+    if rc:
+        raise BzhError(rc, "bzh_params_file_info")
+    return k.value, n.value
+
+
+def encode(k: int, g, g_lagrange, w, u) -> bytes:
+    """halo2_proofs' Params::write for points given as canonical limbs (bzh_params_encode, host only): g, g_lagrange (n, 8) uint64,
+    w, u (8,) uint64."""
+    arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in (g, g_lagrange, w, u)]
+    n = 1 << k
+    if arrs[0].shape != (n, 8) or arrs[1].shape != (n, 8) or arrs[2].size != 8 or arrs[3].size != 8:
+        raise ValueError("encode: g and g_lagrange are (2^k, 8) arrays, w and u 8 limbs")
+    L, size = _bind(), ctypes.c_size_t()
+    ptrs = [_VP(a.ctypes.data) for a in arrs]
+    rc = L.bzh_params_encode(k, *ptrs, None, 0, ctypes.byref(size))
+    if rc:
+        raise BzhError(rc, "bzh_params_encode")
+    out = np.zeros(size.value, dtype=np.uint8)
+    rc = L.bzh_params_encode(k, *ptrs, _VP(out.ctypes.data), out.size, ctypes.byref(size))
+    if rc:
+        raise BzhError(rc, "bzh_params_encode")
+    return out.tobytes()
+
+
 class Params:
     """Params::<vesta::Affine>::new(k): the two commitment-base tables live on the device."""
 
@@ -119,12 +169,51 @@ class Params:
             raise ValueError("Params: generators is 'host' or 'device'")
         ctx._check(L.bzh_params_create_with(ctx.handle, k, None if cache_dir is None else cache_dir.encode(), window_bits,
                                             _GENERATORS[generators], ctypes.byref(h)), "bzh_params_create_with")
+        self._attach(ctx, h, k)
+
+    def _attach(self, ctx: Context, h, k: int):
+        """take over a bzh_params handle, whoever made it"""
         self.ctx, self.handle, self.k, self.n = ctx, h, k, 1 << k
         g, gl = _VP(), _VP()
-        L.bzh_params_bases(h, ctypes.byref(g), ctypes.byref(gl))
+        _bind().bzh_params_bases(h, ctypes.byref(g), ctypes.byref(gl))
         self.bases = Bases(ctx, g, CURVE_VESTA, self.n + 2)
         self.bases_lagrange = Bases(ctx, gl, CURVE_VESTA, self.n + 3)    # (g_lagrange | u | w | g_0)
         self._borrowers = []     # weak references to the proving keys built on these tables (they borrow, include/bzh2.h)
+
+    @classmethod
+    def from_bytes(cls, ctx: Context, data: bytes, check: str = "full", window_bits: int = 0) -> "Params":
+        """halo2_proofs' Params::read (bzh_params_read): the byte string Params::write / to_bytes gives -> Params on ctx's device,
+        as __init__ would have made them for the same points.  check: "points" (every string is a point other than the identity),
+        "lagrange" (and g_lagrange is the inverse group FFT of g), "full" (and g, w, u are Params::new(k)'s -- the default, the only
+        level that protects soundness).  A refused file raises ParamsFileError; a malformed one (length, k) BzhError."""
+        if check not in _CHECKS:
+            raise ValueError("Params.from_bytes: check is 'points', 'lagrange' or 'full'")
+        data = bytes(data)
+        h, v = _VP(), np.zeros(4, dtype=np.uint32)
+        rc = _bind().bzh_params_read(ctx.handle, data, len(data), window_bits, _CHECKS[check], ctypes.byref(h), _VP(v.ctypes.data))
+        if rc == E_RANGE and v[0]:
+            raise ParamsFileError(*(int(x) for x in v), detail=load().bzh_last_error(ctx.handle).decode())
+        ctx._check(rc, "bzh_params_read")
+        self = cls.__new__(cls)
+        self._attach(ctx, h, file_info(data)[0])
+        return self
+
+    def to_bytes(self) -> bytes:
+        """halo2_proofs' Params::write (bzh_params_write): k | g | g_lagrange | w | u, 32 bytes a point."""
+        L, size = _bind(), ctypes.c_size_t()
+        self.ctx._check(L.bzh_params_write(self.ctx.handle, self.handle, None, 0, ctypes.byref(size)), "bzh_params_write")
+        out = np.zeros(size.value, dtype=np.uint8)
+        self.ctx._check(L.bzh_params_write(self.ctx.handle, self.handle, _VP(out.ctypes.data), out.size, ctypes.byref(size)), "bzh_params_write")
+        return out.tobytes()
+
+    @classmethod
+    def from_file(cls, ctx: Context, path, check: str = "full", window_bits: int = 0) -> "Params":
+        with open(path, "rb") as f:
+            return cls.from_bytes(ctx, f.read(), check=check, window_bits=window_bits)
+
+    def to_file(self, path):
+        with open(path, "wb") as f:
+            f.write(self.to_bytes())
 
     def points(self, want_g: bool = True, want_lagrange: bool = True):
         """host copies: (g, g_lagrange, w, u, from_cache) -- arrays of canonical limbs, w / u as (x, y) ints"""

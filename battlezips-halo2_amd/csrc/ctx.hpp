@@ -357,6 +357,10 @@ int expr_eval2(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint
 int expr_eval2_cosets(bzh_ctx* ctx, int field, const void* d_prog, int nops, const uint32_t* const* const* d_cols_by_coset,
                       const size_t* d_strides, const uint32_t* d_shifts, const uint32_t* d_consts, size_t const_stride, unsigned log_n,
                       size_t batch, int nlds, uint32_t* d_out, const std::function<int(unsigned)>& refill);
+// prove.hip: the seeded provers' expansion of bzh_rng_expand's stream on the device (k_chacha20_rows).  d_raw[(b * count + i) * 16 ..]
+// = the 64-byte draw counter0 + i of the stream keyed by the eight words at d_keys + 8 b, b < batch <= 65535; d_raw 16-byte
+// aligned.  Enqueues only.
+int rng_rows_device(bzh_ctx* ctx, const uint32_t* d_keys, uint64_t counter0, size_t count, size_t batch, uint32_t* d_raw);
 // ipa.hip
 int random_field(bzh_ctx* ctx, int field, const uint32_t* d_raw, size_t count, uint32_t* d_out);
 int ipa_open(bzh_ctx* ctx, const bzh_bases* bases, const uint32_t* d_polys, size_t batch, const uint64_t* blinds,

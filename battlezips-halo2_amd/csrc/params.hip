@@ -30,6 +30,7 @@
 #include "ctx.hpp"
 #include "curve.cuh"
 #include "hash_to_curve.hpp"
+#include "params_file.hpp"
 
 namespace {
 
@@ -366,7 +367,157 @@ static int params_generate_device(bzh_ctx* ctx, bzh_params* p, bool trace) {
     return rc;
 }
 
+// ---- Params files (include/bzh2.h; the byte layout: csrc/params_file.hpp) ---------------------------------------------
+// a table bzh_params_read made: the caller holds ctx->mu and has waited for the stream
+static void params_table_release(bzh_bases* b) {
+    if (!b) return;
+    if (b->d_xy) (void)hipFree(b->d_xy);
+    if (b->d_xy29) (void)hipFree(b->d_xy29);
+    delete b;
+}
+
+// bzh_params_read between the argument checks and the hand-over: p has k, n and its host arrays sized; the caller holds ctx->mu.
+// Fills p's two tables and host copies and *v.  On any failure the caller waits for the stream and releases what p holds.
+static int params_read_locked(bzh_ctx* ctx, const uint8_t* bytes, size_t len, int window_bits, int check, bzh_params* p, bzh_params_verdict* v) {
+    const size_t n = p->n, lanes = pf_points(n);
+    const bool lagrange = check >= BZH_PARAMS_CHECK_LAGRANGE, full = check == BZH_PARAMS_CHECK_FULL;
+    // what the host contributes, behind the strings in the one upload: the ChaCha key of r, then Params::new's w and u (Montgomery)
+    uint32_t tail[8 + 32] = {0};
+    if (lagrange) {
+        const uint8_t personal[16] = {'b', 'z', 'h', '2', '-', 'p', 'a', 'r', 'a', 'm', 's', '-', 'f', 'i', 'l', 'e'};
+        uint8_t digest[64];
+        Blake2b h;
+        h.init(64, personal);
+        h.update(bytes, len);
+        h.finalize(digest);
+        memcpy(tail, digest, 32);
+    }
+    if (full) {
+        const uint8_t msgs[2] = {1, 2};
+        uint64_t wu[16];
+        BZH_TRY(bzh_hash_to_curve_batch(nullptr, BZH_CURVE_VESTA, "Halo2-Parameters", msgs, 1, 2, BZH_FORM_MONTGOMERY, BZH_MEM_HOST, wu, nullptr));
+        memcpy(tail + 8, wu, 128);
+    }
+    // WS_STAGE (no driver below takes it): accumulators | verdict | the two sums | strings, key, w, u | decoded points | status bytes
+    // | the draws, r, intt(r) | the regenerated g and its status bytes
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t in_bytes = lanes * kPfPointBytes + sizeof(tail);
+    const size_t o_verdict = 256, o_sums = 512, o_in = 768, o_pts = o_in + pad(in_bytes), o_st = o_pts + lanes * 64, o_raw = o_st + pad(lanes),
+                 o_r = o_raw + (lagrange ? n * 64 : 0), o_ir = o_r + (lagrange ? n * 32 : 0), o_gen = o_ir + (lagrange ? n * 32 : 0),
+                 o_gst = o_gen + (full ? n * 64 : 0), total = o_gst + (full ? pad(n) : 0);
+    if (in_bytes > ((size_t)1 << 20)) BZH_TRY(pin_big_reserve(ctx, pad(in_bytes) + 2 * pad(n * 64) + 4096));   // the upload and the host copies: no recycling in between
+    void* ws = nullptr;
+    BZH_TRY(ws_ensure(ctx, WS_STAGE, total, &ws));
+    auto at = [&](size_t o) { return (uint32_t*)((char*)ws + o); };
+    uint32_t *d_in = at(o_in), *d_pts = at(o_pts), *d_sums = at(o_sums), *d_key = d_in + lanes * 8, *d_wu = d_key + 8;
+    uint8_t* d_st = (uint8_t*)at(o_st);
+    char* slot = nullptr;
+    BZH_TRY(h2d_stage(ctx, in_bytes, &slot));
+    memcpy(slot, bytes + kPfHeaderBytes, lanes * kPfPointBytes);
+    memcpy(slot + lanes * kPfPointBytes, tail, sizeof(tail));
+    BZH_TRY(h2d_commit(ctx, d_in, slot, in_bytes));
+    BZH_TRY(decompress_run(ctx, BZH_CURVE_VESTA, d_in, lanes, BZH_FORM_MONTGOMERY, d_pts, d_st));
+    // (g | u | w) and (g_lagrange | u | w | g_0), as bzh_params_create lays them out, from the decoded points where they lie
+    auto section = [&](int s) { return d_pts + pf_first_lane(s, n) * 16; };
+    for (int which = 0; which < 2; which++) {
+        bzh_bases* b = new (std::nothrow) bzh_bases();
+        if (!b) return BZH_E_OOM;
+        (which ? p->bases_lagrange : p->bases) = b;
+        b->curve = BZH_CURVE_VESTA;
+        b->n = n + 2 + (which ? 1 : 0);
+        b->device = ctx->device;
+        if (hipMalloc((void**)&b->d_xy, b->n * 64) != hipSuccess) return BZH_E_OOM;
+        BZH_TRY(xfer_launch(ctx, b->d_xy, section(which ? PF_G_LAGRANGE : PF_G), n * 64, hipMemcpyDeviceToDevice));
+        BZH_TRY(xfer_launch(ctx, b->d_xy + n * 16, section(PF_U), 64, hipMemcpyDeviceToDevice));
+        BZH_TRY(xfer_launch(ctx, b->d_xy + (n + 1) * 16, section(PF_W), 64, hipMemcpyDeviceToDevice));
+        if (which) BZH_TRY(xfer_launch(ctx, b->d_xy + (n + 2) * 16, section(PF_G), 64, hipMemcpyDeviceToDevice));
+        BZH_TRY(bases_precompute(ctx, b, window_bits));
+    }
+    PfVerdictArgs va;
+    va.d_status = d_st, va.d_points = d_pts, va.d_acc = at(0), va.d_verdict = at(o_verdict), va.n = (uint32_t)n;
+    if (lagrange) {
+        // sum_j r_j g_lagrange[j] against sum_i intt(r)_i g[i]: the matrix of the inverse group FFT is symmetric
+        uint32_t *d_raw = at(o_raw), *d_r = at(o_r), *d_ir = at(o_ir);
+        BZH_TRY(rng_rows_device(ctx, d_key, 0, n, 1, d_raw));
+        BZH_TRY(random_field(ctx, BZH_FIELD_FP, d_raw, n, d_r));
+        BZH_TRY(xfer_launch(ctx, d_ir, d_r, n * 32, hipMemcpyDeviceToDevice));
+        uint64_t omega[4];
+        BZH_TRY(bzh_field_omega(BZH_FIELD_FP, p->k, BZH_FORM_MONTGOMERY, omega));
+        BZH_TRY(ntt_run(ctx, BZH_FIELD_FP, d_ir, p->k, 1, omega, nullptr, 1, BZH_FORM_MONTGOMERY));
+        BZH_TRY(msm_run(ctx, p->bases_lagrange, d_r, n, 1, BZH_FORM_MONTGOMERY, d_sums));
+        BZH_TRY(msm_run(ctx, p->bases, d_ir, n, 1, BZH_FORM_MONTGOMERY, d_sums + 24));
+        va.d_sums = d_sums;
+    }
+    if (full) {
+        BZH_TRY(h2c_generators_run(ctx, 0, n, at(o_gen), (uint8_t*)at(o_gst)));
+        va.d_gen = at(o_gen), va.d_gen_status = (const uint8_t*)at(o_gst), va.d_wu = d_wu;
+    }
+    BZH_TRY(params_file_verdict_run(ctx, va));
+    // behind the verdict: the host copies bzh_params_points serves, canonical
+    BZH_TRY(field_convert(ctx, BZH_FIELD_FQ, d_pts, lanes * 2, 0));
+    BZH_TRY(d2h_async(ctx, v, va.d_verdict, sizeof(*v)));
+    BZH_TRY(d2h_async(ctx, p->g.data(), section(PF_G), n * 64));
+    BZH_TRY(d2h_async(ctx, p->g_lagrange.data(), section(PF_G_LAGRANGE), n * 64));
+    BZH_TRY(d2h_async(ctx, p->w, section(PF_W), 64));
+    BZH_TRY(d2h_async(ctx, p->u, section(PF_U), 64));
+    BZH_TRY(d2h_finish(ctx));
+    if (v->bits) {
+        static const char* const names[kPfSections] = {"g", "g_lagrange", "w", "u"};
+        char msg[224];
+        if (v->bits == BZH_PARAMS_BAD_LAGRANGE)
+            snprintf(msg, sizeof(msg), "bzh_params_read: refused (bits %u): g_lagrange is not the inverse group FFT of g", v->bits);
+        else
+            snprintf(msg, sizeof(msg), "bzh_params_read: refused (bits %u): %s[%u] %s, the first of %u such points%s", v->bits,
+                     names[v->section & 3], v->first_bad, (v->bits & BZH_PARAMS_BAD_DECODE) ? "does not decode to a point of the curve" : "is not Params::new's",
+                     v->n_bad, (v->bits & BZH_PARAMS_BAD_LAGRANGE) ? "; g_lagrange is not the inverse group FFT of g" : "");
+        ctx->last_error = msg;
+        return BZH_E_RANGE;
+    }
+    return BZH_OK;
+}
+
 extern "C" {
+
+int bzh_params_read(bzh_ctx* ctx, const uint8_t* bytes, size_t len, int window_bits, int check, bzh_params** out, bzh_params_verdict* verdict) {
+    if (out) *out = nullptr;
+    if (verdict) memset(verdict, 0, sizeof(*verdict));
+    if (!ctx || !bytes || !out || window_bits < 0 || check < BZH_PARAMS_CHECK_POINTS || check > BZH_PARAMS_CHECK_FULL) return BZH_E_ARG;
+    unsigned k = 0;
+    BZH_TRY(bzh_params_file_info(bytes, len, &k, nullptr));
+    if (k < 1) return BZH_E_ARG;
+    if (check == BZH_PARAMS_CHECK_FULL && !h2c_host<VestaCurve>().ok) return BZH_E_HIP;
+    std::unique_ptr<bzh_params> p(new bzh_params());
+    p->k = k;
+    p->n = (size_t)1 << k;
+    p->g.assign(p->n * 8, 0);
+    p->g_lagrange.assign(p->n * 8, 0);
+    bzh_params_verdict v = {0, 0, 0, 0};
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BZH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = params_read_locked(ctx, bytes, len, window_bits, check, p.get(), &v);
+    if (verdict) *verdict = v;
+    if (rc) {
+        (void)pin_drain(ctx);   // nothing queued reads the tables or writes p's arrays any more
+        params_table_release(p->bases);
+        params_table_release(p->bases_lagrange);
+        return rc;
+    }
+    *out = p.release();
+    return BZH_OK;
+}
+
+int bzh_params_write(bzh_ctx* ctx, const bzh_params* p, uint8_t* out, size_t cap, size_t* len) {
+    if (!p || !len) return BZH_E_ARG;
+    const size_t n = p->n, need = pf_file_bytes(n);
+    *len = need;
+    if (!out) return BZH_OK;   // the size query
+    if (!ctx || cap < need) return BZH_E_ARG;
+    for (int b = 0; b < 4; b++) out[b] = (uint8_t)(p->k >> (8 * b));
+    const uint64_t* src[kPfSections] = {p->g.data(), p->g_lagrange.data(), p->w, p->u};   // by section code
+    for (int s = 0; s < kPfSections; s++)
+        BZH_TRY(bzh_affine_compress_batch(ctx, BZH_CURVE_VESTA, src[s], pf_section_len(s, n), BZH_FORM_CANONICAL, BZH_MEM_HOST, out + pf_offset(s, 0, n)));
+    return BZH_OK;
+}
 
 int bzh_hash_to_curve(int curve, const char* domain_prefix, const uint8_t* msg, size_t len, uint64_t* out_xy) {
     if (!domain_prefix || (!msg && len) || !out_xy) return BZH_E_ARG;

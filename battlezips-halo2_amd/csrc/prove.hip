@@ -132,6 +132,16 @@ static int vk_create_t(bzh_ctx* ctx, const bzh_bases* srs, const uint8_t* blob, 
 }
 
 }  // namespace
+
+// k_chacha20_rows for a caller outside this translation unit (bzh_params_read, csrc/params.hip): see csrc/ctx.hpp
+int rng_rows_device(bzh_ctx* ctx, const uint32_t* d_keys, uint64_t counter0, size_t count, size_t batch, uint32_t* d_raw) {
+    if (!count || !batch) return BZH_OK;
+    if (batch > 65535) return BZH_E_ARG;
+    hipLaunchKernelGGL(k_chacha20_rows, dim3((unsigned)((count + 255) / 256), (unsigned)batch), dim3(256), 0, ctx->stream, d_keys, counter0, count,
+                       d_raw);
+    BZH_HIP_TRY(ctx, hipGetLastError());
+    return BZH_OK;
+}
 }  // namespace bzh
 
 namespace {

@@ -968,6 +968,64 @@ int bzh_params_generators_device(bzh_ctx* ctx, size_t first, size_t count, int f
 typedef enum { BZH_GENERATORS_HOST = 0, BZH_GENERATORS_DEVICE = 1 } bzh_generators_where;
 int bzh_params_create_with(bzh_ctx* ctx, unsigned k, const char* cache_dir, int window_bits, int generators_where, bzh_params** out);
 
+/* ---- Params files in halo2's byte format (csrc/params_file.hpp, csrc/params_file.hip, csrc/params.hip) -----------------
+ * halo2_proofs 0.2.0's Params::write / Params::read: k as a u32 little-endian, the n = 2^k points of g, the n points of
+ * g_lagrange, w, u -- every point the 32-byte to_bytes string bzh_affine_compress writes; 4 + 32 (2 n + 2) bytes.  The way a
+ * Rust caller hands over ITS Params and gets a bzh_params back, and the only SRS file the library reads that
+ * is checked.  The field order is stated from upstream's source as remembered and has NOT been compared with a file that Rust
+ * wrote; it lives in csrc/params_file.hpp alone.
+ *   bzh_params_file_info  host only, no ctx: header and length.  BZH_E_ARG: NULL bytes, len < 4, k above 24 (what
+ *                         bzh_params_generators takes), len != 4 + 32 (2 n + 2).  k and n_points may be NULL.
+ *   bzh_params_encode     host only, no ctx: canonical affine limbs (g_xy, g_lagrange_xy: n x 8; w_xy, u_xy: 8) -> the byte string.
+ *                         *len is always set to the file's size.  out == NULL: the size query, nothing else is read.  BZH_E_ARG
+ *                         with nothing written: cap below that size, a NULL point array, k above 24, a NULL len.
+ *   bzh_params_write      the same for the points of a bzh_params: they are compressed by bzh_affine_compress_batch on the ctx's
+ *                         device.  out == NULL: the size query (ctx may then be NULL).  BZH_E_ARG as above.
+ *   bzh_params_read       the byte string -> a bzh_params that cannot be told from bzh_params_create's for the same points: the
+ *                         tables (g | u | w) and (g_lagrange | u | w | g_0) with window tables of `window_bits` (0: the planner's),
+ *                         the host copies bzh_params_points serves, from_cache = 0.  `check` says how much of the file is believed:
+ *       BZH_PARAMS_CHECK_POINTS    every string is a canonical encoding of a point that is not the identity (the status of
+ *                                  bzh_affine_decompress).  Upstream's from_bytes accepts 32 zero bytes; a generator at infinity
+ *                                  is never a valid SRS, so this library refuses it.
+ *       BZH_PARAMS_CHECK_LAGRANGE  and g_lagrange is the inverse group FFT of g.  The matrix M_ji = n^-1 omega^-ij that
+ *                                  bzh_group_ifft applies is symmetric, so for any r: sum_j r_j g_lagrange[j] = sum_i intt(r)_i g[i].
+ *                                  r is drawn by Fiat-Shamir from the file -- seed = the first 32 bytes of BLAKE2b-512(personal
+ *                                  "bzh2-params-file", bytes); r_j = draw j of bzh_rng_expand(seed, ..) reduced as bzh_random_field
+ *                                  reduces it --, so the file's author cannot choose it and a wrong g_lagrange passes with
+ *                                  probability about 2^-254.  One inverse NTT and two n-term MSMs against the two tables instead
+ *                                  of a group FFT.
+ *       BZH_PARAMS_CHECK_FULL      and g, w, u are Params::new(k)'s: g is made again by bzh_params_generators_device's kernels and
+ *                                  compared limb for limb where it lies, w and u by two bzh_hash_to_curve calls on the host.  The
+ *                                  only level that protects soundness against a g whose discrete logarithms somebody knows.
+ *                         The 2 n + 2 strings go up in one copy and are decoded by bzh_affine_decompress's kernel; one kernel
+ *                         (k_pf_verdict) folds the status bytes, the comparison with the regenerated points and the comparison of
+ *                         the two sums into the 16-byte verdict, which is the one read-back the decision needs.  The host copies
+ *                         of the points are queued behind the verdict kernel and come back in the same wait.  That wait is the only
+ *                         one the call adds; bzh_bases_precompute's own waits, while it swaps a table for its window table, and a
+ *                         workspace or pinned buffer that grows on first use stay as they are.
+ *                         BZH_E_RANGE: the file is refused.  *out is NULL, everything the call allocated is freed, *verdict
+ *                         (may be NULL) says why and bzh_last_error names the section and the index.  bits: BZH_PARAMS_BAD_DECODE
+ *                         alone when a string is no point (nothing else is then decided) -- section / first_bad: the lowest such
+ *                         string in file order, n_bad: how many; else BZH_PARAMS_BAD_LAGRANGE and / or BZH_PARAMS_BAD_GENERATORS --
+ *                         with the latter section / first_bad / n_bad describe the points of g, w, u that are not Params::new's
+ *                         (file order again); with BZH_PARAMS_BAD_LAGRANGE alone section is 1 and first_bad and n_bad are 0: the
+ *                         check says that g_lagrange is wrong, not where.  An accepted file leaves the verdict all zero.
+ *                         BZH_E_ARG, nothing done: a NULL ctx, bytes or out; an unknown check; window_bits < 0; whatever
+ *                         bzh_params_file_info refuses; k = 0 (bzh_params_create takes 1 .. 24). */
+typedef enum { BZH_PARAMS_CHECK_POINTS = 0, BZH_PARAMS_CHECK_LAGRANGE = 1, BZH_PARAMS_CHECK_FULL = 2 } bzh_params_check;
+enum { BZH_PARAMS_BAD_DECODE = 1, BZH_PARAMS_BAD_LAGRANGE = 2, BZH_PARAMS_BAD_GENERATORS = 4 };
+typedef struct {
+    uint32_t bits;      /* BZH_PARAMS_BAD_* */
+    uint32_t section;   /* of first_bad: 0 g, 1 g_lagrange, 2 w, 3 u */
+    uint32_t first_bad; /* index inside the section */
+    uint32_t n_bad;
+} bzh_params_verdict;
+int bzh_params_file_info(const uint8_t* bytes, size_t len, unsigned* k, size_t* n_points);
+int bzh_params_encode(unsigned k, const uint64_t* g_xy, const uint64_t* g_lagrange_xy, const uint64_t* w_xy, const uint64_t* u_xy, uint8_t* out,
+                      size_t cap, size_t* len);
+int bzh_params_write(bzh_ctx* ctx, const bzh_params* p, uint8_t* out, size_t cap, size_t* len);
+int bzh_params_read(bzh_ctx* ctx, const uint8_t* bytes, size_t len, int window_bits, int check, bzh_params** out, bzh_params_verdict* verdict);
+
 /* ---- circuits: the reference's ShotCircuit / BoardCircuit as data + their witness synthesis -------------------------
  * The reference-side interface this replaces is `impl Circuit<pallas::Base> for {ShotCircuit, BoardCircuit}`
  * (src/circuits/shot.rs:22-53, src/circuits/board.rs:21-51): `configure` -> ShotChip::configure / BoardChip::configure
